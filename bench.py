@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/s of the Pix2Pix GCC iteration at 256x256 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the hot path over one synthetic batch of 16 paired 256x256 images per GPU:
@@ -10,17 +10,18 @@ A step = one pass of the hot path over one synthetic batch of 16 paired 256x256 
 for BASELINE.json configs[1]: student U-Net ngf 32 + selective-activation PatchGAN ndf 128, online
 teacher ngf 64 / ndf 128, hinge GAN loss, lambda_L1 100, content 50, gram 1e4, bf16 MFMA compute.
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
+The timed region is exactly K steps of the production schedule: `ms_per_step` = its wall time / K.  Weights and batches are
+seeded, so the same arguments give the same inputs on every run; --dump-outputs DIR writes what the last timed step computed.
 
 roofline: the dominant kernel family is the implicit-GEMM convolution (igemm_kernel / igemm_halo_kernel: conv fprop /
-dgrad / ConvTranspose).  Every launch of it inside the first step of the timed region is bracketed by HIP
+dgrad / ConvTranspose).  Every launch of it inside one step run just before the timed region is bracketed by HIP
 events on the launch stream (bracketing all steps costs ~6% throughput); achieved = sum of algorithmic FLOPs
 (2*M*Cout*taps*Cin, padding excluded) / sum of measured durations; peak = 2.5 PFLOP/s dense bf16 MFMA
 (MI355X_MICROARCH.md).  That step runs with the production streams (student, online teacher, auxiliary, weight
 gradients) folded onto one, so that a launch's duration is the kernel's own and not its neighbours' share of the CUs,
 under the tile plan the production schedule uses (`roofline.frac`); one more such step AFTER the timed region runs the
 plan for launches that have the chip to themselves (pair split, full-chip weight-gradient splits:
-`roofline.frac_alone_plan`).  The other
-steps of the timed region run the production schedule (profiles/: rocprofv3 summaries of `bench.py
+`roofline.frac_alone_plan`).  The steps of the timed region run the production schedule (profiles/: rocprofv3 summaries of `bench.py
 --serialize-streams`, which agree with these durations, and of the default command).
 other_configs: after the timed region and outside `value`, one short run each of BASELINE.json configs 3-5 (CycleGAN,
 SAGAN, SRGAN at their reference widths, synthetic batches, 10 warm-up + 30 timed iterations).
@@ -103,6 +104,45 @@ def one_step(model, train, val):
     model.set_input(val)
     model.clipping_mask_alpha()
     model.optimizer_netD_arch()
+
+
+DUMP_IMAGES = 16            # generated images kept per generator: 16 x 3 x 256 x 256 fp32 = 12.6 MB each
+DUMP_SAMPLE = 1 << 20       # elements kept of each network's parameters + buffers (a fixed, seeded sample): 4 MB each
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(model, path, rank):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files, for an output-for-output
+    comparison of two builds on the same arguments (same seeded weights and batches):
+        fake_B, teacher_fake_B     the student's / online teacher's generated images (get_current_visuals), first DUMP_IMAGES
+        loss_<name>                every logged loss (get_current_losses), float64 scalars
+        student_D_alpha            every architecture parameter of the student's discriminator, after the arch step + clip
+        <net>_state                student_G / student_D / teacher_G / teacher_D: the float entries of the state_dict (the
+                                   updated weights and BatchNorm running statistics) flattened in key order; DUMP_SAMPLE
+                                   positions drawn with a fixed seed when the network holds more
+    Called on every rank (the loss read is a collective under data parallelism); rank 0 writes.  Returns the result line's entry."""
+    losses = model.get_current_losses()
+    if rank != 0:
+        return None
+    T = model.teacher_model
+    arrays = {'fake_B': model.fake_B[:DUMP_IMAGES], 'teacher_fake_B': T.fake_B[:DUMP_IMAGES]}
+    arrays.update(('loss_' + k, torch.tensor(v, dtype=torch.float64)) for k, v in losses.items())
+    arrays['student_D_alpha'] = torch.cat([p.detach().reshape(-1) for n, p in model.netD.named_parameters() if n.endswith('alpha')])
+    g = torch.Generator().manual_seed(0)
+    for name, net in (('student_G', model.netG), ('student_D', model.netD), ('teacher_G', T.netG), ('teacher_D', T.netD)):
+        flat = torch.cat([v.detach().reshape(-1).float() for v in net.state_dict().values() if v.is_floating_point()])
+        if flat.numel() > DUMP_SAMPLE:
+            flat = flat[torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(flat.device)]
+        arrays[name + '_state'] = flat
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, nbytes
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    log('dumped %d arrays (%.1f MB) to %s' % (len(arrays), nbytes / 1e6, path))
+    return {'dir': path, 'arrays': sorted(arrays), 'bytes': nbytes}
 
 
 def cpu_baseline(iters=16, batch=1, budget=30.0):
@@ -378,7 +418,11 @@ def main():
     ap.add_argument('--serialize-streams', action='store_true',
                     help='run every step on one HIP stream (as the profiled steps do): for rocprofv3 runs whose per-kernel '
                          'average must be the kernel\'s own duration')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     from gcc_amd import dist as gdist
     from gcc_amd import ops
@@ -414,43 +458,45 @@ def main():
             log('first step done')
             first_losses = dict(model.get_current_losses())
     torch.cuda.synchronize()
-    log('warm-up done; timing %d steps' % args.steps)
-    if world > 1:
-        torch.distributed.barrier()
+    log('warm-up done')
     from gcc_amd import engine
-    n_prof = 0 if args.no_roofline else min(args.steps, 1)
+    n_prof = 0 if args.no_roofline else 1
     if args.serialize_streams:
         serialize_streams(model, engine, True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
     roofs = []
     gen_tags = None
+    if n_prof:
+        # profiled step, before the timed region (it runs on one stream and pays two events per launch, so it is not a step of
+        # the production schedule): a launch's duration is its own; the tile plan is the production schedule's
+        torch.cuda.synchronize()
+        serialize_streams(model, engine, True, 'production')
+        ops.PROFILE.start(steps=1)          # HIP events bracket the MFMA-kernel launches of this step
+        one_step(model, train, val)
+        ops.PROFILE.step_done()
+        r = ops.PROFILE.stop()
+        if r is not None:
+            gen_tags = ops.PROFILE.tag_stats
+        roofs.append(r)
+        torch.cuda.synchronize()
+        serialize_streams(model, engine, args.serialize_streams)
+    log('timing %d steps' % args.steps)
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
     launches_per_step = None
     for i in range(args.steps):
-        if i < n_prof:
-            # profiled step: one stream, a launch's duration is its own; the tile plan is the production schedule's
-            torch.cuda.synchronize()
-            serialize_streams(model, engine, True, 'production')
-            ops.PROFILE.start(steps=1)          # HIP events bracket the MFMA-kernel launches of this step
-        elif i == n_prof and n_prof:
-            torch.cuda.synchronize()
-            serialize_streams(model, engine, args.serialize_streams)
-        if i == n_prof:
+        if i == 0:
             ops.lib().gcc_launch_count(1)
         one_step(model, train, val)
-        if i == n_prof:
+        if i == 0:
             launches_per_step = int(ops.lib().gcc_launch_count(0))
-        if i < n_prof:
-            ops.PROFILE.step_done()
-            r = ops.PROFILE.stop()
-            if i == 0 and r is not None:
-                gen_tags = ops.PROFILE.tag_stats
-            roofs.append(r)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     log('timed region: %.3f s (%.1f ms/step)' % (dt, 1000 * dt / args.steps))
+    dumped = dump_outputs(model, args.dump_outputs, rank) if args.dump_outputs else None
     if n_prof:
         # after the timed region: one more single-stream step under the plan for launches that have the chip to themselves
         serialize_streams(model, engine, True, 'alone')
@@ -526,6 +572,8 @@ def main():
             roof['conv_roofline']['frac_of_step'] = round(roof['conv_roofline']['bound_ms'] / (1000.0 * dt / args.steps), 4)
         out['roofline'] = roof
     out['rccl_ranks'] = rccl_ranks
+    if dumped is not None:
+        out['outputs_dumped'] = dumped
     if comm is not None:
         out['allreduce'] = comm
     if world == 1 and not args.no_cpu_baseline:

@@ -27,10 +27,12 @@ Fixtures
   cyclegan_pretrain.npz CycleGAN without teacher, --lambda_weight (heavy-layer L1 sparsity), 1 iteration; ImagePool(3) sequence
   prune_resnet.npz      resnet_prune / CycleGAN get_prunenet_cfg cfgs + max_min_conv_norm; pruned MobileResnet (one with a block removed): eval + 1 iteration
   sagan_gcc.npz         SAGAN student + online teacher (spectral norm, self attention, duplicated optimizer entries): eval image, 2 x (iteration + arch step)
+  sagan_gcc_f64.npz     the same run in float64: only the losses and final states (the values behind Adam sign steps)
   srgan_gcc.npz         SRGAN student + online teacher (SRResNet, avg-pool discriminator, VGG stand-in): eval image, 2 x (iteration + arch step)
   prune_search_d8.npz   binarysearch_threshold trajectory end points with a documented thop stand-in
   prune_d8.npz          scale_prune / norm_prune cfgs + max_min_* at several thresholds (ngf 8)
 """
+import contextlib
 import copy
 import importlib.machinery
 import os
@@ -112,6 +114,31 @@ def sd_np_sampled(prefix, sd, out):
     for k, v in sd.items():
         v = v.detach().cpu().reshape(-1)
         out[prefix + k] = v[sample_idx(v.numel())].numpy().copy()
+
+
+@contextlib.contextmanager
+def float64(*models):
+    """Run the reference models in float64 from their float32 recipe weights (exactly representable).  For fixtures whose
+    tests compare elements that a first Adam step moves by +-lr whatever the size of their gradient: in float32 the sign of
+    a near-zero gradient is summation noise, which differs between CPUs (kernel choice), and so would the fixture; in
+    float64 it is fixed far below every tolerance.  Inputs drawn inside stay float32 (dtype= given); stored arrays are
+    cast back to float32 by as_float32."""
+    for m in models:
+        for v in [m] + list(vars(m).values()):
+            for mod in (v if isinstance(v, (list, tuple)) else [v]):
+                if isinstance(mod, torch.nn.Module):
+                    mod.double()
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        yield
+    finally:
+        torch.set_default_dtype(prev)
+
+
+def as_float32(out):
+    """float64 arrays of a float64 run -> float32, the dtype the fp32 fixtures store (0-d values: losses, lr stay float64)"""
+    return {k: (v.astype(np.float32) if v.dtype == np.float64 and v.ndim > 0 else v) for k, v in out.items()}
 
 
 def fixture_eval_d8():
@@ -664,12 +691,14 @@ def fixture_cyclegan_pretrain():
     A, B = (torch.rand(2, 3, 64, 64, generator=g) * 2 - 1 for _ in range(2))
     out = {'A': A.numpy(), 'B': B.numpy(), 'direction': np.array(opt.direction)}
     model.model_train()
-    model.set_input({'A': A, 'B': B, 'A_paths': ['a'], 'B_paths': ['b']})
-    model.optimize_parameters()
+    with float64(model):          # the weights after one Adam step: +-lr per element (float64: see float64())
+        model.set_input({'A': A.double(), 'B': B.double(), 'A_paths': ['a'], 'B_paths': ['b']})
+        model.optimize_parameters()
     for k, v in model.get_current_losses().items():
         out['loss.%s' % k] = np.array(v, dtype=np.float64)
     for tag, net in (('G_A', model.netG_A), ('G_B', model.netG_B), ('D_A', model.netD_A), ('D_B', model.netD_B)):
         sd_np_sampled('final.%s.' % tag, net.state_dict(), out)
+    out = as_float32(out)
     from utils.image_pool import ImagePool
     random.seed(1234)
     pool = ImagePool(3)
@@ -752,9 +781,26 @@ def fixture_prune_resnet():
 
 
 def fixture_sagan():
+    out = sagan_run(f64=False)
+    np.savez_compressed(os.path.join(HERE, 'sagan_gcc.npz'), **out)
+    print('sagan_gcc ok', {k: round(float(v), 4) for k, v in out.items() if k.startswith('it1.loss.')})
+    print('  G keys', list(out['G_keys'])[:14], '\n  D keys', list(out['D_keys']), '\n  dup G', list(out['dup_G']), '\n  dup D', list(out['dup_D']))
+
+
+def fixture_sagan_f64():
+    """the values of sagan_gcc.npz that sit behind Adam steps (beta1 = 0: sign steps) -- every logged loss of both
+    iterations and the final states -- from the same run in float64 (see float64())"""
+    out = sagan_run(f64=True)
+    out = {k: v for k, v in out.items() if '.loss.' in k or '.tloss.' in k or k.startswith('final.')}
+    np.savez_compressed(os.path.join(HERE, 'sagan_gcc_f64.npz'), **out)
+    print('sagan_gcc_f64 ok', {k: round(float(v), 4) for k, v in out.items() if k.startswith('it1.loss.')})
+
+
+def sagan_run(f64):
     """SAGANModel student (ngf 8, masked D ndf 8) + online teacher (ngf 16, ndf 16), z_dim 128, 64x64, N=4, recipe
-    weights 801..: eval image, then two iterations of optimize_parameters + arch step.  torch >= 2 rejects the
-    reference's Adam(betas=(0, 0.9)) (int 0): the script casts betas to float on the way in (SURVEY.md hazard H7)."""
+    weights 801..: eval image, then two iterations of optimize_parameters + arch step, in float32 or (f64) float64.
+    torch >= 2 rejects the reference's Adam(betas=(0, 0.9)) (int 0): the script casts betas to float on the way in
+    (SURVEY.md hazard H7)."""
     import torch.optim as optim
     real_adam = optim.Adam
 
@@ -788,42 +834,42 @@ def fixture_sagan():
         out['dup_' + tag] = np.array(sorted({names[i] for i in ids if ids.count(i) > 1 and i in names}))
     g = torch.Generator().manual_seed(90)
     z0 = torch.randn(4, 128, generator=g)
-    model.model_eval()
-    model.set_input({'z': z0, 'real_img': torch.zeros(4, 3, 64, 64), 'img_path': ['p'] * 4})
-    sdG_before = {k: v.clone() for k, v in model.netG.state_dict().items()}
-    with torch.no_grad():
-        model.forward()
-    out['eval.z'], out['eval.fake_img'] = z0.numpy(), model.fake_img.numpy().copy()
-    model.netG.load_state_dict(sdG_before)          # the eval pass moved u, v: put them back
-    model.model_train()
-    for it in range(2):
-        z, vz = torch.randn(4, 128, generator=g), torch.randn(4, 128, generator=g)
-        real, vreal = (torch.rand(4, 3, 64, 64, generator=g) * 2 - 1 for _ in range(2))
-        for n, t in (('z', z), ('vz', vz), ('real', real), ('vreal', vreal)):
-            out['it%d.%s' % (it, n)] = t.numpy()
-        model.set_input({'z': z, 'real_img': real, 'img_path': ['p'] * 4})
-        model.optimize_parameters()
-        if it == 0:
-            out['it0.fake_img'] = model.fake_img.detach().numpy().copy()
-            out['it0.Tfake_img'] = teacher.fake_img.detach().numpy().copy()
-            for j, f in enumerate(model.target_distillation_features):
-                out['it0.target.%d' % j] = f.detach().numpy().copy()
-            for j, f in enumerate(model.get_distillation_features()[:2]):
-                out['it0.sfeat.%d' % j] = f.detach().numpy().copy()
-        model.set_input({'z': vz, 'real_img': vreal, 'img_path': ['p'] * 4})
-        model.clipping_mask_alpha()
-        model.optimizer_netD_arch()
-        for k, v in model.get_current_losses().items():
-            out['it%d.loss.%s' % (it, k)] = np.array(v, dtype=np.float64)
-        for k, v in teacher.get_current_losses().items():
-            out['it%d.tloss.%s' % (it, k)] = np.array(v, dtype=np.float64)
+    f32, dt = torch.float32, (torch.float64 if f64 else torch.float32)
+    with (float64(model, teacher) if f64 else contextlib.nullcontext()):
+        model.model_eval()
+        model.set_input({'z': z0.to(dt), 'real_img': torch.zeros(4, 3, 64, 64), 'img_path': ['p'] * 4})
+        sdG_before = {k: v.clone() for k, v in model.netG.state_dict().items()}
+        with torch.no_grad():
+            model.forward()
+        out['eval.z'], out['eval.fake_img'] = z0.numpy(), model.fake_img.numpy().copy()
+        model.netG.load_state_dict(sdG_before)          # the eval pass moved u, v: put them back
+        model.model_train()
+        for it in range(2):
+            z, vz = torch.randn(4, 128, generator=g, dtype=f32), torch.randn(4, 128, generator=g, dtype=f32)
+            real, vreal = (torch.rand(4, 3, 64, 64, generator=g, dtype=f32) * 2 - 1 for _ in range(2))
+            for n, t in (('z', z), ('vz', vz), ('real', real), ('vreal', vreal)):
+                out['it%d.%s' % (it, n)] = t.numpy()
+            model.set_input({'z': z.to(dt), 'real_img': real.to(dt), 'img_path': ['p'] * 4})
+            model.optimize_parameters()
+            if it == 0:
+                out['it0.fake_img'] = model.fake_img.detach().numpy().copy()
+                out['it0.Tfake_img'] = teacher.fake_img.detach().numpy().copy()
+                for j, f in enumerate(model.target_distillation_features):
+                    out['it0.target.%d' % j] = f.detach().numpy().copy()
+                for j, f in enumerate(model.get_distillation_features()[:2]):
+                    out['it0.sfeat.%d' % j] = f.detach().numpy().copy()
+            model.set_input({'z': vz.to(dt), 'real_img': vreal.to(dt), 'img_path': ['p'] * 4})
+            model.clipping_mask_alpha()
+            model.optimizer_netD_arch()
+            for k, v in model.get_current_losses().items():
+                out['it%d.loss.%s' % (it, k)] = np.array(v, dtype=np.float64)
+            for k, v in teacher.get_current_losses().items():
+                out['it%d.tloss.%s' % (it, k)] = np.array(v, dtype=np.float64)
     for tag, net in (('sG', model.netG), ('sD', model.netD), ('tG', teacher.netG), ('tD', teacher.netD)):
         sd_np_sampled('final.%s.' % tag, net.state_dict(), out)
     for i, t in enumerate(model.transform_convs):
         out['final.T.%d' % i] = t.weight.detach().numpy().copy()
-    np.savez_compressed(os.path.join(HERE, 'sagan_gcc.npz'), **out)
-    print('sagan_gcc ok', {k: round(float(v), 4) for k, v in out.items() if k.startswith('it1.loss.')})
-    print('  G keys', list(out['G_keys'])[:14], '\n  D keys', list(out['D_keys']), '\n  dup G', list(out['dup_G']), '\n  dup D', list(out['dup_D']))
+    return as_float32(out)
 
 
 VGG_STANDIN = (8, 8, 'M', 16, 16, 'M', 32, 32, 32, 32, 'M', 64, 64, 64, 64, 'M', 64, 64, 64, 64, 'M')
@@ -1265,6 +1311,6 @@ if __name__ == '__main__':
     only = sys.argv[1:]            # e.g. "make_fixtures.py cyclegan cyclegan_pretrain"; none = all
     import_reference()
     for fn in (fixture_options, fixture_ops, fixture_eval_d8, fixture_gcc_d6, fixture_pretrain_d6, fixture_prune_d8,
-               fixture_pruned_d8, fixture_pruned_removed_d8, fixture_prune_search, fixture_resnet_gcc, fixture_cyclegan, fixture_cyclegan_pretrain, fixture_prune_resnet, fixture_sagan, fixture_srgan, fixture_prune_search_gan, fixture_checkpoint, fixture_checkpoint_other, fixture_metric, fixture_pipeline, fixture_srgan_content):
+               fixture_pruned_d8, fixture_pruned_removed_d8, fixture_prune_search, fixture_resnet_gcc, fixture_cyclegan, fixture_cyclegan_pretrain, fixture_prune_resnet, fixture_sagan, fixture_sagan_f64, fixture_srgan, fixture_prune_search_gan, fixture_checkpoint, fixture_checkpoint_other, fixture_metric, fixture_pipeline, fixture_srgan_content):
         if not only or fn.__name__[len('fixture_'):] in only:
             fn()

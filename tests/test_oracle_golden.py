@@ -17,6 +17,10 @@ def load(golden_dir, name):
     return np.load(os.path.join(golden_dir, name), allow_pickle=False)
 
 
+def as_dtype(sd, dtype):
+    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+
+
 def sd_from(z, prefix):
     sd = OrderedDict()
     for k in z.files:
@@ -439,9 +443,12 @@ def test_cyclegan_pretrain_l1_sparsity_and_image_pool(golden_dir):
     z = load(golden_dir, 'cyclegan_pretrain.npz')
     opt = O.Opt(ngf=8, ndf=8, direction=str(z['direction']), gan_mode='lsgan', lambda_weight=1e-3)
     gs, ds = O.mobile_resnet_shapes(8), O.patchgan_shapes(8, 3, False, norm='instance')
-    m = O.CycleGANOracle(opt, {'A': recipe_state_dict(gs, 641), 'B': recipe_state_dict(gs, 642)},
-                         {'A': recipe_state_dict(ds, 643), 'B': recipe_state_dict(ds, 644)}, masked=False)
-    m.set_input(torch.from_numpy(z['A']), torch.from_numpy(z['B']))
+    # float64, as the fixture (make_fixtures.float64): the first Adam step moves every weight by +-lr, and the sign of a
+    # near-zero gradient is float32 summation noise that differs between CPUs
+    f64 = torch.float64
+    m = O.CycleGANOracle(opt, {'A': as_dtype(recipe_state_dict(gs, 641), f64), 'B': as_dtype(recipe_state_dict(gs, 642), f64)},
+                         {'A': as_dtype(recipe_state_dict(ds, 643), f64), 'B': as_dtype(recipe_state_dict(ds, 644), f64)}, masked=False)
+    m.set_input(torch.from_numpy(z['A']).double(), torch.from_numpy(z['B']).double())
     m.optimize_parameters()
     for k in z.files:
         if k.startswith('loss.'):
@@ -457,17 +464,17 @@ def test_cyclegan_pretrain_l1_sparsity_and_image_pool(golden_dir):
         assert pool.query(imgs).reshape(-1).tolist() == z['pool.returned'][step].tolist(), step
 
 
-def build_sagan_oracle(z):
-    """SAGAN student (ngf 8, masked D ndf 8) + teacher (ngf 16 / ndf 16) with the recipe weights of sagan_gcc.npz"""
+def build_sagan_oracle(z, dtype=torch.float32):
+    """SAGAN student (ngf 8, masked D ndf 8) + teacher (ngf 16 / ndf 16) with the recipe weights of sagan_gcc.npz, in `dtype`"""
     opt = O.Opt(ngf=8, ndf=8, teacher_ngf=16, teacher_ndf=16, gan_mode=str(z['gan_mode']), lr=float(z['lr']),
                 lambda_L1=1.0, lambda_content=1.0, lambda_gram=1.0)
-    teacher = O.SAGANOracle(opt, recipe_state_dict(O.sagan_generator_shapes(16), 803),
-                            recipe_state_dict(O.sagan_discriminator_shapes(16, False), 804), masked=False)
-    sD = recipe_state_dict(O.sagan_discriminator_shapes(8, True), 802)
+    teacher = O.SAGANOracle(opt, as_dtype(recipe_state_dict(O.sagan_generator_shapes(16), 803), dtype),
+                            as_dtype(recipe_state_dict(O.sagan_discriminator_shapes(16, False), 804), dtype), masked=False)
+    sD = as_dtype(recipe_state_dict(O.sagan_discriminator_shapes(8, True), 802), dtype)
     sD['l1.1.alpha'][0] = 0.3
     sD['l3.1.alpha'][2] = 0.5
-    T = [recipe_transform(int(t), int(s_), 810 + i) for i, (t, s_) in enumerate(z['T_shapes'])]
-    m = O.SAGANOracle(opt, recipe_state_dict(O.sagan_generator_shapes(8), 801), sD, T, masked=True, teacher=teacher)
+    T = [recipe_transform(int(t), int(s_), 810 + i).to(dtype) for i, (t, s_) in enumerate(z['T_shapes'])]
+    m = O.SAGANOracle(opt, as_dtype(recipe_state_dict(O.sagan_generator_shapes(8), 801), dtype), sD, T, masked=True, teacher=teacher)
     return m, teacher, opt
 
 
@@ -476,17 +483,20 @@ def test_sagan_two_iterations(golden_dir):
     assert list(O.sagan_generator_shapes(8).keys()) == [str(k) for k in z['G_keys']]
     assert list(O.sagan_discriminator_shapes(8, True).keys()) == [str(k) for k in z['D_keys']]
     assert list(O.sagan_discriminator_shapes(16, False).keys()) == [str(k) for k in z['TD_keys']]
-    m, teacher, opt = build_sagan_oracle(z)
+    # float64 (make_fixtures.float64): iteration 1 sits behind Adam sign steps.  The losses and final states are checked
+    # against the reference's float64 run (sagan_gcc_f64.npz), the values ahead of the first step against its float32 run
+    z64 = load(golden_dir, 'sagan_gcc_f64.npz')
+    m, teacher, opt = build_sagan_oracle(z, torch.float64)
     # duplicated optimizer entries (hazard H5); the generator's u, v are listed too but never receive a gradient
     assert sorted(m.G_dup) == sorted(str(k) for k in z['dup_G'] if not (str(k).endswith('_u') or str(k).endswith('_v')))
     assert sorted(m.D_dup) == sorted(str(k) for k in z['dup_D'])
     # eval image on a copy (the pass moves u, v)
     G0 = {k: v.clone() for k, v in m.G.items()}
     with torch.no_grad():
-        out = O.sagan_generator_forward(G0, torch.from_numpy(z['eval.z']), train=False)
+        out = O.sagan_generator_forward(G0, torch.from_numpy(z['eval.z']).double(), train=False)
     np.testing.assert_allclose(out.numpy(), z['eval.fake_img'], atol=2e-5)
     for it in range(2):
-        m.set_input(torch.from_numpy(z['it%d.z' % it]), torch.from_numpy(z['it%d.real' % it]))
+        m.set_input(torch.from_numpy(z['it%d.z' % it]).double(), torch.from_numpy(z['it%d.real' % it]).double())
         m.optimize_parameters()
         if it == 0:
             np.testing.assert_allclose(m.fake_img.numpy(), z['it0.fake_img'], atol=2e-5)
@@ -497,13 +507,13 @@ def test_sagan_two_iterations(golden_dir):
             for j in range(2):
                 ref = z['it0.sfeat.%d' % j]
                 np.testing.assert_allclose(list(m.g_feats.values())[j].detach().numpy(), ref, atol=2e-5 + 1e-4 * np.abs(ref).max())
-        m.set_input(torch.from_numpy(z['it%d.vz' % it]), torch.from_numpy(z['it%d.vreal' % it]))
+        m.set_input(torch.from_numpy(z['it%d.vz' % it]).double(), torch.from_numpy(z['it%d.vreal' % it]).double())
         m.clipping_mask_alpha()
         m.optimizer_netD_arch()
-        for k in z.files:
+        for k in z64.files:
             for pre, who in (('it%d.loss.' % it, m), ('it%d.tloss.' % it, teacher)):
                 if k.startswith(pre):
-                    name, ref = k[len(pre):], float(z[k])
+                    name, ref = k[len(pre):], float(z64[k])
                     # iteration 1 sits behind Adam steps with beta1 = 0 (pure sign steps of 4e-4, twice for the
                     # duplicated entries): elements with a ~0 gradient amplify fp32 summation noise into the losses
                     tol = 2e-4 if it == 0 else 1.5e-3
@@ -514,12 +524,12 @@ def test_sagan_two_iterations(golden_dir):
     # zero-gradient parameters of the discriminators: key bias (softmax is shift invariant) and, with every hinge term
     # active, the value bias of attn2 (the real and fake passes cancel)
     skipD = lambda n: n.endswith('key_conv.bias') or n == 'attn2.value_conv.bias'
-    _compare_sd(m.G, z, 'final.sG.', skip=skipG, **kw)
-    _compare_sd(teacher.G, z, 'final.tG.', skip=skipG, **kw)
-    _compare_sd(m.D, z, 'final.sD.', skip=skipD, **kw)
-    _compare_sd(teacher.D, z, 'final.tD.', skip=skipD, **kw)
+    _compare_sd(m.G, z64, 'final.sG.', skip=skipG, **kw)
+    _compare_sd(teacher.G, z64, 'final.tG.', skip=skipG, **kw)
+    _compare_sd(m.D, z64, 'final.sD.', skip=skipD, **kw)
+    _compare_sd(teacher.D, z64, 'final.tD.', skip=skipD, **kw)
     for i in range(2):
-        np.testing.assert_allclose(m.T[i].detach().numpy(), z['final.T.%d' % i], atol=1e-4)
+        np.testing.assert_allclose(m.T[i].detach().numpy(), z64['final.T.%d' % i], atol=1e-4)
 
 
 VGG_STANDIN = (8, 8, 'M', 16, 16, 'M', 32, 32, 32, 32, 'M', 64, 64, 64, 64, 'M', 64, 64, 64, 64)
