@@ -8,11 +8,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GCC_HIP_LIB') or os.path.join(_HERE, 'libgcc_hip.so')     # GCC_HIP_LIB: another build of the same ABI (A/B runs)
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
-GCC_HIP_ABI = 603
+GCC_HIP_ABI = 604       # include/gcc_hip.h GCC_HIP_ABI: the generation of struct layouts / option ids these bindings were written for
 WGRAD_GROUP_MAX = 32     # include/gcc_hip.h GCC_WGRAD_GROUP_MAX
 CHANSUM_GROUP_MAX = 24   # include/gcc_hip.h GCC_CHANSUM_GROUP_MAX
 SPECTRAL_GROUP_MAX = 8    # include/gcc_hip.h GCC_SPECTRAL_GROUP_MAX
-CHANSUM_SMALL_MAX_PIXELS = 16384     # include/gcc_hip.h GCC_HIP_ABI: the generation of struct layouts / option ids these bindings were written for
+CHANSUM_SMALL_MAX_PIXELS = 16384     # include/gcc_hip.h GCC_CHANSUM_SMALL_MAX_PIXELS
 
 
 class GccError(RuntimeError):
@@ -96,14 +96,9 @@ class adam_chunk_t(C.Structure):
 
 
 # gcc_set_option ids (enum in include/gcc_hip.h)
-(OPT_IGEMM_GLDS, OPT_IGEMM_HEAD, OPT_IGEMM_THIN, OPT_WGRAD_BIG, OPT_BN_SWEEPS, OPT_BN_MAXBLK, OPT_BN_REDUCE_THREADS,
- OPT_BN_REDUCE_CAP, OPT_INORM_LPP, OPT_IGEMM_FORCE_BC, OPT_IGEMM_FORCE_KSPLIT, OPT_IGEMM_NARROW, OPT_WGRAD_BIG_MIN_TILES,
- OPT_FUSE_BN, OPT_BN_BWD_SMALL, OPT_WGRAD_ROW_TABLE, OPT_IGEMM_HALO, OPT_FUSE_BN_PARTIAL_KB, OPT_INORM_GRID, OPT_IGEMM_STAGES,
- OPT_WGRAD_TS, OPT_HALO_XCD_COLS) = range(22)
-OPT_COUNT = 22
-OPT_NAMES = ('IGEMM_GLDS', 'IGEMM_HEAD', 'IGEMM_THIN', 'WGRAD_BIG', 'BN_SWEEPS', 'BN_MAXBLK', 'BN_REDUCE_THREADS', 'BN_REDUCE_CAP',
-             'INORM_LPP', 'IGEMM_FORCE_BC', 'IGEMM_FORCE_KSPLIT', 'IGEMM_NARROW', 'WGRAD_BIG_MIN_TILES', 'FUSE_BN', 'BN_BWD_SMALL',
-             'WGRAD_ROW_TABLE', 'IGEMM_HALO', 'FUSE_BN_PARTIAL_KB', 'INORM_GRID', 'IGEMM_STAGES', 'WGRAD_TS', 'HALO_XCD_COLS')
+(OPT_IGEMM_THIN, OPT_FUSE_BN, OPT_BN_BWD_SMALL, OPT_IGEMM_HALO, OPT_INORM_GRID, OPT_WGRAD_TS, OPT_HALO_XCD_COLS) = range(7)
+OPT_COUNT = 7
+OPT_NAMES = ('IGEMM_THIN', 'FUSE_BN', 'BN_BWD_SMALL', 'IGEMM_HALO', 'INORM_GRID', 'WGRAD_TS', 'HALO_XCD_COLS')
 
 _P = C.c_void_p
 _I = C.c_int

@@ -29,10 +29,9 @@
 
 namespace gcc_igemm {
 
-// GLDS = true : tiles are staged global -> LDS directly (buffer_load ... lds, 1 KiB per wave-instruction,
-//               XOR swizzle applied on the per-lane SOURCE address, zero fill by the descriptor range
-//               check), one barrier per k-step: no staging VGPRs, no ds_write traffic.
-// GLDS = false: register-staged variant (kept for A/B measurement).
+// Tiles are staged global -> LDS directly (buffer_load ... lds, 1 KiB per wave-instruction, XOR swizzle applied on the
+// per-lane SOURCE address, zero fill by the descriptor range check), one barrier per k-step: no staging VGPRs, no ds_write
+// traffic.
 #ifdef GCC_CLOCK_PROBE
 // Diagnostic build only (scratch/probe_clock.py; never part of libgcc_hip.so): the shader clock the chip holds inside the
 // main loop = d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, 'DVFS give-back' item 6), one stamp pair per
@@ -44,11 +43,10 @@ __device__ unsigned long long g_clock_probe[4096][8];
 // tiles of 32 / 64 columns on the uniform-tap path): two k-steps in flight.  The U-Net's mid layers run these tiles on 256-512
 // workgroups with 8-32 k-steps of 8-16 MFMAs per wave: a k-step was ~0.85 us of which ~0.06 us is matrix work -- the step waits
 // for the loads it issued one step earlier (profiles/r4f_unet_student_chain.txt: d3 27 us for 32 steps).
-template <int BP, int BC, bool GLDS, bool UT, int NS = 2>
+template <int BP, int BC, bool UT, int NS = 2>
 __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams p) {
     using C = Cfg<BP, BC>;
-    static_assert(GLDS || BP == 128, "register staging is only kept for the 128-pixel tile");
-    static_assert(NS == 2 || (GLDS && UT && BP == 128 && (BC == 32 || BC == 64)), "deeper loops: uniform-tap 128 x {32, 64} tiles");
+    static_assert(NS == 2 || (UT && BP == 128 && (BC == 32 || BC == 64)), "deeper loops: uniform-tap 128 x {32, 64} tiles");
     constexpr int NT = C::NT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sA = smem;                          // pixels  [NS][BP][128 B]
@@ -111,17 +109,16 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc((void*)srcp, 0, p.src_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_wgt = __builtin_amdgcn_make_buffer_rsrc((void*)wgtp, 0, p.wgt_bytes, 0x00020000);
 
-    // ---- per-thread gather rows (4 pixel rows, fixed 16-B chunk column) ----------------------
-    // register staging: row = (tid>>3) + 32*i, chunk = tid&7 (swizzled on the LDS write)
-    // LDS-DMA        : wave-instruction q = wave*4+i covers rows 8q..8q+7; lane -> row 8q + (lane>>3),
-    //                  physical chunk lane&7, which must hold logical chunk (lane&7) ^ (row&7)
-    const int chunk = GLDS ? ((lane & 7) ^ (lane >> 3)) : (tid & 7);
+    // ---- per-thread gather rows (fixed 16-B chunk column) -----------------------------------
+    // wave-instruction q = wave*4+i covers rows 8q..8q+7; lane -> row 8q + (lane>>3), physical chunk lane&7, which must
+    // hold logical chunk (lane&7) ^ (row&7)
+    const int chunk = (lane & 7) ^ (lane >> 3);
     constexpr int AI = C::AI;
-    static_assert(AI <= 8 && (GLDS || AI == 4), "pixel staging instructions per wave");
+    static_assert(AI <= 8, "pixel staging instructions per wave");
     int a_off[8], a_iy[8], a_ix[8];      // byte offset of the row's (iy0, ix0) pixel (+ chunk), and iy0 / ix0 (first AI used)
 #pragma unroll
     for (int i = 0; i < AI; i++) {
-        const int rloc = GLDS ? ((wave * AI + i) * 8 + (lane >> 3)) : ((tid >> 3) + 32 * i);
+        const int rloc = (wave * AI + i) * 8 + (lane >> 3);
         const int m = m0 + rloc;
         if (m < M) {
             const int n = m / (Hg * Wg);
@@ -137,14 +134,13 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
     }
     // weight rows of this thread
     constexpr int WPW = C::WPW;                        // LDS-DMA weight instructions per wave (0: waves < WI issue one)
-    constexpr int W_N = GLDS ? (WPW > 0 ? WPW : 1) : C::W_CHUNKS;
+    constexpr int W_N = C::WN;
     int w_off[W_N];
     bool w_ok[W_N];
 #pragma unroll
     for (int i = 0; i < W_N; i++) {
-        const int wr = GLDS ? ((wave * (WPW > 0 ? WPW : 1) + i) * 8 + (lane >> 3)) : ((tid >> 3) + 32 * i);
-        const int row = n0 + wr;
-        w_ok[i] = row < p.Cout && (GLDS || BC >= 32 || wr < BC);
+        const int row = n0 + (wave * (WPW > 0 ? WPW : 1) + i) * 8 + (lane >> 3);
+        w_ok[i] = row < p.Cout;
         w_off[i] = row * p.ldw * 2 + (UT ? chunk * 16 : 0);
     }
 
@@ -162,10 +158,7 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
         tb = tap0 - ta * TB;
     }
 
-    i32x4 ra[GLDS ? 1 : 4];
-    i32x4 rw[GLDS ? 1 : C::W_CHUNKS];
-
-    // issue the global loads of the next k-step (in order); GLDS: straight into LDS stage `stage`
+    // issue the global loads of the next k-step (in order), straight into LDS stage `stage`
     auto issue_loads = [&](int stage) {
         const bool kval = ta < TA;
         const int dyo = ta * dstep, dxo = tb * dstep;
@@ -175,27 +168,15 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
         for (int i = 0; i < AI; i++) {
             const bool ok = kval && (unsigned)(a_iy[i] + dyo) < (unsigned)p.Hs && (unsigned)(a_ix[i] + dxo) < (unsigned)p.Ws;
             const uint32_t off = ok ? (uint32_t)(a_off[i] + pix_off) : OOB;
-            if constexpr (GLDS) {
-                char* dst = sA + stage * (BP * BK * 2) + (wave * AI + i) * 1024;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, LDS_PTR(void, dst), 16, off, 0, 0, 0);
-            } else {
-                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_src, off, 0, 0);
-            }
+            char* dst = sA + stage * (BP * BK * 2) + (wave * AI + i) * 1024;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, LDS_PTR(void, dst), 16, off, 0, 0, 0);
         }
-        if constexpr (GLDS) {
-            if (WPW > 0 || wave < C::WI) {       // wave-uniform
+        if (WPW > 0 || wave < C::WI) {       // wave-uniform
 #pragma unroll
-                for (int i = 0; i < W_N; i++) {
-                    const uint32_t off = (kval && w_ok[i]) ? (uint32_t)(w_off[i] + wt_off) : OOB;
-                    char* dst = sW + stage * (BC * BK * 2) + (wave * (WPW > 0 ? WPW : 1) + i) * 1024;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_wgt, LDS_PTR(void, dst), 16, off, 0, 0, 0);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < C::W_CHUNKS; i++) {
+            for (int i = 0; i < W_N; i++) {
                 const uint32_t off = (kval && w_ok[i]) ? (uint32_t)(w_off[i] + wt_off) : OOB;
-                rw[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_wgt, off, 0, 0);
+                char* dst = sW + stage * (BC * BK * 2) + (wave * (WPW > 0 ? WPW : 1) + i) * 1024;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_wgt, LDS_PTR(void, dst), 16, off, 0, 0, 0);
             }
         }
         // advance to the next k-step
@@ -204,23 +185,6 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
             if (cc == p.Ct) { cc = 0; if (++tb == TB) { tb = 0; ++ta; } }
         } else {
             while (cc >= p.Ct) { cc -= p.Ct; if (++tb == TB) { tb = 0; ++ta; } }
-        }
-    };
-
-    auto write_lds = [&](int stage) {
-        if constexpr (!GLDS) {
-            char* a = sA + stage * (BP * BK * 2);
-            char* w = sW + stage * (BC * BK * 2);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = (tid >> 3) + 32 * i;
-                *(i32x4*)(a + row * 128 + ((chunk ^ (row & 7)) << 4)) = ra[i];
-            }
-#pragma unroll
-            for (int i = 0; i < C::W_CHUNKS; i++) {
-                const int row = (tid >> 3) + 32 * i;
-                if (BC >= 32 || row < BC) *(i32x4*)(w + row * 128 + ((chunk ^ (row & 7)) << 4)) = rw[i];
-            }
         }
     };
 
@@ -272,11 +236,11 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
         __builtin_amdgcn_sched_group_barrier(0x008, 2 * MFMAS - READS * MPR, 0);
     };
 
-    if constexpr (GLDS && UT) {
+    if constexpr (UT) {
         // Uniform-tap fast path: a tap spans Ct/64 consecutive k-steps, so the per-row source offsets
         // (bounds checks included) are computed once per tap and then just advance by 128 bytes per
         // k-step; the loop body is 8 LDS-DMA + 8 adds + 16 ds_read + 32 MFMA per wave.
-        static_assert(C::WN_GLDS <= 8, "weight staging instructions per wave");
+        static_assert(C::WN <= 8, "weight staging instructions per wave");
         uint32_t cur_a[8], cur_w[8];   // literal bound on purpose: with a template-dependent bound hipcc (ROCm 7.2)
                                        // silently drops the host stub of this instantiation
         int left;                                  // k-steps left in the current tap (scalar)
@@ -455,7 +419,7 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
             }
         }
 #endif
-    } else if constexpr (GLDS) {
+    } else {
         // one barrier per k-step: [tile kt landed for every wave AND everyone left tile kt-1] ->
         // issue tile kt+1 into the buffer tile kt-1 occupied -> compute tile kt while it flies
 #ifdef GCC_CLOCK_PROBE
@@ -481,21 +445,6 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
             }
         }
 #endif
-    } else {
-        // registers hold tile t+1 while LDS[t&1] is consumed
-        issue_loads(0);
-        write_lds(0);
-        if (nk > 1) issue_loads(0);
-        __syncthreads();
-        for (int kt = 0; kt < nk; kt++) {
-            const int cur = kt & 1;
-            if (kt + 1 < nk) {
-                write_lds(cur ^ 1);                 // tile kt+1 (its loads were issued one step ago)
-                if (kt + 2 < nk) issue_loads(0);
-            }
-            compute(cur);
-            __syncthreads();
-        }
     }
 
     if constexpr (BP == 256 && BC == 256) {
@@ -734,12 +683,6 @@ struct SplitPlan { int ksplit, kper; };
 // split only launches that cannot fill the chip and have a long K loop
 static SplitPlan plan_ksplit(long blocks, int nk, int max_slices = 1 << 30) {
     SplitPlan sp = {1, nk};
-    if (const int f = gcc_opt(GCC_OPT_IGEMM_FORCE_KSPLIT)) {          // tuning hook
-        const int s = f > nk ? nk : f;
-        sp.kper = (nk + s - 1) / s;
-        sp.ksplit = (nk + sp.kper - 1) / sp.kper;
-        return sp;
-    }
     if (blocks >= 128 || nk < 16) return sp;
     int s = (int)((1024 + blocks - 1) / blocks);
     if (s > nk / 4) s = nk / 4;
@@ -751,44 +694,34 @@ static SplitPlan plan_ksplit(long blocks, int nk, int max_slices = 1 << 30) {
     return sp;
 }
 
-static bool use_glds() { return gcc_opt(GCC_OPT_IGEMM_GLDS) != 0; }
-
 template <int BP, int BC>
 int launch(const IgemmParams& p, int phases, int batch, hipStream_t st) {
     using C = Cfg<BP, BC>;
     static std::once_flag attr_once;       // one-time kernel attribute (idempotent; once per instantiation)
     std::call_once(attr_once, [] {
-        hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if constexpr (BP == 128)
-            hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+        hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+        hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
     });
     dim3 grid(p.mtiles_max * p.ntiles, p.ksplit > 1 ? p.ksplit : batch, phases);
     const bool ut = (p.Ct % BK) == 0;
     bool launched = false;
     if constexpr (BP == 128 && (BC == 32 || BC == 64)) {
-        // three LDS stages (two k-steps in flight) for the short-tile layers: GCC_OPT_IGEMM_STAGES
-        if (ut && use_glds() && gcc_opt(GCC_OPT_IGEMM_STAGES) >= 3 && !(GCC_DIAG(p.debug) & 14)) {
+        // three LDS stages (two k-steps in flight) for the short-tile layers
+        if (ut && !(GCC_DIAG(p.debug) & 14)) {
             constexpr int LDS3 = 3 * (BP + BC) * BK * 2 > C::LDS_BYTES_EPI ? 3 * (BP + BC) * BK * 2 : C::LDS_BYTES_EPI;
             static std::once_flag attr3;
             std::call_once(attr3, [] {
-                hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, true, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
+                hipFuncSetAttribute((const void*)igemm_kernel<BP, BC, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
             });
-            hipLaunchKernelGGL((igemm_kernel<BP, BC, true, true, 3>), grid, dim3(C::NT), LDS3, st, p);
-            launched = true;
-        }
-    }
-    if constexpr (BP == 128) {
-        if (!use_glds()) {
-            hipLaunchKernelGGL((igemm_kernel<BP, BC, false, false>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
+            hipLaunchKernelGGL((igemm_kernel<BP, BC, true, 3>), grid, dim3(C::NT), LDS3, st, p);
             launched = true;
         }
     }
     if (!launched) {
         if (ut)
-            hipLaunchKernelGGL((igemm_kernel<BP, BC, true, true>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
+            hipLaunchKernelGGL((igemm_kernel<BP, BC, true>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
         else
-            hipLaunchKernelGGL((igemm_kernel<BP, BC, true, false>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
+            hipLaunchKernelGGL((igemm_kernel<BP, BC, false>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
     }
     GCC_CHECK_LAUNCH();
     if (p.ksplit > 1 && !p.raw_partial && !p.pair) {
@@ -821,7 +754,7 @@ static TilePlan select_tile(const gcc_conv_plan_t& pl, size_t max_rows, int Cout
     else if (Cout > 32) { t.BC = 64; t.ntiles = 1; }
     else if (Cout > 16) { t.BC = 32; t.ntiles = 1; }
     else { t.BC = 16; t.ntiles = 1; }
-    if (gcc_opt(GCC_OPT_IGEMM_NARROW) && batch == 1 && t.BC > 32) {
+    if (batch == 1 && t.BC > 32) {
         // Mid-size layers (the U-Nets at 32 x 32 .. 8 x 8): 128 x 128 tiles leave most CUs without a workgroup.  Measured
         // per shape inside the step (profiles/r02_j, r02_m):  (a) K loop of <= 64 steps: the widest tile that still gives
         // every CU a workgroup, un-split (one kernel instead of partials + fold + statistics);  (b) longer loops on >= 8
@@ -837,15 +770,12 @@ static TilePlan select_tile(const gcc_conv_plan_t& pl, size_t max_rows, int Cout
             t.BC = 64; t.ntiles = cdiv(Cout, 64); t.max_slices = 8;
         }
     }
-    if (const int f = gcc_opt(GCC_OPT_IGEMM_FORCE_BC)) {               // tuning hook
-        if (f == 16 || f == 32 || f == 64 || f == 128) { t.BC = f; t.ntiles = cdiv(Cout, f); }
-    }
     // the plan (gcc_conv_t.plan): which tile families are allowed, minimum number of 256-pixel tiles, minimum K depth
     const int g_big_tiles = plan_or(pl.tile_families, PLAN_TILE_FAMILIES) - 1, g_big_min = plan_or(pl.big_min, PLAN_BIG_MIN),
               g_big_nk = plan_or(pl.big_nk, PLAN_BIG_NK);
     // 256-pixel tiles (one 8-wave workgroup per CU) when they still fill the chip and the K loop is
     // long enough to amortise the un-overlapped prologue / epilogue of a lone workgroup
-    if (g_big_tiles && use_glds() && batch == 1 && Cout >= 128 && nk >= g_big_nk) {
+    if (g_big_tiles && batch == 1 && Cout >= 128 && nk >= g_big_nk) {
         const long m256 = (long)((max_rows + 255) / 256);
         if (g_big_tiles >= 2 && Cout % 256 == 0 && m256 * (Cout / 256) * phases >= g_big_min) {
             t.BP = 256; t.BC = 256; t.ntiles = Cout / 256;
@@ -951,11 +881,10 @@ __global__ __launch_bounds__(256) void head_gather_kernel(const HeadArgs a) {
     }
 }
 
-static bool head_enabled() { return gcc_opt(GCC_OPT_IGEMM_HEAD) != 0; }
 // rows of the tap matrix / bytes of the gathered dy matrix
 static size_t head_rows(const gcc_conv_t* c) { return (size_t)c->N * c->H * c->W; }
 static bool head_shape(const gcc_conv_t* c) {
-    return c->Co == 1 && c->KH * c->KW >= 4 && c->KH * c->KW <= 16 && ceil8(c->Ci) >= 256 && head_enabled();
+    return c->Co == 1 && c->KH * c->KW >= 4 && c->KH * c->KW <= 16 && ceil8(c->Ci) >= 256;
 }
 size_t gcc_internal_head_gather_bytes(const gcc_conv_t* c) { return head_shape(c) ? head_rows(c) * c->KH * c->KW * 8 * 2 : 0; }
 int gcc_internal_head_gather(const gcc_conv_t* c, const void* dy, void* g, hipStream_t st) {
@@ -1482,6 +1411,10 @@ int gcc_internal_thinout_dgrad(const gcc_conv_t* c, const void* dy, const void* 
 int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep, hipStream_t st);
 int gcc_internal_ring3_rows(const gcc_conv_t* c, int dgrad);
 bool gcc_internal_ring3_routed(const gcc_conv_t* c, int dgrad, const gcc_epilogue_t* ep);
+
+// cap on the fp32 partial tiles of a split BatchNorm layer (gcc_internal_igemm's fold, gcc_conv_bn_act's fused fold)
+constexpr size_t FUSE_BN_PARTIAL_BYTES = (size_t)4096 * 1024;
+
 int gcc_internal_igemm(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep,
                        int batch, long src_bstride, long wgt_bstride, long dst_bstride, hipStream_t st) {
     GCC_ENTER();
@@ -1632,10 +1565,10 @@ int gcc_internal_igemm(const gcc_conv_t* c, int dgrad, const void* src, const vo
     if (batch == 1 && tp.BP == 128 && ep && ep->workspace) {
         SplitPlan sp = plan_ksplit((long)p.mtiles_max * p.ntiles * phases, conv_nk(c, dgrad), tp.max_slices);
         if (sp.ksplit > 4 && stats_out) {
-            // a BatchNorm layer's slices are all read back by the fold kernel: cap them at GCC_OPT_FUSE_BN_PARTIAL_KB of partial
+            // a BatchNorm layer's slices are all read back by the fold kernel: cap them at FUSE_BN_PARTIAL_BYTES of partial
             // tiles, never below four (fewer leave the partial-tile launch with a handful of workgroups)
             const size_t per_slice = (size_t)phases * max_rows * p.Cpad * sizeof(float);
-            const size_t cap = (size_t)gcc_opt(GCC_OPT_FUSE_BN_PARTIAL_KB) * 1024;
+            const size_t cap = FUSE_BN_PARTIAL_BYTES;
             const int nk = conv_nk(c, dgrad);
             int ks = sp.ksplit;
             while (ks > 4 && per_slice * ks > cap) ks = (ks + 1) / 2;
@@ -1916,11 +1849,11 @@ extern "C" int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, co
     // The K split is sized to fill the chip with the partial-tile launch, but every slice is one more fp32 copy of the output
     // that splitk_bn_act_kernel -- C / 8 workgroups -- has to read back: the student's 16x16 -> 8x8 layer wrote and folded 16
     // slices = 16.8 MB for a 0.5 MB output, 59 us of fold behind 11 us of MFMA work (profiles/r3z_unet_student_chain.txt).
-    // Cap the slices at GCC_OPT_FUSE_BN_PARTIAL_KB of partial tiles (default 4 MB), never below four (fewer leave the partial-tile
+    // Cap the slices at FUSE_BN_PARTIAL_BYTES of partial tiles (4 MB), never below four (fewer leave the partial-tile
     // launch with a handful of workgroups: student forward 628 -> 569 us, teacher 836 -> 796 with 8 MB: profiles/r3z_*).
     if (sp.ksplit > 4 && max_rows * phases <= FOLD_BN_MAX_ROWS) {
         const size_t per_slice = (size_t)phases * max_rows * tp.ntiles * tp.BC * sizeof(float);
-        const size_t cap = (size_t)gcc_opt(GCC_OPT_FUSE_BN_PARTIAL_KB) * 1024;
+        const size_t cap = FUSE_BN_PARTIAL_BYTES;
         int ks = sp.ksplit;
         while (ks > 4 && per_slice * ks > cap) ks = (ks + 1) / 2;
         if (ks != sp.ksplit) { sp.kper = cdiv(nk, ks); sp.ksplit = cdiv(nk, sp.kper); }

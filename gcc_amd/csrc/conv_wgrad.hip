@@ -703,11 +703,12 @@ int plan_splits(const gcc_conv_t* c, int batch, int* ksteps_per_split, bool* big
     const long M = (long)c->N * Ho * Wo;
     const int ksteps = (int)((M + TP - 1) / TP);
     const int ncols = c->KH * c->KW * ceil8(c->Ci);
-    // 256 x 256 tiles (one workgroup per CU): large regular outputs only, where at most ~8 pixel splits fill the chip
-    const int big_mode = gcc_opt(GCC_OPT_WGRAD_BIG);
+    // 256 x 256 tiles (one workgroup per CU): large regular outputs only, where at most ~8 pixel splits fill the chip, from
+    // BIG_MIN_TILES output tiles up (the PatchGAN's 128 -> 256 layer; 32 until round 6: +0.3 % on the step at 8,
+    // profiles/r6_ab_wgrad_big_min_tiles.txt)
+    constexpr int BIG_MIN_TILES = 8;
     const int tiles_big = cdiv(ncols, 256) * cdiv(c->Co, 256);
-    bool big = big_mode && batch == 1 && (c->Ci & 7) == 0 && c->Co >= 256 && ncols >= 256 && tiles_big >= gcc_opt(GCC_OPT_WGRAD_BIG_MIN_TILES) &&
-               ksteps >= 64;
+    bool big = batch == 1 && (c->Ci & 7) == 0 && c->Co >= 256 && ncols >= 256 && tiles_big >= BIG_MIN_TILES && ksteps >= 64;
     int splits;
     if (big) {
         const int target = plan_or(c->plan.wgrad_wgs_big, PLAN_WGRAD_WGS_BIG);
@@ -812,9 +813,7 @@ int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float
     p.direct = (splits == 1 && regular) ? 1 : 0;
     p.accumulate = accumulate; p.dw = dw;
     p.debug = gcc_diag_bits();
-    {
-        p.rowmode = (gcc_opt(GCC_OPT_WGRAD_ROW_TABLE) && c->KH <= 15 && c->KW <= 15) ? 1 : 0;
-    }
+    p.rowmode = (c->KH <= 15 && c->KW <= 15) ? 1 : 0;     // taller or wider kernels decompose the pixels in every lane
     int tper = 0;
     const int tsplits = regular ? ts_plan(c, batch, &tper) : 0;
     if (tsplits > 0) {

@@ -160,8 +160,7 @@ struct Cfg {
     static constexpr int PB = TP / 16;
     static constexpr int WI = BC / 8;                      // 1-KiB weight staging instructions per k-step
     static constexpr int WPW = WI / WAVES;                 // ... per wave (0: the first WI waves issue one)
-    static constexpr int WN_GLDS = WPW > 0 ? WPW : 1;      // weight staging instructions a wave issues per k-step
-    static constexpr int W_CHUNKS = (BC * 8 + NT - 1) / NT;  // register path: 16-B weight chunks per thread
+    static constexpr int WN = WPW > 0 ? WPW : 1;           // weight staging instructions a wave issues per k-step
     static constexpr int LDS_BYTES_LOOP = 2 * (BP + BC) * BK * 2;
     static constexpr int OSTRIDE = BC * 2 + 16;            // epilogue tile row stride (bytes)
     static constexpr int LDS_BYTES_EPI = BP * OSTRIDE + 2 * NT * 4 + 16;      // + the ticket word of stats_tail

@@ -438,15 +438,12 @@ extern "C" const char* gcc_strerror(int code) {
 extern "C" int gcc_version(void) {
     GCC_ENTER(); return GCC_HIP_ABI; }
 
-// ---- tuning options (the library's only process-wide state) --------------------------------------------------------
+// ---- route switches (the library's only process-wide state) --------------------------------------------------------
 namespace {
 struct OptDef { const char* env; int def; };
 const OptDef kOptDef[GCC_OPT_COUNT_] = {
-    {"GCC_IGEMM_GLDS", 1}, {"GCC_IGEMM_HEAD", 1}, {"GCC_IGEMM_THIN", 1}, {"GCC_WGRAD_BIG", 1}, {"GCC_BN_SWEEPS", 0},
-    {"GCC_BN_MAXBLK", 2048}, {"GCC_BN_REDUCE_THREADS", 256}, {"GCC_BN_REDUCE_CAP", 1024}, {"GCC_INORM_LPP", 0},
-    {"GCC_IGEMM_FORCE_BC", 0}, {"GCC_IGEMM_FORCE_KSPLIT", 0}, {"GCC_IGEMM_NARROW", 1}, {"GCC_WGRAD_BIG_MIN_TILES", 8},
-    {"GCC_FUSE_BN", 3}, {"GCC_BN_BWD_SMALL", 1}, {"GCC_WGRAD_ROW_TABLE", 1}, {"GCC_IGEMM_HALO", 3}, {"GCC_FUSE_BN_PARTIAL_KB", 4096},
-    {"GCC_INORM_GRID", 1}, {"GCC_IGEMM_STAGES", 3}, {"GCC_WGRAD_TS", 1}, {"GCC_HALO_XCD_COLS", 1},
+    {"GCC_IGEMM_THIN", 1}, {"GCC_FUSE_BN", 3}, {"GCC_BN_BWD_SMALL", 1}, {"GCC_IGEMM_HALO", 3}, {"GCC_INORM_GRID", 1},
+    {"GCC_WGRAD_TS", 1}, {"GCC_HALO_XCD_COLS", 1},
 };
 std::atomic<int> g_opt[GCC_OPT_COUNT_];
 int g_opt_default[GCC_OPT_COUNT_];
@@ -507,7 +504,7 @@ extern "C" int gcc_set_option(int id, int value) {
     std::call_once(g_opt_once, opt_init);
     return g_opt[id].exchange(value < 0 ? g_opt_default[id] : value, std::memory_order_relaxed);
 }
-// 1 while every tuning hook holds its built-in default (environment overrides count as changes): what bench.py asserts
+// 1 while every route switch holds its built-in default (environment overrides count as changes): what bench.py asserts
 extern "C" int gcc_options_default(void) {
     for (int i = 0; i < GCC_OPT_COUNT_; i++)
         if (gcc_opt(i) != kOptDef[i].def) return 0;

@@ -28,11 +28,10 @@ static bool make_layout(int C, Layout* L, int V = 8) {
     return true;
 }
 static int stream_blocks(size_t pixels, const Layout& L, int sweeps_per_block) {
-    const int sw = gcc_opt(GCC_OPT_BN_SWEEPS), cap = gcc_opt(GCC_OPT_BN_MAXBLK);
-    if (sw > 0) sweeps_per_block = sw;
+    constexpr size_t MAX_BLOCKS = 2048;      // cap on streaming workgroups
     size_t b = (pixels + (size_t)L.PPB * sweeps_per_block - 1) / ((size_t)L.PPB * sweeps_per_block);
     if (b < 1) b = 1;
-    if (b > (size_t)cap) b = cap;
+    if (b > MAX_BLOCKS) b = MAX_BLOCKS;
     return (int)b;
 }
 
@@ -337,9 +336,9 @@ __device__ __forceinline__ void bwd_tail(const BwdArgs& a, int* sh) {
 }
 
 // V = channels per thread (4: 8-byte accesses, half the per-channel state -> twice the occupancy)
-// NTH = 256 (default): small workgroups with 5 KB of LDS, so that they can share a CU with the two 74 KB workgroups of the
+// NTH = 256 (REDUCE_NT): small workgroups with 5 KB of LDS, so that they can share a CU with the two 74 KB workgroups of the
 // weight-gradient kernel running on the side stream (with 1024-thread / 61 KB workgroups the two streams took turns:
-// the BatchNorm backward behind a big wgrad launch ran 4x slower than alone).  NTH = 1024 is kept for A/B.
+// the BatchNorm backward behind a big wgrad launch ran 4x slower than alone).
 template <bool GATE, bool DROP, int V, int NTH>
 __global__ __launch_bounds__(NTH) void bnact_bwd_reduce_kernel(const BwdArgs a0) {
     __shared__ float red[NTH][V + 1];
@@ -1667,19 +1666,16 @@ bool inorm_launch(const InFusedArgs& a, int N, hipStream_t st, void* ws, size_t 
         return true;
     }
     if (need_grid || EXT) return false;
-    const int lpp_env = gcc_opt(GCC_OPT_INORM_LPP);
-    const int lpp = lpp_env ? lpp_env : 2;
-    const int slabs = ((a.C + 7) / 8 + lpp - 1) / lpp;
+    constexpr int LPP = 2;                   // lanes per pixel
+    const int slabs = ((a.C + 7) / 8 + LPP - 1) / LPP;
     const dim3 grid(slabs, N);
     const bool big = a.HW >= 2048;
-#define GCC_IN_LAUNCH(NTH, LPP)                                                                         \
+#define GCC_IN_LAUNCH(NTH)                                                                              \
     do {                                                                                                \
         if (BWD) hipLaunchKernelGGL((inorm_bwd_fused_kernel<NTH, LPP>), grid, dim3(NTH), 0, st, a);     \
         else hipLaunchKernelGGL((inorm_fwd_fused_kernel<NTH, LPP>), grid, dim3(NTH), 0, st, a);         \
     } while (0)
-    if (lpp == 1) { if (big) GCC_IN_LAUNCH(1024, 1); else GCC_IN_LAUNCH(256, 1); }
-    else if (lpp == 2) { if (big) GCC_IN_LAUNCH(1024, 2); else GCC_IN_LAUNCH(256, 2); }
-    else { if (big) GCC_IN_LAUNCH(1024, 4); else GCC_IN_LAUNCH(256, 4); }
+    if (big) GCC_IN_LAUNCH(1024); else GCC_IN_LAUNCH(256);
 #undef GCC_IN_LAUNCH
     return false;
 }
@@ -1812,7 +1808,7 @@ __global__ __launch_bounds__(1024) void channel_sum_finalize_kernel(const float*
 // channels, four pixels' loads in flight per thread, wave shuffles + LDS in double.  The two-launch pipeline above costs those
 // launch-bound models two host enqueues and two dependent launches per convolution bias.
 constexpr int SUM_SMALL_NT = 512;
-constexpr size_t SUM_SMALL_MAX_PIXELS = 16384;
+constexpr size_t SUM_SMALL_MAX_PIXELS = GCC_CHANSUM_SMALL_MAX_PIXELS;
 __device__ __forceinline__ void channel_sum_small_body(const bf16_t* x, const int ld, const int off, const int C, const int pixels,
                                                        float* out, const int accumulate, const int c0) {
     __shared__ double red[SUM_SMALL_NT / 64][8];
@@ -2057,16 +2053,14 @@ extern "C" int gcc_bnact_fwd(const gcc_bnact_t* p, const void* x, int ldx, int x
     return GCC_OK;
 }
 
-static int reduce_threads() {
-    return gcc_opt(GCC_OPT_BN_REDUCE_THREADS) == 1024 ? 1024 : 256;
-}
+constexpr int REDUCE_NT = 256;      // threads per bnact_bwd_reduce_kernel workgroup
 static int bwd_blocks(size_t pixels, const Layout& L) {
     // (L is the 8-channel, 256-thread layout.)  256-thread reduce workgroups sweep PPB/2 pixels at a time: ~16 sweeps
-    // each, at most 4 workgroups per CU; the 1024-thread variant: one per CU.  Bounds the partial rows the finalize folds.
-    const bool small = reduce_threads() == 256;
-    const size_t per = small ? (size_t)L.PPB * 8 : (size_t)L.PPB * 8 * 4;
+    // each, at most 4 workgroups per CU.  Bounds the partial rows the finalize folds.
+    constexpr size_t MAX_BLOCKS = 1024;
+    const size_t per = (size_t)L.PPB * 8;
     size_t b = (pixels + per - 1) / per;
-    if (small && b < 512) {
+    if (b < 512) {
         // Tensors that cannot fill the chip at 16 sweeps per workgroup (the U-Net's <= 32x32 layers): a sweep is one dependent
         // round trip to memory (~1 us with two pixels in flight per thread), so 16 of them made a 15-29 us kernel out of a few
         // hundred KB -- on the generators' backward chain, which runs alone.  Down to 2 sweeps, up to 512 workgroups.
@@ -2077,9 +2071,7 @@ static int bwd_blocks(size_t pixels, const Layout& L) {
         b = (pixels + lane_pixels * sweeps - 1) / (lane_pixels * sweeps);
     }
     if (b < 1) b = 1;
-    const int capv = gcc_opt(GCC_OPT_BN_REDUCE_CAP);
-    const size_t cap = small ? (size_t)capv : 256;
-    if (b > cap) b = cap;
+    if (b > MAX_BLOCKS) b = MAX_BLOCKS;
     return (int)b;
 }
 
@@ -2146,14 +2138,10 @@ extern "C" int gcc_bnact_bwd_ex(const gcc_bnact_bwd_t* p, int in_act, float in_s
     {
         BwdArgs r = a;                      // the reduce pass runs 4 channels per thread
         if (!make_layout(C, &r.L, 4)) return GCC_ERR_UNSUPPORTED;
-        const int nth = reduce_threads();
-        if (r.L.CHP > nth) return GCC_ERR_UNSUPPORTED;
-        r.L.PPB = nth / r.L.CHP;
-#define GCC_LAUNCH_REDUCE(G, D)                                                                                             \
-        do {                                                                                                                \
-            if (nth == 256) hipLaunchKernelGGL((bnact_bwd_reduce_kernel<G, D, 4, 256>), dim3(blocks, groups), dim3(256), 0, st, r);   \
-            else hipLaunchKernelGGL((bnact_bwd_reduce_kernel<G, D, 4, 1024>), dim3(blocks, groups), dim3(1024), 0, st, r);           \
-        } while (0)
+        if (r.L.CHP > REDUCE_NT) return GCC_ERR_UNSUPPORTED;
+        r.L.PPB = REDUCE_NT / r.L.CHP;
+#define GCC_LAUNCH_REDUCE(G, D) \
+        hipLaunchKernelGGL((bnact_bwd_reduce_kernel<G, D, 4, REDUCE_NT>), dim3(blocks, groups), dim3(REDUCE_NT), 0, st, r)
         if (gate && drop) GCC_LAUNCH_REDUCE(true, true);
         else if (gate) GCC_LAUNCH_REDUCE(true, false);
         else if (drop) GCC_LAUNCH_REDUCE(false, true);

@@ -10,7 +10,6 @@ inside the concat buffer of the up path).
 
 Reference anchors: U-Net models/Pix2Pix.py:20-130, PatchGAN :267-348, hooks :363-373,702-727.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -19,28 +18,21 @@ from . import _lib, ops
 from .ops import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH
 
 LRELU = 0.2
-# run weight-gradient kernels on a side stream, concurrently with the data-gradient / BN chain
-OVERLAP_WGRAD = os.environ.get('GCC_OVERLAP_WGRAD', '1') != '0'
+# run weight-gradient kernels on a side stream, concurrently with the data-gradient / BN chain (the model classes set it per
+# schedule: overlap_wgrad_default, and off for the chains that keep their weight gradients on their own stream)
+OVERLAP_WGRAD = True
 
 
 def overlap_wgrad_default(world):
-    """Weight gradients on the side stream?  Yes on one GPU (+1.2 %); no under data parallelism unless GCC_OVERLAP_WGRAD=1 asks:
-    the communication library's stream is one more busy stream on four hardware queues, and with the gradient buckets issued
-    from the chains' own streams a data-parallel rank steps in 16.45 ms instead of 17.04-17.30 (one-rank RCCL rig,
-    profiles/r5_dp_one_rank.txt; 15.1-15.4 without a process group)"""
-    env = os.environ.get('GCC_OVERLAP_WGRAD')
-    if env is not None:
-        return env != '0'
+    """Weight gradients on the side stream?  Yes on one GPU (+1.2 %); no under data parallelism: the communication library's
+    stream is one more busy stream on four hardware queues, and with the gradient buckets issued from the chains' own streams a
+    data-parallel rank steps in 16.45 ms instead of 17.04-17.30 (one-rank RCCL rig, profiles/r5_dp_one_rank.txt; 15.1-15.4
+    without a process group)"""
     return world <= 1
-# U-Net layers as one C call (gcc_conv_bn_act): conv + BatchNorm statistics + finalize + normalise / activation
-FUSE_CONV_BN = os.environ.get('GCC_FUSE_CONV_BN', '1') != '0'
-# GCC_WGRAD_GROUP (default 1): the regular weight gradients of a generator's backward pass run as grouped launches (ops.WgradGroup:
-# one launch + one fold per group) instead of one launch + fold per layer -- the U-Net's up path when its last data gradient is
-# enqueued, its down path at the end of the pass.  0: per layer, as before round 6.
-WGRAD_GROUP = os.environ.get('GCC_WGRAD_GROUP', '1') != '0'
-# the power iterations of a SAGAN pass's spectrally normalised layers as four grouped launches (SNConvOp.iterate_all); 0: four per layer
-SN_GROUP = os.environ.get('GCC_SN_GROUP', '1') != '0'
-WGRAD_GROUP_MAX_UNITS = int(os.environ.get('GCC_WGRAD_GROUP_MAX_UNITS', '20000'))
+# The regular weight gradients of a generator's backward pass run as grouped launches (ops.WgradGroup: one launch + one fold per
+# group) instead of one launch + fold per layer -- the U-Net's up path when its last data gradient is enqueued, its down path at
+# the end of the pass -- for layers of at most this many units of work (ConvOp.group_entry)
+WGRAD_GROUP_MAX_UNITS = 20000
 
 
 # ------------------------------------------------------------------------------------------------
@@ -326,7 +318,7 @@ class WgradCollector:
 
     def __init__(self, owner, ctx, enabled=True):
         self.owner, self.ctx = owner, ctx
-        self.on = bool(enabled) and WGRAD_GROUP and not ops.PROFILE.active      # (bench.py's bracketed step times every launch on its own)
+        self.on = bool(enabled) and not ops.PROFILE.active      # (bench.py's bracketed step times every launch on its own)
         self.entries, self.bias, self.segs = [], [], []
 
     def add(self, conv, x, dy, seg=None, bias_done=False):
@@ -562,8 +554,9 @@ class UnetEngine:
         # outermost down conv (no norm): both activated copies of e[0] straight from the conv launch -- the LeakyReLU'd one for the
         # next down conv, the ReLU'd one into the concat buffer (hazard H1); e[0] itself is never materialised
         self.down[0].forward(c.x_in, c.lin[1], act=ACT_LRELU, y2=ops.cslice(c.rcat[1], 0, wd[0]), y2_mode=ops.Y2_RELU)
+        # U-Net layers as one C call (gcc_conv_bn_act): conv + BatchNorm statistics + finalize + normalise / activation
         # (bench.py's bracketed roofline step times every igemm launch on its own: the layers run as separate calls there)
-        fused = train and FUSE_CONV_BN and not ops.PROFILE.active
+        fused = train and not ops.PROFILE.active
         for d in range(1, D - 1):
             n = N * c.hs[d][0] * c.hs[d][1]
             if fused and self.down[d].bias is None and not (self.down[d].row_split or self.down[d].col_split):
@@ -628,7 +621,7 @@ class UnetEngine:
         D, wd, uw, N = self.D, self.width, self.uwidth, c.N
         if g_feat is None:
             g_feat = [None] * 4
-        # weight gradients: the regular layers are collected and run as two grouped launches (WGRAD_GROUP; bench.py's bracketed
+        # weight gradients: the regular layers are collected and run as two grouped launches (WgradCollector; bench.py's bracketed
         # roofline step times every launch on its own: per layer there)
         wg = WgradCollector(self, c)
         weight_gradient = wg.add
@@ -1217,13 +1210,13 @@ class SNConvOp:
         return SNState(self)
 
     def fused_pack_ok(self):
-        return ops.SN_FUSED_PACK and self.w_bar.data.is_contiguous(memory_format=torch.channels_last if self.k > 1 else torch.contiguous_format)
+        return self.w_bar.data.is_contiguous(memory_format=torch.channels_last if self.k > 1 else torch.contiguous_format)
 
     @staticmethod
     def iterate_all(pairs):
         """the power iterations of a forward pass's layers [(SNConvOp, SNState)] up front, grouped (they depend on the weights alone):
         four launches instead of four per layer; True when done -- the layers' forward(..., iterated=True) then skip their own"""
-        if not SN_GROUP or len(pairs) < 2 or not all(op.fused_pack_ok() for op, _ in pairs):
+        if len(pairs) < 2 or not all(op.fused_pack_ok() for op, _ in pairs):
             return False
         ops.spectral_power_iteration_pack_group([(op.w_bar.data, op.u.data, op.v.data, st.t, st.sigma, st.w, st.wt) for op, st in pairs])
         return True

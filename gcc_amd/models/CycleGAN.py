@@ -30,24 +30,24 @@ from .Pix2Pix import HipAdam, MobileResnetGenerator, _patchgan_tree, _portable
 from ._streams import TeacherStreamMixin
 
 HEAVY_SPARSITY = ('model.1', 'model.4', 'model.19', 'model.22')      # models/CycleGAN.py:243, 548-569
-# GCC_CYCLE_FORK=1: the two sides of the model (generator A -> B with its discriminator, generator B -> A with its) are
-# independent chains of small kernels inside forward, backward_G, backward_D and the architecture step: side B runs on the
-# auxiliary stream beside side A.  The host enqueues A then B as before, so everything that accumulates in launch order on the
-# weight-gradient side stream (both generators' parameter gradients) keeps the reference's order: same bits.
-CYCLE_FORK = int(os.environ.get('GCC_CYCLE_FORK', '2'))
-# 2 (default): the online teacher's two sides fork as well, and the weight gradients stay on their chain's stream instead of a
-# side stream each: four chains on four HIP streams = the device's four hardware queues (with side streams the same forks
-# make eight streams and lose: profiles/r4ag_cyclegan_streams.txt -- eager 32.2 -> 23.3 ms, replayed 30.0 -> 24.7);
-# 1: the student's sides only, weight gradients on side streams (six streams: 25.6 ms replayed)
+# CYCLE_FORK: the two sides of the model (generator A -> B with its discriminator, generator B -> A with its) are independent
+# chains of small kernels inside forward, backward_G, backward_D and the architecture step: side B runs on the auxiliary stream
+# beside side A, for the student and the online teacher alike, and the weight gradients stay on their chain's stream instead of
+# a side stream each: four chains on four HIP streams = the device's four hardware queues (with side streams the same forks
+# make eight streams and lose: profiles/r4ag_cyclegan_streams.txt -- eager 32.2 -> 23.3 ms, replayed 30.0 -> 24.7).  The host
+# enqueues A then B as before, so everything that accumulates in launch order keeps the reference's order: same bits.
+# False: both sides in line, weight gradients on side streams (the serialized reference of
+# tests/test_replay_gpu.py::test_cyclegan_two_sides_fork_changes_nothing).
+CYCLE_FORK = True
 
 
 class _ChainWgrad:
-    """with CYCLE_FORK >= 2: weight-gradient launches stay on the stream of the chain that needs them (engine.OVERLAP_WGRAD
-    off for the duration of the step; restored afterwards: other model families of the process keep their side streams)"""
+    """with CYCLE_FORK: weight-gradient launches stay on the stream of the chain that needs them (engine.OVERLAP_WGRAD off for
+    the duration of the step; restored afterwards: other model families of the process keep their side streams)"""
 
     def __enter__(self):
         self.prev = engine.OVERLAP_WGRAD
-        if CYCLE_FORK >= 2 and os.environ.get('GCC_CYCLE_CHAIN_WGRAD', '1') != '0':
+        if CYCLE_FORK:
             engine.OVERLAP_WGRAD = False
         return self
 
@@ -282,11 +282,11 @@ class MobileCycleGANModel(TeacherStreamMixin, nn.Module):
         ops.nchw_to_nhwc(self.real_B, self._B)
 
     def _forks(self):
-        return bool(CYCLE_FORK and not getattr(self, '_no_fork', False) and self._aux_stream())
+        return bool(CYCLE_FORK and self._aux_stream())
 
     def _two_sides(self, side_a, side_b, shared=None):
-        """side_a() on the current stream, side_b() on the auxiliary stream beside it (CYCLE_FORK; the online teacher, which
-        already runs on a stream of its own, and a single-stream schedule keep both in line); joined before returning.
+        """side_a() on the current stream, side_b() on the auxiliary stream beside it (CYCLE_FORK; a single-stream schedule keeps
+        both in line); joined before returning.
         shared: the optimizer whose parameter gradients BOTH sides add to (backward_G: each generator is differentiated by
         both sides) -- side B then accumulates into a zeroed second buffer (engine.FlatParams.redirect) that is added
         afterwards: (0 + A) + (0 + B), the bits of A-then-B, and no two launches ever add to one buffer at the same time"""
@@ -485,13 +485,11 @@ class MobileCycleGANModel(TeacherStreamMixin, nn.Module):
         if self.opt.online_distillation:
             T = self.teacher_model
 
-            T._no_fork = CYCLE_FORK < 2   # 1: the online teacher, already on a stream of its own, keeps its sides in line
-
             def teacher_step():
                 T.set_input(self.input)
                 T.optimize_parameters()
                 # the reference clones; here the teacher's activation buffers are not overwritten before they are consumed
-                # (read by the student after _join: the step may be enqueued by the teacher's host thread)
+                # (read by the student after _join)
                 self.target_distillation_A_features = T.get_distillation_features(AorB='A')
                 self.target_distillation_B_features = T.get_distillation_features(AorB='B')
             ts = self._run_teacher(teacher_step)

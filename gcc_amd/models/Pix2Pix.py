@@ -251,34 +251,17 @@ class HipAdam(torch.optim.Optimizer):
             self.plan_dup.step(g['lr'], g['betas'], g['eps'])
 
 
-# host-enqueue scheduling: alternate the chunks of two generators (GCC_INTERLEAVE=0: teacher first, then the student)
-# GCC_INTERLEAVE: 0 (default) the teacher's whole iteration is enqueued first, then the student's; 1 alternate chunk by chunk;
-# n >= 2 alternate the first n chunks only.  Measured (profiles/r02_ab_tables.md): every interleaving is 3.5-6 % SLOWER -- the
-# teacher's iteration is the critical path (its end gates the student's backward_G) and both networks' discriminator passes
-# fill the chip, so work given to the student early only delays the teacher.
-INTERLEAVE = int(os.environ.get('GCC_INTERLEAVE', '0'))
-# the online teacher's D(real) pass started early too: 1 = on an auxiliary stream of its own (measured: -7 %, a fifth busy queue on
-# four hardware queues); 2 = on the STUDENT's auxiliary stream, in front of the student's pass (no extra queue: round 4 A/B)
-TEACHER_EARLY_DREAL = int(os.environ.get('GCC_TEACHER_EARLY_DREAL', '0'))
-# the student joins the teacher's stream where the teacher's features and discriminator are final (after the head of the
-# teacher's backward_G), not at the end of the teacher's iteration: the teacher's generator backward + Adam + repack
-# (small and HBM-bound kernels) then run beside the student's distillation passes instead of in front of them
-EARLY_JOIN = os.environ.get('GCC_EARLY_JOIN', '1') != '0'
-# GCC_DISTILL_FORK (default 1): the distillation terms on the generator's features run on the auxiliary stream beside the
-# teacher discriminator's pass over the student's fake (backward_G's tail): +2.6 % (profiles/r4s_ab_distill_fork.txt)
-DISTILL_FORK = os.environ.get('GCC_DISTILL_FORK', '1') != '0'
-# GCC_ARCH_FORK (default 1): the architecture step's two discriminator backward passes (fake, real) side by side on two
-# streams: +1.9 % (profiles/r4y_ab_arch_fork.txt), same bits (tests/test_replay_gpu.py::test_pix2pix_stream_forks_change_nothing)
-ARCH_FORK = os.environ.get('GCC_ARCH_FORK', '1') != '0'
-# GCC_ARCH_EARLY=1: the online teacher's part of the architecture step (generator forward + two discriminator forwards over the
-# validation batch) starts when the teacher's iteration ends instead of when the student has finished reading the teacher
-ARCH_EARLY = os.environ.get('GCC_ARCH_EARLY', '0') == '1'
-# GCC_TAIL_HALO_HC (default 1): the teacher discriminator's pass over the student's fake (the student's tail: one or two busy queues)
-# takes the 128-column halo tiles for its half-chip launches: +0.3-0.6 % (profiles/r4ao_ab_tail_halo_hc.txt)
-TAIL_HALO_HC = os.environ.get('GCC_TAIL_HALO_HC', '1') != '0'
-# GCC_ARCH_FREE_EARLY (default 1): in the architecture step the teacher's stream hands its difference scalar over itself and is
-# released behind its own part: +0.6 % (profiles/r4ay_ab_arch_free_early.txt), same bits
-ARCH_FREE_EARLY = os.environ.get('GCC_ARCH_FREE_EARLY', '1') != '0'
+# Stream forks of the schedule.  Each is the product's path; False is the serialized form that
+# tests/test_replay_gpu.py::test_pix2pix_stream_forks_change_nothing holds it to, bit for bit.
+# DISTILL_FORK: the distillation terms on the generator's features run on the auxiliary stream beside the teacher
+# discriminator's pass over the student's fake (backward_G's tail): +2.6 % (profiles/r4s_ab_distill_fork.txt)
+DISTILL_FORK = True
+# ARCH_FORK: the architecture step's two discriminator backward passes (fake, real) side by side on two streams: +1.9 %
+# (profiles/r4y_ab_arch_fork.txt)
+ARCH_FORK = True
+# ARCH_FREE_EARLY: in the architecture step the teacher's stream hands its difference scalar over itself and is released behind
+# its own part: +0.6 % (profiles/r4ay_ab_arch_free_early.txt)
+ARCH_FREE_EARLY = True
 # GCC_DP_TEACHER_UPDATE_EARLY (default 1; data parallelism only): the online teacher's generator update -- wait for its gradient
 # buckets, Adam, repack -- is enqueued on the teacher's own stream right behind its backward pass instead of in front of the
 # architecture step's teacher forward
@@ -286,20 +269,8 @@ DP_TEACHER_UPDATE_EARLY = os.environ.get('GCC_DP_TEACHER_UPDATE_EARLY', '1') != 
 DP_TEACHER_BUCKETS_LATE = os.environ.get('GCC_DP_TEACHER_BUCKETS_LATE', '1') != '0'
 
 
-def _step(gen, stream):
-    """one chunk of `gen` with `stream` current (None: the current stream); False when the generator is exhausted"""
-    try:
-        if stream:
-            with ops.on_stream(stream):
-                next(gen)
-        else:
-            next(gen)
-        return True
-    except StopIteration:
-        return False
-
-
 def _drain(gen, stream):
+    """every chunk of `gen` with `stream` current (None: the current stream)"""
     if stream:
         with ops.on_stream(stream):
             for _ in gen:
@@ -307,21 +278,6 @@ def _drain(gen, stream):
     else:
         for _ in gen:
             pass
-
-
-def _alternate(tgen, ts, sgen):
-    """teacher chunk, student chunk, ... until both are exhausted (tgen may be None)"""
-    t_alive, s_alive = tgen is not None, sgen is not None
-    n = 0
-    while t_alive or s_alive:
-        if t_alive:
-            t_alive = _step(tgen, ts)
-        n += 1
-        if INTERLEAVE >= 2 and n >= INTERLEAVE and t_alive:
-            _drain(tgen, ts)
-            t_alive = False
-        if s_alive:
-            s_alive = _step(sgen, None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -501,20 +457,16 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         ops.nchw_to_nhwc(self.real_A, self._A)
         ops.nchw_to_nhwc(self.real_B, self._B)
 
-    def forward(self, slot=0):
-        """fake_B = G(real_A)  (models/Pix2Pix.py:460-462).  slot 1: in a second set of activation buffers (the online teacher's
-        architecture-step forward, started while the student still reads the features of the training batch)"""
+    def forward(self):
+        """fake_B = G(real_A)  (models/Pix2Pix.py:460-462)"""
         self.finish_G_update()
         N, _, H, W = self._A.shape
-        if self.resnet:
-            c = self.G._ctx(N, H, W, 'main' if slot == 0 else 'slot%d' % slot)
-        else:
-            c = self.G._ctx(N, H, W, slot)
+        c = self.G._ctx(N, H, W, 'main' if self.resnet else 0)
         ops.nhwc_copy(self._A, 0, c.x_in, 0, 3, cfill=8)
         if self.resnet:
             self._gctx = self.G.forward(c, train=self.netG.training)
         else:
-            self._gctx = self.G.forward(N, H, W, train=self.netG.training, slot=slot)
+            self._gctx = self.G.forward(N, H, W, train=self.netG.training)
         self._fake = self._gctx.out
         self._fake_nchw = None
 
@@ -534,13 +486,13 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         """ctx.x_in = cat(real_A, second) along channels (3 + 3, zero-filled to 8)"""
         ops.nhwc_pack_pair(self._A if A is None else A, second, ctx.x_in, 3, 3)
 
-    def _d_forward(self, tag, second, refresh=True, A=None, defer_running=False):
+    def _d_forward(self, tag, second, refresh=True, A=None):
         """A: the caller's own copy of real_A (the student's, when it runs the teacher's discriminator over its fake: the
-        teacher may already hold the next batch).  defer_running: see PatchGANEngine.forward"""
+        teacher may already hold the next batch)"""
         N, _, H, W = (self._A if A is None else A).shape
         ctx = self.D.new_ctx(N, H, W, tag)
         self._pack_pair(ctx, second, A)
-        self.D.forward(ctx, train=True, refresh=refresh, defer_running=defer_running)
+        self.D.forward(ctx, train=True, refresh=refresh)
         return ctx
 
     def _start_real_pass(self, tag):
@@ -549,11 +501,9 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         streams idle half the time).  The pass keeps its place in the reference's order for everything that is order
         dependent: its BatchNorm running-statistics updates are applied in _take_real_pass(), after D(fake)'s."""
         self._early = getattr(self, '_early', {})
-        # the student always; the online teacher only with GCC_TEACHER_EARLY_DREAL=1 (measured: 833 against 893 images/s)
-        is_teacher = self.teacher_model is None
-        aux = self._aux_stream() if (not is_teacher or (TEACHER_EARLY_DREAL and getattr(self, '_is_online_teacher', False))) else False
-        if is_teacher and TEACHER_EARLY_DREAL == 2 and aux:
-            aux = getattr(self, '_shared_aux', None) or False
+        # the student only: the online teacher's pass started early too measured slower (833 against 893 images/s: a fifth busy
+        # queue on four hardware queues)
+        aux = self._aux_stream() if self.teacher_model is not None else False
         if not aux:
             return
         main = ops.current_stream()
@@ -649,7 +599,7 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         if self.optimizer_G.reducer is not None:
             self.optimizer_G.reducer.begin()
         if ts:
-            ev = getattr(self.teacher_model, '_head_done', None) if EARLY_JOIN else None
+            ev = getattr(self.teacher_model, '_head_done', None)
             if ev is not None:
                 ops.wait_event(ops.current_stream(), ev)
             else:
@@ -658,7 +608,7 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
             aux = self._aux_stream() if DISTILL_FORK else False
             if aux:
                 # the generator's own terms on the auxiliary stream, beside the teacher discriminator's forward / backward over
-                # the student's fake: this stretch of the step has one busy queue otherwise (GCC_DISTILL_FORK=0: in line).
+                # the student's fake: this stretch of the step has one busy queue otherwise (DISTILL_FORK False: in line).
                 # Forking the whole block earlier -- beside the student's discriminator step -- loses 4.7 %: the step is
                 # chip-bound there (profiles/r4s_ab_distill_fork.txt)
                 ops.wait_stream(aux, ops.current_stream())
@@ -709,23 +659,19 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         opt = self.opt
         T = self.teacher_model
         # this pass runs where the step has one or two busy queues (the student's tail): its half-chip launches (L3 forward, L4
-        # data gradient: 128 workgroups of 256 x 256) take the 128-column halo tiles of the 'alone' plan (GCC_TAIL_HALO_HC)
-        if not TAIL_HALO_HC:
-            return self._distill_teacher_d_terms_body(T, opt)
+        # data gradient: 128 workgroups of 256 x 256) take the 128-column halo tiles of the 'alone' plan: +0.3-0.6 %
+        # (profiles/r4ao_ab_tail_halo_hc.txt)
         with ops.plan_override(halo_hc=1):
-            return self._distill_teacher_d_terms_body(T, opt)
-
-    def _distill_teacher_d_terms_body(self, T, opt):
-        ct = T._d_forward('on_student', self._fake, A=self._A)
-        dfe = T.D.features(ct)
-        N = dfe[0].shape[0]
-        dtd = [self._tbuf(4 + j, N, dfe[j].shape[1], dfe[j].shape[2], dfe[j].shape[3])[1] for j in range(2)]
-        for j in range(2):
-            f, t = dfe[j], self.target_distillation_features[4 + j]
-            ws = self._dws(4 + j, N, f.shape[1], f.shape[2] * f.shape[3])
-            ops.distill_fwd(f, t, self._dist_out[4 + j], ws)
-            ops.distill_bwd(f, t, opt.lambda_gram, opt.lambda_content, dtd[j], ws)
-        return T.D.backward(ct, has_pred_grad=False, g_feat=dtd, wgrad=False, need_dx=True)
+            ct = T._d_forward('on_student', self._fake, A=self._A)
+            dfe = T.D.features(ct)
+            N = dfe[0].shape[0]
+            dtd = [self._tbuf(4 + j, N, dfe[j].shape[1], dfe[j].shape[2], dfe[j].shape[3])[1] for j in range(2)]
+            for j in range(2):
+                f, t = dfe[j], self.target_distillation_features[4 + j]
+                ws = self._dws(4 + j, N, f.shape[1], f.shape[2] * f.shape[3])
+                ops.distill_fwd(f, t, self._dist_out[4 + j], ws)
+                ops.distill_bwd(f, t, opt.lambda_gram, opt.lambda_content, dtd[j], ws)
+            return T.D.backward(ct, has_pred_grad=False, g_feat=dtd, wgrad=False, need_dx=True)
 
     def _tbuf(self, i, N, C, H, W):
         key = ('t', i, N, C, H, W)
@@ -744,15 +690,14 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
     # -- one iteration (models/Pix2Pix.py:565-583) ----------------------------------------------------
     def optimize_parameters(self):
         """models/Pix2Pix.py:565-583.  The online teacher's whole iteration (its own stream) is enqueued first, then the
-        student's forward + discriminator step + the teacher-independent head of backward_G; both are generators of
-        host-enqueue chunks so that the order can be chosen (GCC_INTERLEAVE, see above: teacher first is the fastest)."""
+        student's forward + discriminator step + the teacher-independent head of backward_G.  Teacher first is the fastest
+        order: its iteration is the critical path (its end gates the student's backward_G), and enqueueing the two networks'
+        chunks alternately measured 3.5-6 % slower (profiles/r02_ab_tables.md)."""
         self.finish_G_update()
-        ts, tgen = None, None
+        ts = None
         if self.opt.online_distillation:
             T = self.teacher_model
             T._defer_G_update = True
-            T._is_online_teacher = True
-            T._shared_aux = self._aux_stream() if TEACHER_EARLY_DREAL == 2 else None
             ts = self._teacher_stream()
             T._own_stream = bool(ts)
             if ts and self._world > 1 and T._comm_group is None and not getattr(T, '_comm_group_set', False):
@@ -764,12 +709,8 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
                         o.reducer.set_group(T._comm_group)
             if ts:
                 self._release_teacher_stream(ts)                 # after the last launch that reads the teacher's buffers
-            tgen = T._iteration_steps(self.input)
-            if not ts or not INTERLEAVE:
-                _drain(tgen, ts)
-                tgen = None
-        sgen = self._pre_join_steps()
-        _alternate(tgen, ts, sgen)
+            _drain(T._iteration_steps(self.input), ts)
+        _drain(self._pre_join_steps(), None)
         if ts and getattr(self.teacher_model, '_held_G', False):
             # the student's discriminator buckets are issued: now the teacher generator's, and its update, on the teacher's stream
             self.teacher_model._held_G = False
@@ -866,18 +807,12 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
             self._apply_G_update()
 
     # -- architecture step (models/Pix2Pix.py:479-511, 585-593) -----------------------------------------
-    def get_D_arch_diff(self, isTeacher=False, defer_running=False):
-        """three hinge terms on one fake / real pair; the |.| difference (EMA'd for the teacher).
-        defer_running: both passes leave the BatchNorm running statistics alone (the caller replays the updates where the
-        passes belong in the reference's order: PatchGANEngine.apply_deferred_running)"""
+    def get_D_arch_diff(self, isTeacher=False):
+        """three hinge terms on one fake / real pair; the |.| difference (EMA'd for the teacher)"""
         mode = self.opt.gan_mode
         early = 'a_real' in getattr(self, '_early', {})
-        if defer_running:
-            cf = self._d_forward('a_fake', self._fake, defer_running=True)
-            cr = self._d_forward('a_real', self._B, refresh=False, defer_running=True)
-        else:
-            cf = self._d_forward('a_fake', self._fake, refresh=not early)
-            cr = self._take_real_pass('a_real')
+        cf = self._d_forward('a_fake', self._fake, refresh=not early)
+        cr = self._take_real_pass('a_real')
         ops.gan_loss(mode, cf.pred, False, True, self._l('D_arch_fake'))
         ops.gan_loss(mode, cf.pred, True, False, self._l('D_arch_fake_real'))
         ops.gan_loss(mode, cr.pred, True, True, self._l('D_arch_real'))
@@ -961,11 +896,8 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         T = self.teacher_model
         ts = self._teacher_stream()
 
-        free = getattr(self, '_teacher_free', None)
-        early = bool(ts) and ARCH_EARLY and free is not None and isinstance(T.D, engine.PatchGANEngine)
-
         def hand_over():
-            # GCC_ARCH_FREE_EARLY: the last thing the student reads of the teacher in this step is its difference scalar -- the
+            # ARCH_FREE_EARLY: the last thing the student reads of the teacher in this step is its difference scalar -- the
             # teacher's stream copies it into the student's loss vector itself and is free from here (its next iteration then
             # starts behind its own architecture-step part, not behind the student's two discriminator forwards)
             if ts and ARCH_FREE_EARLY:
@@ -975,41 +907,18 @@ class Pix2PixModel(TeacherStreamMixin, nn.Module):
         def teacher_part():
             T.finish_G_update()
             T.set_input(self.input)
-            yield
-            if not early:
-                T.forward()
-                yield
-                T.get_D_arch_diff(isTeacher=True)
-                hand_over()
-                return
-            # GCC_ARCH_EARLY: started when the teacher's own iteration ends, not when the student has finished reading the
-            # teacher (its stream idles ~2 ms there).  What the student still reads stays untouched: the generator's features
-            # (this forward runs in a second set of activation buffers), the discriminator contexts of the training batch
-            # (other tags), real_A (the student packs its own copy); the BatchNorm running statistics of the teacher's
-            # discriminator are updated where these two passes belong -- after the student's pass over it
-            T.forward(slot=1)
-            yield
-            cf, cr = T.get_D_arch_diff(isTeacher=True, defer_running=True)
-            ops.wait_event(ops.current_stream(), free)
-            T.D.apply_deferred_running(cf)
-            T.D.apply_deferred_running(cr)
+            T.forward()
+            T.get_D_arch_diff(isTeacher=True)
             hand_over()
 
-        def student_part():
-            if ts:
-                self._start_real_pass('a_real')
-                yield
-            self.forward()
-
         if ts:
-            self._release_teacher_stream(ts, wait_free=not early)
-            tgen = teacher_part()
-            if not INTERLEAVE:
-                _drain(tgen, ts)
-                tgen = None
-            _alternate(tgen, ts, student_part())
+            self._release_teacher_stream(ts)
+            with ops.on_stream(ts):
+                teacher_part()
+            self._start_real_pass('a_real')
+            self.forward()
         else:
-            _drain(student_part(), None)
+            self.forward()
             T.finish_G_update()
             T.set_input(self.input)
             T.forward()

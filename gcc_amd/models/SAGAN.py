@@ -37,20 +37,14 @@ def l2normalize(v, eps=1e-12):
     return v / (v.norm() + eps)
 
 
-# GCC_SAGAN_CHAIN_WGRAD (default 1): the weight-gradient launches stay on the stream of the chain that needs them instead of a side
-# stream: at 64 x 64 every kernel is a few microseconds and the two event operations of a side-stream fork cost more than the
-# overlap returns (eager 10.6 -> 8.8 ms, replayed 9.3 -> 8.4: profiles/r4ak_chain_wgrad.txt; SRGAN measured the other way round)
-CHAIN_WGRAD = os.environ.get('GCC_SAGAN_CHAIN_WGRAD', '1') != '0'
-# GCC_SAGAN_FORK=1: backward_G's distillation block on the auxiliary stream beside the discriminator's pass -- same bits, measured
-# SLOWER (replayed 8.42 -> 9.0 ms, profiles/r4an_sagan_fork.txt: the chains are too short to pay for a third stream): off
-G_FORK = os.environ.get('GCC_SAGAN_FORK', '0') == '1'
-
-
 class _ChainWgrad:
+    """the weight-gradient launches stay on the stream of the chain that needs them instead of a side stream: at 64 x 64 every
+    kernel is a few microseconds and the two event operations of a side-stream fork cost more than the overlap returns (eager
+    10.6 -> 8.8 ms, replayed 9.3 -> 8.4: profiles/r4ak_chain_wgrad.txt; SRGAN measured the other way round)"""
+
     def __enter__(self):
         self.prev = engine.OVERLAP_WGRAD
-        if CHAIN_WGRAD:
-            engine.OVERLAP_WGRAD = False
+        engine.OVERLAP_WGRAD = False
         return self
 
     def __exit__(self, *exc):
@@ -363,21 +357,13 @@ class SAGANModel(TeacherStreamMixin, nn.Module):
             ops.l1_loss(self._fake, T._fake, self._l('L1'), weight=opt.lambda_L1, da=tmp)
             return gf, dx2, tmp
 
-        # the student discriminator's pass over the fake and the distillation block (teacher discriminator over the same fake,
-        # transform convs, gram / content terms) only meet in dL/d(fake): the block runs on the auxiliary stream beside the pass
-        # (GCC_SAGAN_FORK; the online teacher keeps everything in line); the gradients are added in the reference's order
-        aux = self._aux_stream() if (self.distill and G_FORK and not getattr(self, '_no_fork', False)) else False
-        if aux:
-            ops.wait_stream(aux, ops.current_stream())
-            with ops.on_stream(aux):
-                g_feat, dx2, tmp = distill_terms()
+        # (the student discriminator's pass and the distillation block only meet in dL/d(fake); running the block on the auxiliary
+        # stream beside the pass measured slower -- replayed 8.42 -> 9.0 ms, profiles/r4an_sagan_fork.txt: the chains are too
+        # short to pay for a third stream)
         dx = own_d()
         ops.nhwc_copy(dx, 0, gc.g_out, 0, 3)
         if self.distill:
-            if aux:
-                ops.wait_stream(ops.current_stream(), aux)
-            else:
-                g_feat, dx2, tmp = distill_terms()
+            g_feat, dx2, tmp = distill_terms()
             ops.nhwc_add(dx2, 0, gc.g_out, 0, 3)
             ops.nhwc_add(tmp, 0, gc.g_out, 0, 3)
             self._mark_teacher_free()
@@ -392,8 +378,6 @@ class SAGANModel(TeacherStreamMixin, nn.Module):
         ts = None
         if self.opt.online_distillation:
             T = self.teacher_model
-
-            T._no_fork = True            # the online teacher already runs on a stream of its own
 
             def teacher_step():
                 T.set_input(self.input)

@@ -34,9 +34,9 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 VGG19_CFG = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M')
 
 
-# GCC_SR_FORK (default 1): backward_G's VGG chain on the auxiliary stream beside the discriminator's pass over the fake
-SR_FORK = os.environ.get('GCC_SR_FORK', '1') != '0'
-TEACHER_CHAIN_WGRAD = os.environ.get('GCC_SR_TEACHER_CHAIN_WGRAD', '0') == '1'
+# backward_G's VGG chain on the auxiliary stream beside the discriminator's pass over the fake (False: in line, the serialized
+# reference of tests/test_replay_gpu.py::test_srgan_vgg_fork_changes_nothing)
+SR_FORK = True
 
 class ConvolutionalBlock(nn.Module):
     """conv (padding k // 2) [+ BatchNorm] [+ DifferentiableOP] [+ PReLU | LeakyReLU(0.2) | Tanh]  (models/SRGAN.py:15-70)"""
@@ -375,7 +375,7 @@ class SRGAN(TeacherStreamMixin, nn.Module):
             return self.V.backward(vf, g_ff)
 
         # the VGG chain (two forwards, one backward; frozen weights) and the discriminator's pass over the fake only meet in
-        # dL/d(fake_n): the VGG chain runs on the auxiliary stream beside the discriminator's (GCC_SR_FORK; the online teacher,
+        # dL/d(fake_n): the VGG chain runs on the auxiliary stream beside the discriminator's (SR_FORK; the online teacher,
         # already on a stream of its own, keeps it in line); the two gradients are added in the reference's order
         aux = self._aux_stream() if (SR_FORK and not getattr(self, '_no_fork', False)) else False
         if aux:
@@ -452,13 +452,7 @@ class SRGAN(TeacherStreamMixin, nn.Module):
 
             def teacher_step():
                 T.set_input(self.input)
-                prev = engine.OVERLAP_WGRAD
-                if TEACHER_CHAIN_WGRAD:          # the teacher's weight gradients on its own stream: one HIP stream fewer
-                    engine.OVERLAP_WGRAD = False
-                try:
-                    T.optimize_parameters()
-                finally:
-                    engine.OVERLAP_WGRAD = prev
+                T.optimize_parameters()
                 self.target_distillation_features = T.get_distillation_features()     # read after _join
             ts = self._run_teacher(teacher_step)
         self.forward()

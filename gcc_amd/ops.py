@@ -439,12 +439,9 @@ def _geom(t):
 # ---- the tile plan of the convolution calls (include/gcc_hip.h gcc_conv_plan_t) ------------------------------------------
 # It travels with every call (conv_desc) instead of living in the library as process-wide options (rounds 2-4).  A model class
 # states the plan of its schedule at the head of each phase (models/_streams.py _ensure_plan); the statement is THREAD-local, so
-# the teacher's enqueue thread and the main thread -- or two models of different schedules -- never see each other's.
-# GCC_IGEMM_TILES / GCC_IGEMM_BIG_MIN / GCC_IGEMM_BIG_NK / GCC_IGEMM_PAIR / GCC_HALO_HC / GCC_WGRAD_WGS_BIG / GCC_WGRAD_WGS in
-# the environment pin a field for A/B runs (an explicit value wins over what the schedule asks for, as before).
-_PLAN_ENV = {'tile_families': 'GCC_IGEMM_TILES', 'big_min': 'GCC_IGEMM_BIG_MIN', 'big_nk': 'GCC_IGEMM_BIG_NK', 'pair': 'GCC_IGEMM_PAIR',
-             'halo_hc': 'GCC_HALO_HC', 'wgrad_wgs_big': 'GCC_WGRAD_WGS_BIG', 'wgrad_wgs': 'GCC_WGRAD_WGS'}
-_plan_pinned = {f: int(os.environ[e]) for f, e in _PLAN_ENV.items() if os.environ.get(e, '') not in ('', '-1')}
+# two host threads -- or two models of different schedules -- never see each other's.  plan_override changes fields for the calls
+# inside it; _plan_pinned holds fields against every statement (tests: a whole model step under another tile plan).
+_plan_pinned = {}
 _plan_tls = threading.local()
 _PLAN_DEFAULT = (0,) * len(_lib.PLAN_FIELDS)
 
@@ -474,7 +471,7 @@ def current_plan():
 
 
 class plan_override:
-    """with plan_override(halo_hc=1): ... -- the current plan with some fields changed, for the calls inside (environment pins win)"""
+    """with plan_override(halo_hc=1): ... -- the current plan with some fields changed, for the calls inside (pins win)"""
 
     def __init__(self, **fields):
         self.fields = fields
@@ -518,7 +515,7 @@ def pack_weights_into(master, w, wt):
                                  wt.data_ptr() if wt is not None else None, stream()), 'gcc_pack_weights')
 
 
-FUSED_PACK = os.environ.get('GCC_FUSED_PACK', '1') != '0'
+FUSED_PACK = True      # False (tests' reference): W and Wt of a tile packed by separate reads of the master
 
 
 class PackPlan:
@@ -576,7 +573,7 @@ def _epilogue(bias, act, slope, stats, d=None, dgrad=0, device=None, bn=None):
 
 
 Y2_RELU, Y2_GATE = 1, 2        # gcc_epilogue_t.y2_mode
-CONV_Y2 = os.environ.get('GCC_CONV_Y2', '1') != '0'      # A/B hook: 0 = always the separate gcc_bnact_fwd launch
+CONV_Y2 = True      # False (tests' reference): always the separate gcc_bnact_fwd launch
 
 
 def conv_fprop(x, w, Co, k, stride, pad, out=None, bias=None, act=ACT_NONE, slope=0.2, want_stats=False, bn=None,
@@ -898,7 +895,7 @@ def in_finalize(stats, count, st, eps=1e-5):
                                 st.scale.data_ptr(), st.shift.data_ptr(), stream()), 'gcc_in_finalize')
 
 
-INORM_FUSED_MAX_HW = int(os.environ.get('GCC_INORM_FUSED_MAX_HW', str(1 << 20)))   # planes above this take the three-pass route
+INORM_FUSED_MAX_HW = 1 << 20     # planes above this take the three-pass route
 INORM_WS_BYTES = 4096 + (3 << 19)      # include/gcc_hip.h: GCC_INORM_WORKSPACE_BYTES
 _inorm_ws = {}
 _zero_ws = {}
@@ -929,15 +926,16 @@ def tail_workspace(device):
     return ws
 
 
-FOLD_GRID = os.environ.get('GCC_FOLD_GRID', '1') != '0'      # the U-Net's split layers: fold + BatchNorm + activation as one full-chip kernel (GCC_OPT_FUSE_BN 3)
-IN_CONV_FINALIZE = os.environ.get('GCC_IN_CONV_FINALIZE', '1') != '0'      # the conv launch's last-arriving workgroups finalize (0: a gcc_bn_finalize launch; profiles/r4_summary.md)
+# the conv launch's last-arriving workgroups finalize (False, the tests' reference: a gcc_bn_finalize launch; profiles/r4_summary.md)
+IN_CONV_FINALIZE = True
 
 
 def bn_desc(bn_module, st, count, device, running=True):
     """gcc_bn_t of a training-mode BatchNorm2d application: statistics of `count` pixels, coefficients into the BNState `st`;
     running=False leaves running_mean / running_var alone (a pass that runs ahead of its place: engine.PatchGANEngine)"""
+    # the tail workspace also serves the U-Net's split layers: fold + BatchNorm + activation as one full-chip kernel (GCC_OPT_FUSE_BN 3)
     # (bench.py's bracketed roofline step times every conv launch on its own: no finalize tail inside it there)
-    ws = tail_workspace(device) if ((IN_CONV_FINALIZE or FOLD_GRID) and not PROFILE.active) else None
+    ws = tail_workspace(device) if not PROFILE.active else None
     return _lib.bn_t(bn_module.weight.data_ptr(), bn_module.bias.data_ptr(), bn_module.eps, bn_module.momentum, float(count),
                      bn_module.running_mean.data_ptr() if running else None, bn_module.running_var.data_ptr() if running else None,
                      st.mean.data_ptr(), st.rstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(),
@@ -1025,16 +1023,17 @@ def bnact_fwd(x, y, y2=None, scale=None, shift=None, gate=None, gate_after_act=F
     check(lib().gcc_bnact_fwd(C.byref(p), xp, ldx, 0, yp, ldy, 0, y2p, ldy2, 0, Cc, pixels, stream()), 'gcc_bnact_fwd')
 
 
-BN_BWD_TAIL = os.environ.get('GCC_BN_BWD_TAIL', '0') == '1'      # 1: the reduce launch's last-arriving workgroups finalize (measured: profiles/r4_summary.md)
-BN_BWD_GRID = os.environ.get('GCC_BN_BWD_GRID', '1') != '0'
+# Routes of the BatchNorm backward; the tests set the other values to compare the routes (the product keeps these)
+BN_BWD_TAIL = False      # True: the reduce launch's last-arriving workgroups finalize (measured: profiles/r4_summary.md)
+BN_BWD_GRID = True
 # gcc_bn_bwd_one_launch_ex (the U-Net's layers): 0 off; 1 (default) tensors of <= BN_BWD_GRID_EX_MAX_PIXELS pixels; 2 every size
-BN_BWD_GRID_EX = int(os.environ.get('GCC_BN_BWD_GRID_EX', '1'))
-BN_BWD_GRID_EX_MAX_PIXELS = int(os.environ.get('GCC_BN_BWD_GRID_EX_MAX_PIXELS', '4096'))
+BN_BWD_GRID_EX = 1
+BN_BWD_GRID_EX_MAX_PIXELS = 4096
 BN_BWD_GRID_MIN_PIXELS = 4096        # at or below: bnact_bwd_small_kernel (one workgroup per 8 channels) is the one-launch form
 # above: reduce + finalize + apply.  The one-launch kernel runs on the grid family's 4 x CUs / Q workgroups (one wave per SIMD): it wins
 # while the tensor is a few launches' worth of latency and loses once it is bandwidth (profiles/r5_bn_bwd_paths.txt: 9.4 MB 23.7 against
 # 25.7 us, 18.9 MB 44.4 against 36.6, 151 MB 388 against 204)
-BN_BWD_GRID_MAX_BYTES = int(os.environ.get('GCC_BN_BWD_GRID_MAX_BYTES', str(12 << 20)))
+BN_BWD_GRID_MAX_BYTES = 12 << 20
 
 
 def bnact_bwd(x, y, g1, dx, g2=None, bn=None, gamma=None, beta=None, bn_eval=False, gate=None, gate_after_act=False,
@@ -1145,9 +1144,6 @@ def spectral_power_iteration(w_bar, u, v, t_out, sigma_out, w_eff, slot='sn_fwd'
     check(lib().gcc_spectral_power_iteration(w_bar.data_ptr(), u.data_ptr(), v.data_ptr(), R, Cc, kh * kw, t_out.data_ptr(),
                                              sigma_out.data_ptr(), w_eff.data_ptr(), ws.data_ptr(), ws.numel(), stream()),
           'gcc_spectral_power_iteration')
-
-
-SN_FUSED_PACK = os.environ.get('GCC_SN_FUSED_PACK', '1') != '0'
 
 
 def spectral_power_iteration_pack(w_bar, u, v, t_out, sigma_out, w, wt, slot='sn_fwd'):

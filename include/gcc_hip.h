@@ -6,7 +6,7 @@
  * it replaces (paths relative to the reference root).  Conventions:
  *   - plain C, no torch types; every pointer is a DEVICE pointer owned by the caller (activations,
  *     weights, workspaces); the library allocates nothing.  What a launch does is decided by its arguments
- *     (the tile plan travels in gcc_conv_t.plan); the only process-wide state is the table of A/B tuning hooks below
+ *     (the tile plan travels in gcc_conv_t.plan); the only process-wide state is the table of route switches below
  *     (gcc_set_option: atomics, defaults read once from GCC_* environment variables; the product leaves them alone), the one-time hipFuncSetAttribute of the kernels that use > 64 KB of LDS, and the RCCL entry
  *     points resolved on the first gcc_comm_* call (communicators themselves are explicit objects the caller owns);
  *   - every kernel is enqueued on the caller's `stream` and never synchronises;
@@ -44,7 +44,7 @@ enum { GCC_ACT_NONE = 0, GCC_ACT_LRELU = 1, GCC_ACT_RELU = 2, GCC_ACT_TANH = 3 }
 /* ABI generation of this header: bumped whenever a struct layout, an enum numbering or a prototype below changes.  gcc_version()
  * of the library a host loads must return exactly this number (gcc_amd/_lib.py refuses any other; an external host should check it
  * the same way): a stale .so reads gcc_conv_t.plan past its struct and sets the wrong option ids without any error. */
-#define GCC_HIP_ABI 603
+#define GCC_HIP_ABI 604
 
 const char* gcc_strerror(int code);
 int gcc_version(void); /* == GCC_HIP_ABI of the header the library was built from */
@@ -57,52 +57,32 @@ long long gcc_launch_count(int reset);
 int gcc_device_error(int clear);
 
 /* ---------------------------------------------------------------------------------------------
- * Tuning hooks: which kernel family a geometry is routed to.  Every option only selects between kernels that compute the same
- * result (the parity tests run the cases under each).  These are A/B switches for measurements and tests -- NOT the way a host
- * chooses its schedule: everything the model classes switch at run time (tile families, pair split, halo columns, weight-
- * gradient split targets) travels with the call in gcc_conv_t.plan, and the product runs with every hook at its default
- * (bench.py prints the vector and refuses to run otherwise).  Defaults come from the environment variable of the same name
- * (GCC_<NAME>) when it is set at first use.  gcc_set_option(id, value): value < 0 restores the default; returns the previous
- * value (>= 0) or GCC_ERR_BAD_ARG.  Process-wide atomics: set them while nothing is being launched.
+ * Route switches: which kernel family a geometry is routed to.  Every option only selects between kernels that compute the same
+ * result: the tests set them to run a case down both routes and compare.  They are NOT the way a host chooses its schedule:
+ * everything the model classes switch at run time (tile families, pair split, halo columns, weight-gradient split targets)
+ * travels with the call in gcc_conv_t.plan, and the product runs with every option at its default (bench.py prints the vector
+ * and refuses to run otherwise).  Defaults come from the environment variable of the same name (GCC_<NAME>) when it is set at
+ * first use.  gcc_set_option(id, value): value < 0 restores the default; returns the previous value (>= 0) or GCC_ERR_BAD_ARG.
+ * Process-wide atomics: set them while nothing is being launched.
  * The shipped library holds no diagnostic ablation: the "results are wrong" switches of the earlier rounds (main loops without
  * staging loads, a grid exchange made to time out) exist only in the GCC_DIAG_BUILD variant (csrc/build.sh: libgcc_hip_diag.so,
  * same ABI plus gcc_diag_set(bits)), which tests and probes load explicitly through GCC_HIP_LIB.
  * ------------------------------------------------------------------------------------------- */
 enum {
-    GCC_OPT_IGEMM_GLDS = 0,       /* 1 (default): LDS-DMA staging; 0: register-staged 128-pixel tiles */
-    GCC_OPT_IGEMM_HEAD,         /* 1 (default): single-output-channel head route */
-    GCC_OPT_IGEMM_THIN,         /* 1 (default): thin image-layer kernels; 2: without the LDS-staged wide (65..128 channel) data-gradient form; 0: none */
-    GCC_OPT_WGRAD_BIG,          /* 1 (default): 256x256 weight-gradient tiles on the large layers */
-    GCC_OPT_BN_SWEEPS,          /* 0 (default): per-kernel choice of sweeps per streaming workgroup */
-    GCC_OPT_BN_MAXBLK,          /* cap on streaming workgroups (default 2048) */
-    GCC_OPT_BN_REDUCE_THREADS,  /* 256 (default) or 1024 threads per BatchNorm-backward reduce workgroup */
-    GCC_OPT_BN_REDUCE_CAP,      /* cap on those workgroups (default 1024) */
-    GCC_OPT_INORM_LPP,          /* 0 (default): automatic lanes per pixel of the one-launch InstanceNorm */
-    GCC_OPT_IGEMM_FORCE_BC,     /* tuning: 0 (default) automatic; 16 / 32 / 64 / 128: channel width of the 128-pixel tiles */
-    GCC_OPT_IGEMM_FORCE_KSPLIT, /* tuning: 0 (default) automatic; n >= 1: K slices of a 128-pixel-tile launch (1 = never split) */
-    GCC_OPT_IGEMM_NARROW,       /* 1 (default): 128-pixel tiles narrow to 64 / 32 channels until the launch has >= 256 workgroups, and
-                                   K is split only for loops of >= 48 steps (0: the round-1 plan) */
-    GCC_OPT_WGRAD_BIG_MIN_TILES,/* minimum number of 256x256 output tiles for the big weight-gradient tiling (default 8: from the PatchGAN's 128 -> 256 layer up; 32 until round 6: +0.3 % on the step, profiles/r6_ab_wgrad_big_min_tiles.txt) */
+    GCC_OPT_IGEMM_THIN = 0,     /* 1 (default): thin image-layer kernels; 2: without the LDS-staged wide (65..128 channel) data-gradient form; 0: none */
     GCC_OPT_FUSE_BN,            /* gcc_conv_bn_act: 3 (default; profiles/r4_summary.md): a split layer's K slices folded, statistics exchanged inside the
                                    launch and rows normalised by one kernel on the whole chip (bn_fold_grid_kernel; needs gcc_bn_t.tail_ws; other
                                    layers as 1); 2: BatchNorm finalized by the last-arriving workgroups of the launch that writes the statistic
                                    rows (gcc_bn_t.tail_ws), split layers folded by one full-chip kernel; 1: the round-2 form (a split layer's
                                    partials, statistics, finalize and normalise in one kernel of C / 8 workgroups); 0: separate launches */
     GCC_OPT_BN_BWD_SMALL,       /* 1 (default): gcc_bnact_bwd of <= 4096 pixels (training BatchNorm, no gate) runs as one kernel instead of
-                                   three, gcc_channel_sum of <= 16384 pixels as one instead of two */
-    GCC_OPT_WGRAD_ROW_TABLE,    /* 1 (default): the weight-gradient kernel decomposes each pixel of a workgroup's range once, into an LDS table
-                                   (gather base + validity mask), instead of in every lane at every k-step (0: the round-2 form;
-                                   kernels taller or wider than 15 taps always take that form) */
+                                   three, gcc_channel_sum of <= GCC_CHANSUM_SMALL_MAX_PIXELS pixels as one instead of two */
     GCC_OPT_IGEMM_HALO,         /* 3 (default): also k3 s1 p1 convolutions on a 16-divisible grid (9 taps per staged slice: the VGG19 layers of SRGAN's
                                    perceptual loss, 10-25 % per layer, profiles/r4as_halo_3x3.txt); 2: also k4 s1 p1 convolutions on a 16-divisible grid (16 taps per staged slice); 1: k4 s2 p1 convolutions whose geometry fits (channels per tap a multiple of 64, 256 output channels
                                    per tile, output rows that tile 256 pixels) stage each 64-channel slice of the input neighbourhood of a
                                    256-pixel tile ONCE in LDS and serve the taps that share it from there (conv_halo.hip); 0: the gather
                                    kernel re-stages the pixels for every tap */
-    GCC_OPT_FUSE_BN_PARTIAL_KB, /* gcc_conv_bn_act: cap (KB of fp32 partial tiles, default 4096) on the K split of the layers whose fold + statistics +
-                                   normalise run as one kernel: every slice is another copy of the output that kernel reads back */
     GCC_OPT_INORM_GRID,         /* 1 (default): gcc_inorm_fwd / _bwd with a workspace split an image's plane over workgroups (in-launch barrier); 0: slab kernels */
-    GCC_OPT_IGEMM_STAGES,       /* 3 (default): the 128-pixel x 32 / 64-column tiles (uniform taps) keep two k-steps of LDS-DMA in flight behind
-                                   the one being multiplied (three LDS stages); 2: one (the round-1 loop) */
     GCC_OPT_WGRAD_TS,           /* 1 (default): k4 s1 p1 weight gradients with channels in multiples of 64, >= 32 channel tiles and >= 16 pixel
                                    blocks per split, and k3 s1 p1 ones with channels in multiples of 64 and >= 128 workgroups of >= 8 blocks, run
                                    tap-stationary (wgrad_ts_kernel<4 / 3>: the 16 / 9 taps share one staged halo image of the input);
@@ -449,10 +429,11 @@ int gcc_dwconv3x3_reflect_wgrad(const void* x, int ldx, const void* dy, int lddy
 int gcc_channel_sum(const void* x, int ld, int off, int C, size_t pixels, float* out, int accumulate,
                     void* ws, size_t ws_bytes, gcc_stream_t stream);
 size_t gcc_channel_sum_workspace(int C, size_t pixels);
-/* several channel sums of <= 16384 pixels each (the bias gradients of the layers of one grouped weight gradient) as ONE launch;
- * entry i is gcc_channel_sum(x, ld, off, C, pixels, out, accumulate, ..) bit for bit.  n <= GCC_CHANSUM_GROUP_MAX;
- * GCC_ERR_UNSUPPORTED when an entry has more pixels (the caller keeps it on gcc_channel_sum). */
+/* several channel sums of <= GCC_CHANSUM_SMALL_MAX_PIXELS pixels each (the bias gradients of the layers of one grouped weight
+ * gradient) as ONE launch; entry i is gcc_channel_sum(x, ld, off, C, pixels, out, accumulate, ..) bit for bit.
+ * n <= GCC_CHANSUM_GROUP_MAX; GCC_ERR_UNSUPPORTED when an entry has more pixels (the caller keeps it on gcc_channel_sum). */
 #define GCC_CHANSUM_GROUP_MAX 24
+#define GCC_CHANSUM_SMALL_MAX_PIXELS 16384   /* also the limit of gcc_channel_sum's one-launch form (GCC_OPT_BN_BWD_SMALL) */
 typedef struct {
     const void* x;
     int ld, off, C;

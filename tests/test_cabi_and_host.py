@@ -121,12 +121,11 @@ def test_weight_gradient_plan_follows_the_schedule(monkeypatch):
     """models/_streams.py + ops.set_plan: every model instance keeps the tile plan its schedule asked for and states it at the
     head of its phases, for the thread that enqueues: the production plan halves the workgroup targets of split weight-gradient
     launches and leaves the pair split off, the alone plan keeps the library's defaults with the pair split (and the 128-column
-    halo tiles) on; an explicit GCC_WGRAD_WGS* environment value wins; two instances with different plans each get their own
-    when their turn comes; another THREAD never sees either (the plan travels in gcc_conv_t.plan, round 5: no library state)"""
+    halo tiles) on; a pinned field (ops._plan_pinned) wins; two instances with different plans each get their own when their
+    turn comes; another THREAD never sees either (the plan travels in gcc_conv_t.plan, round 5: no library state)"""
     import threading
     from gcc_amd import ops
     from gcc_amd.models._streams import TeacherStreamMixin as M
-    monkeypatch.delenv('GCC_PAIR_CONCURRENT', raising=False)
     monkeypatch.setattr(ops, '_plan_pinned', {})
 
     class Fake(M):
@@ -156,7 +155,7 @@ def test_weight_gradient_plan_follows_the_schedule(monkeypatch):
         assert state() == (1, 1, 0, 0)
         a.set_stream_schedule(False, plan='production')      # one stream under the production plan (bench.py's bracketed step)
         assert state() == (0, 0, 128, 256)
-        monkeypatch.setattr(ops, '_plan_pinned', {'wgrad_wgs': 512})       # GCC_WGRAD_WGS=512 in the environment
+        monkeypatch.setattr(ops, '_plan_pinned', {'wgrad_wgs': 512})
         a.set_stream_schedule(True)
         assert state() == (0, 0, 128, 512)
     finally:
@@ -293,12 +292,12 @@ def test_tile_plan_travels_with_the_call():
     assert ws(conv(16, 32, 32, 512, 1024, 4, 1, 1, pair=1)) >= 128 * 256 * 256 * 4 > ws(l4)
     assert lib.gcc_options_default() == 1 or any(os.environ.get('GCC_' + n) is not None for n in _lib.OPT_NAMES)
     try:
-        prev = lib.gcc_set_option(_lib.OPT_WGRAD_BIG, 0)
-        assert prev == 1 and lib.gcc_get_option(_lib.OPT_WGRAD_BIG) == 0 and lib.gcc_options_default() == 0
+        prev = lib.gcc_set_option(_lib.OPT_WGRAD_TS, 0)
+        assert prev == 1 and lib.gcc_get_option(_lib.OPT_WGRAD_TS) == 0 and lib.gcc_options_default() == 0
         assert lib.gcc_set_option(99, 1) < 0 and lib.gcc_get_option(-1) < 0
     finally:
-        lib.gcc_set_option(_lib.OPT_WGRAD_BIG, -1)
-    assert lib.gcc_get_option(_lib.OPT_WGRAD_BIG) == 1
+        lib.gcc_set_option(_lib.OPT_WGRAD_TS, -1)
+    assert lib.gcc_get_option(_lib.OPT_WGRAD_TS) == 1
     assert not hasattr(lib, 'gcc_diag_set') or True       # (the shipped library exports no diagnostic switch: checked below)
     import subprocess
     syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], capture_output=True, text=True).stdout
@@ -375,7 +374,8 @@ def test_flat_params_redirect_is_a_host_side_pointer_swap():
 
 def test_struct_layouts_match_header(tmp_path):
     """the ctypes mirrors of gcc_amd/_lib.py against the header itself: a C program that includes include/gcc_hip.h prints
-    sizeof and the offset of the last field of every struct the shim mirrors (gcc, the host compiler a binding would use)"""
+    sizeof and the offset of the last field of every struct the shim mirrors (gcc, the host compiler a binding would use), and
+    the limits and the option count the shim mirrors as constants"""
     import subprocess
     from gcc_amd import _lib
     pairs = [('gcc_conv_plan_t', _lib.conv_plan_t, 'wgrad_wgs'), ('gcc_conv_t', _lib.conv_t, 'plan'), ('gcc_epilogue_t', _lib.epilogue_t, 'y2_gate'),
@@ -385,6 +385,11 @@ def test_struct_layouts_match_header(tmp_path):
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "gcc_hip.h"\nint main(void) {\n'
     for cname, _, last in pairs:
         src += '  printf("%s %%zu %%zu\\n", sizeof(%s), %s);\n' % (cname, cname, 'offsetof(%s, %s)' % (cname, last) if last else '(size_t)0')
+    limits = {'GCC_WGRAD_GROUP_MAX': _lib.WGRAD_GROUP_MAX, 'GCC_CHANSUM_GROUP_MAX': _lib.CHANSUM_GROUP_MAX,
+              'GCC_SPECTRAL_GROUP_MAX': _lib.SPECTRAL_GROUP_MAX, 'GCC_CHANSUM_SMALL_MAX_PIXELS': _lib.CHANSUM_SMALL_MAX_PIXELS,
+              'GCC_OPT_COUNT_': _lib.OPT_COUNT}
+    for name in limits:
+        src += '  printf("%s %%zu 0\\n", (size_t)(%s));\n' % (name, name)
     src += '  return 0;\n}\n'
     c = tmp_path / 'layout.c'
     c.write_text(src)
@@ -395,6 +400,9 @@ def test_struct_layouts_match_header(tmp_path):
         assert ctypes.sizeof(ct) == out[cname][0], (cname, ctypes.sizeof(ct), out[cname][0])
         if last:
             assert getattr(ct, last).offset == out[cname][1], (cname, last)
+    for name, mirrored in limits.items():
+        assert out[name][0] == mirrored, (name, out[name][0], mirrored)
+    assert len(_lib.OPT_NAMES) == _lib.OPT_COUNT
     assert ctypes.sizeof(_lib.conv_t) == 13 * 4 + 7 * 4 and _lib.conv_t.plan.offset == 13 * 4
 
 

@@ -545,7 +545,7 @@ def test_full_config_iteration_vs_oracle(plan, batch, monkeypatch):
     from oracle import gcc_oracle as O
     from tests.golden.recipe import recipe_state_dict, recipe_transform
     from gcc_amd import ops
-    # (pinned like a GCC_IGEMM_* environment value: the model classes state their own plan at the head of every phase)
+    # (pinned: the model classes state their own plan at the head of every phase)
     monkeypatch.setattr(ops, '_plan_pinned', dict(tile_families=3, big_min=1, big_nk=1) if plan == 'tile256' else {})
     try:
         model, teacher, opt = build_model(FULL_ARGV)

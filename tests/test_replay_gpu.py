@@ -124,16 +124,6 @@ def test_replay_invalidate_and_shape_change():
     torch.cuda.synchronize()
 
 
-def test_teacher_enqueue_thread_changes_nothing(monkeypatch):
-    """GCC_TEACHER_THREAD=1 (the teacher's step enqueued by a second host thread, models/_streams.py): same bits"""
-    m0, l0, s0, _ = _run(_cyclegan, 1, False, iters=3)
-    monkeypatch.setenv('GCC_TEACHER_THREAD', '1')
-    m1, l1, s1, _ = _run(_cyclegan, 1, False, iters=3)
-    assert l0 == l1
-    bad = [k for k in s0 if not torch.equal(s0[k], s1[k])]
-    assert not bad, bad[:8]
-
-
 def test_pix2pix_stream_forks_change_nothing(monkeypatch):
     """the two stretches of the Pix2Pix step that run independent chains side by side on the auxiliary stream (round 4:
     Pix2Pix.DISTILL_FORK -- the distillation terms on the generator's features beside the teacher discriminator's pass over
@@ -143,37 +133,18 @@ def test_pix2pix_stream_forks_change_nothing(monkeypatch):
     from gcc_amd.models import Pix2Pix as P
     monkeypatch.setattr(P, 'DISTILL_FORK', False)
     monkeypatch.setattr(P, 'ARCH_FORK', False)
-    monkeypatch.setattr(P, 'ARCH_EARLY', False)
-    m0, l0, s0, _ = _run(_pix2pix, 1, False, iters=5)
-    # (ARCH_EARLY: the online teacher's architecture-step forward started before the student has finished reading the teacher:
-    # second set of generator activations, deferred BatchNorm running updates of the teacher's discriminator)
     monkeypatch.setattr(P, 'ARCH_FREE_EARLY', False)
-    for fork in ((True, False, False, False), (False, True, False, False), (False, False, True, False), (False, False, False, True),
-                 (True, True, True, True)):
-        # (fork[3], ARCH_FREE_EARLY: the teacher's stream copies its difference scalar itself and is released behind its own
+    m0, l0, s0, _ = _run(_pix2pix, 1, False, iters=5)
+    for fork in ((True, False, False), (False, True, False), (False, False, True), (True, True, True)):
+        # (fork[2], ARCH_FREE_EARLY: the teacher's stream copies its difference scalar itself and is released behind its own
         # architecture-step part)
         monkeypatch.setattr(P, 'DISTILL_FORK', fork[0])
         monkeypatch.setattr(P, 'ARCH_FORK', fork[1])
-        monkeypatch.setattr(P, 'ARCH_EARLY', fork[2])
-        monkeypatch.setattr(P, 'ARCH_FREE_EARLY', fork[3])
+        monkeypatch.setattr(P, 'ARCH_FREE_EARLY', fork[2])
         m1, l1, s1, _ = _run(_pix2pix, 1, False, iters=5)
         assert l0 == l1, 'logged losses differ with forks %s' % (fork,)
         bad = [k for k in s0 if not torch.equal(s0[k], s1[k])]
         assert not bad, 'forks %s: %s' % (fork, bad[:8])
-
-
-def test_sagan_distill_fork_changes_nothing(monkeypatch):
-    """SAGAN.G_FORK: backward_G's distillation block on the auxiliary stream beside the discriminator's pass -- eager and
-    replayed -- against the in-line order: same bits"""
-    from gcc_amd.models import SAGAN as Sa
-    monkeypatch.setattr(Sa, 'G_FORK', False)
-    m0, l0, s0, _ = _run(_sagan, 1, False, iters=5)
-    monkeypatch.setattr(Sa, 'G_FORK', True)
-    for enabled, threads in ((False, 1), (True, 4)):
-        m1, l1, s1, info = _run(_sagan, threads, enabled, iters=5)
-        assert l0 == l1, 'logged losses differ (replay %s)' % enabled
-        bad = [k for k in s0 if not torch.equal(s0[k], s1[k])]
-        assert not bad, 'fork (replay %s): %s' % (enabled, bad[:8])
 
 
 def test_srgan_vgg_fork_changes_nothing(monkeypatch):
@@ -192,19 +163,19 @@ def test_srgan_vgg_fork_changes_nothing(monkeypatch):
 
 def test_cyclegan_two_sides_fork_changes_nothing(monkeypatch):
     """CycleGAN.CYCLE_FORK: side B of forward / backward_G / backward_D / the architecture step on the auxiliary stream beside
-    side A -- eager and replayed -- against the in-line order: every weight, optimizer moment and logged loss bit for bit"""
+    side A (student and online teacher, weight gradients on their chains) -- eager and replayed -- against the in-line order
+    (weight gradients on side streams): every weight, optimizer moment and logged loss bit for bit"""
     from gcc_amd.models import CycleGAN as Cg
-    monkeypatch.setattr(Cg, 'CYCLE_FORK', 0)
+    monkeypatch.setattr(Cg, 'CYCLE_FORK', False)
     m0, l0, s0, _ = _run(_cyclegan, 1, False, iters=5)
-    for mode, enabled, threads in ((1, False, 1), (1, True, 4), (2, False, 1), (2, True, 4)):
-        # 1: the student's sides, weight gradients on side streams; 2: the teacher's sides too, weight gradients on their chains
-        monkeypatch.setattr(Cg, 'CYCLE_FORK', mode)
+    monkeypatch.setattr(Cg, 'CYCLE_FORK', True)
+    for enabled, threads in ((False, 1), (True, 4)):
         m1, l1, s1, info = _run(_cyclegan, threads, enabled, iters=5)
         if enabled:
             assert m1[-1] == 'replay' and info['streams'] >= 3, (m1, info)
-        assert l0 == l1, 'logged losses differ (mode %d, replay %s)' % (mode, enabled)
+        assert l0 == l1, 'logged losses differ (replay %s)' % enabled
         bad = [k for k in s0 if not torch.equal(s0[k], s1[k])]
-        assert not bad, 'fork mode %d (replay %s): %s' % (mode, enabled, bad[:8])
+        assert not bad, 'fork (replay %s): %s' % (enabled, bad[:8])
 
 
 @pytest.mark.parametrize('which', ['srgan', 'cyclegan'])
