@@ -27,6 +27,7 @@ from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
 from .Pix2Pix import HipAdam, MobileResnetGenerator, _patchgan_tree, _portable
+from ._resume import TrainingStateMixin
 from ._streams import TeacherStreamMixin
 
 HEAVY_SPARSITY = ('model.1', 'model.4', 'model.19', 'model.22')      # models/CycleGAN.py:243, 548-569
@@ -124,6 +125,33 @@ class ImagePool:
             ops.image_pool_query(images[lo:hi], out[lo:hi], self.store, self.sel)
         return out
 
+    def _padded(self, store):
+        """the whole NHWC buffer behind a store view, pad channels included: [P, H, W, ld]"""
+        P, _, H, W = store.shape
+        ld = store.stride(3)
+        return torch.as_strided(store, (P, H, W, ld), (H * W * ld, W * ld, ld, 1), store.storage_offset())
+
+    def state(self):
+        """fill count and history (CPU copy of the padded device store; None before the first query)"""
+        store = None if self.store is None else {'shape': tuple(self.store.shape),
+                                                 'data': self._padded(self.store).detach().to('cpu').clone()}
+        return {'pool_size': self.pool_size, 'count': self.count, 'store': store}
+
+    def load_state(self, state, device):
+        if state['pool_size'] != self.pool_size:
+            raise GccError('image pool state holds %d images, this pool %d' % (state['pool_size'], self.pool_size))
+        self.count = int(state['count'])
+        src = state['store']
+        if src is None:
+            return
+        P, Cc, H, W = src['shape']
+        if self.store is None:
+            self.store = ops.new_act(P, Cc, H, W, device)
+            self.sel = torch.zeros(16, dtype=torch.int32, device=device)
+        elif tuple(self.store.shape) != (P, Cc, H, W):
+            raise GccError('image pool state holds %s images, this pool %s' % (src['shape'], tuple(self.store.shape)))
+        self._padded(self.store).copy_(src['data'])
+
 
 class _PoolGroup:
     """one group of <= 8 images of an ImagePool.query: the unit a recorded gcc_write_i32 launch is patched by"""
@@ -149,7 +177,7 @@ class _Half:
         self.out, self.g_out = full.out[lo:hi], full.g_out[lo:hi]
 
 
-class MobileCycleGANModel(TeacherStreamMixin, nn.Module):
+class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def __init__(self, opt, cfg_AtoB=None, cfg_BtoA=None):
         super().__init__()

@@ -30,6 +30,7 @@ from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
 from .Pix2Pix import HipAdam, _portable
+from ._resume import TrainingStateMixin
 from ._streams import TeacherStreamMixin
 
 
@@ -154,7 +155,7 @@ def _is_dup(name):
     return ('.module.' in name) or ('_conv.' in name)
 
 
-class SAGANModel(TeacherStreamMixin, nn.Module):
+class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def __init__(self, opt, filter_cfgs=None, channel_cfgs=None):
         super().__init__()

@@ -27,6 +27,7 @@ from .._lib import GccError, check
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
 from .Pix2Pix import HipAdam, _portable
+from ._resume import TrainingStateMixin
 from ._streams import TeacherStreamMixin
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -154,7 +155,7 @@ class TruncatedVGG19(nn.Module):
         self.truncated_vgg19.load_state_dict({k: sd['features.' + k] for k in own})
 
 
-class SRGAN(TeacherStreamMixin, nn.Module):
+class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def __init__(self, opt, filter_cfgs=None, channel_cfgs=None, vgg_widths=None):
         super().__init__()

@@ -13,11 +13,14 @@ the arithmetic downstream of those networks -- and keeps the reference's best-ch
 """
 import copy
 import os
+import random
+import tempfile
 import time
 
 import torch
 
 from . import dist as gdist
+from ._lib import GccError
 from .models import get_model_class
 from .options import options
 from .utils import util
@@ -107,10 +110,72 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
     return [v for v, _ in scores]
 
 
+STATE_FILE = 'training_state.pth'
+# options that may differ between the run that wrote a training state and the run that resumes from it: they change neither the
+# arithmetic nor the data of an epoch (save_epoch_freq only how often the state is written)
+RESUME_FREE = ('print_freq', 'gpu_ids', 'num_threads', 'checkpoints_dir', 'continue_train', 'save_epoch_freq')
+
+
+def write_atomic(obj, path):
+    """torch.save(obj, path) through a temporary file in the same directory and os.replace: a write that fails or is killed
+    part way leaves the previous file as it was"""
+    fd, tmp = tempfile.mkstemp(prefix='.' + os.path.basename(path) + '.', suffix='.tmp', dir=os.path.dirname(path) or '.')
+    try:
+        with os.fdopen(fd, 'wb') as f:
+            torch.save(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def _host_rng():
+    return {'python': random.getstate(), 'torch': torch.get_rng_state(),
+            'cuda': torch.cuda.get_rng_state() if torch.cuda.is_available() else None}
+
+
+def _set_host_rng(state):
+    random.setstate(state['python'])
+    torch.set_rng_state(state['torch'])
+    if state['cuda'] is not None:
+        torch.cuda.set_rng_state(state['cuda'])
+
+
+def save_training_state(path, model, start_opt, epoch, total_iters, best):
+    """--continue_train: the run as it stands at the top of epoch + 1, written by rank 0.  Under data parallelism every rank's
+    host RNG streams and rank-local model state (the image pools: each rank pools its own fakes) are gathered into it."""
+    model._quiesce()
+    mine = {'rng': _host_rng(), 'local': model.rank_local_state() if gdist.is_dist() else None}
+    if gdist.is_dist():
+        ranks = [None] * gdist.world_size()
+        torch.distributed.all_gather_object(ranks, mine)
+    else:
+        ranks = [mine]
+    if gdist.rank() != 0:
+        return None
+    t0 = time.time()
+    write_atomic({'model': model.training_state(), 'epoch': epoch, 'total_iters': total_iters, 'best': (best.value, best.epoch),
+                  'ranks': ranks, 'opt': start_opt}, path)
+    return time.time() - t0
+
+
+def check_resume_options(stored, opt):
+    """GccError naming every option in which the stored run and this one differ (RESUME_FREE aside)"""
+    now = vars(opt)
+    diff = sorted(k for k in set(stored) | set(now) if k not in RESUME_FREE and stored.get(k, '<unset>') != now.get(k, '<unset>'))
+    if diff:
+        raise GccError('--continue_train: the saved training state was written by a run with other options: ' +
+                       ', '.join('%s (saved %r, now %r)' % (k, stored.get(k, '<unset>'), now.get(k, '<unset>')) for k in diff))
+
+
 def main(argv=None, datasets=None, evaluate=None):
     gdist.init_from_env()
     opt = options.parse(argv)
     opt.isTrain = True
+    start_opt = copy.deepcopy(vars(opt))                   # update_learning_rate moves opt.ema_beta
     exp = os.path.join(opt.checkpoints_dir, opt.name)
     util.mkdirs(exp)
     logger = util.get_logger(os.path.join(exp, 'logger.log' if gdist.rank() == 0 else 'logger.rank%d.log' % gdist.rank()))
@@ -127,13 +192,31 @@ def main(argv=None, datasets=None, evaluate=None):
     logger.info('The number of training images = %d' % len(train_set))
     total_iters = 0
     best, last_scores = BestRecord(opt), None
+    first_epoch = opt.epoch_count
+    state_path = os.path.join(exp, STATE_FILE) if opt.continue_train else None
+    if state_path is not None and os.path.exists(state_path):
+        state = torch.load(state_path, map_location='cpu', weights_only=False)
+        check_resume_options(state['opt'], opt)
+        if len(state['ranks']) != gdist.world_size():
+            raise GccError('--continue_train: the saved training state holds %d ranks, this run has %d'
+                           % (len(state['ranks']), gdist.world_size()))
+        mine = state['ranks'][gdist.rank()]
+        model.load_training_state(state['model'])
+        if mine['local'] is not None:
+            model.load_rank_local_state(mine['local'])
+        total_iters = state['total_iters']
+        best.value, best.epoch = state['best']
+        first_epoch = state['epoch'] + 1
+        _set_host_rng(mine['rng'])                       # last: building the model and the loaders drew from them
+        logger.info('resuming from epoch %d (iters %d) of %s' % (first_epoch, total_iters, state_path))
+        del state
     # GCC_REPLAY=1: the iteration is recorded once per epoch and re-issued from native code (gcc_amd.replay: the launch-bound
     # models -- CycleGAN at batch 1, SAGAN, SRGAN -- train at the GPU's pace instead of the Python host's); same results
     replay = None
     if os.environ.get('GCC_REPLAY', '0') == '1':
         from .replay import IterationReplay
         replay = IterationReplay(model, opt, enabled=True)
-    for epoch in range(opt.epoch_count, opt.n_epochs + opt.n_epochs_decay + 1):
+    for epoch in range(first_epoch, opt.n_epochs + opt.n_epochs_decay + 1):
         model.model_train()
         logger.info('\nEpoch:%d' % epoch)
         t_epoch = time.time()
@@ -169,6 +252,10 @@ def main(argv=None, datasets=None, evaluate=None):
         model.update_learning_rate(epoch)
         if replay is not None:
             replay.invalidate()          # learning rates (and the EMA beta) are launch arguments of the recording
+        if state_path is not None and epoch % opt.save_epoch_freq == 0:
+            took = save_training_state(state_path, model, start_opt, epoch, total_iters, best)
+            if took is not None:
+                logger.info('training state of epoch %d written to %s in %.1f s' % (epoch, state_path, took))
     if last_scores is not None:
         best.report(logger, last_scores)
     return model
