@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GCC_HIP_LIB') or os.path.join(_HERE, 'libgcc_hip.so')     # GCC_HIP_LIB: another build of the same ABI (A/B runs)
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH = 0, 1, 2, 3
-GCC_HIP_ABI = 604       # include/gcc_hip.h GCC_HIP_ABI: the generation of struct layouts / option ids these bindings were written for
+GCC_HIP_ABI = 605       # include/gcc_hip.h GCC_HIP_ABI: the generation of struct layouts / option ids these bindings were written for
 WGRAD_GROUP_MAX = 32     # include/gcc_hip.h GCC_WGRAD_GROUP_MAX
 CHANSUM_GROUP_MAX = 24   # include/gcc_hip.h GCC_CHANSUM_GROUP_MAX
 SPECTRAL_GROUP_MAX = 8    # include/gcc_hip.h GCC_SPECTRAL_GROUP_MAX
@@ -53,6 +53,22 @@ class epilogue_t(C.Structure):
     _fields_ = [('bias', C.c_void_p), ('act', C.c_int), ('slope', C.c_float), ('stats_partial', C.c_void_p),
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('bn', C.c_void_p),
                 ('y2', C.c_void_p), ('ldy2', C.c_int), ('y2off', C.c_int), ('y2_mode', C.c_int), ('y2_gate', C.c_void_p)]
+
+
+class eval_epilogue_t(C.Structure):
+    """include/gcc_hip.h gcc_eval_epilogue_t: the eval-mode epilogue of gcc_conv_fprop_eval"""
+    _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('slope', C.c_void_p), ('residual', C.c_void_p),
+                ('ld_residual', C.c_int), ('residual_off', C.c_int), ('act', C.c_int), ('pad_', C.c_int),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
+EVAL_ACT_NONE, EVAL_ACT_PRELU, EVAL_ACT_TANH = 0, 1, 2     # include/gcc_hip.h GCC_EVAL_ACT_*
+
+
+class bn_eval_item_t(C.Structure):
+    """include/gcc_hip.h gcc_bn_eval_item_t: one entry of gcc_bn_eval_coeffs_group"""
+    _fields_ = [('gamma', C.c_void_p), ('beta', C.c_void_p), ('running_mean', C.c_void_p), ('running_var', C.c_void_p),
+                ('bias', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p), ('C', C.c_int), ('eps', C.c_float)]
 
 
 class bnact_t(C.Structure):
@@ -165,6 +181,10 @@ PROTOTYPES = {
     'gcc_bn_eval_coeffs': (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P]),
     'gcc_bnact_fwd': (_I, [C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _Z, _P]),
     'gcc_conv_bn_act_workspace': (_Z, [C.POINTER(conv_t), _I]),
+    'gcc_conv_fprop_eval': (_I, [C.POINTER(conv_t), _P, _P, _P, C.POINTER(eval_epilogue_t), _P]),
+    'gcc_conv_eval_route': (_I, [C.POINTER(conv_t), _Z]),
+    'gcc_conv_eval_workspace': (_Z, [C.POINTER(conv_t)]),
+    'gcc_bn_eval_coeffs_group': (_I, [_P, _I, _P]),
     'gcc_conv_bn_act': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(bn_t), C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_bnact_bwd_workspace': (_Z, [_I, _Z]),
     'gcc_bnact_bwd': (_I, [C.POINTER(bnact_bwd_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I,

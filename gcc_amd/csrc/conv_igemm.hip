@@ -43,8 +43,9 @@ __device__ unsigned long long g_clock_probe[4096][8];
 // tiles of 32 / 64 columns on the uniform-tap path): two k-steps in flight.  The U-Net's mid layers run these tiles on 256-512
 // workgroups with 8-32 k-steps of 8-16 MFMAs per wave: a k-step was ~0.85 us of which ~0.06 us is matrix work -- the step waits
 // for the loads it issued one step earlier (profiles/r4f_unet_student_chain.txt: d3 27 us for 32 steps).
-template <int BP, int BC, bool UT, int NS = 2>
-__global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams p) {
+// EV: the eval-mode epilogue of gcc_conv_fprop_eval (IgemmParams.ev) instead of bias / activation / statistics.
+template <int BP, int BC, bool UT, int NS = 2, bool EV = false>
+__global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmArgs<EV> p) {
     using C = Cfg<BP, BC>;
     static_assert(NS == 2 || (UT && BP == 128 && (BC == 32 || BC == 64)), "deeper loops: uniform-tap 128 x {32, 64} tiles");
     constexpr int NT = C::NT;
@@ -490,7 +491,7 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
                 }
         }
     }
-    igemm_epilogue<C, BP, BC>(p, acc, smem, tid, lr, lq, wc, wp, m0, n0, M, Hg, Wg, ostr, py, px, mt, ks_idx, dstp);
+    igemm_epilogue<C, BP, BC, EV>(p, acc, smem, tid, lr, lq, wc, wp, m0, n0, M, Hg, Wg, ostr, py, px, mt, ks_idx, dstp);
 #ifdef GCC_CLOCK_PROBE
     {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -501,8 +502,9 @@ __global__ __launch_bounds__((BP / 32) * 64) void igemm_kernel(const IgemmParams
 }
 
 
-// finish a split-K launch: sum the K slices, bias + activation, bf16 NHWC store (same pixel map)
-__global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IgemmParams p) {
+// finish a split-K launch: sum the K slices, bias + activation (EV: the eval-mode epilogue), bf16 NHWC store (same pixel map)
+template <bool EV = false>
+__global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IgemmArgs<EV> p) {
     int py = 0, px = 0, Hg, Wg, ostr = 1;
     if (!p.dgrad) { Hg = p.Hd; Wg = p.Wd; }
     else {
@@ -536,11 +538,27 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IgemmParams 
             v[0] += a[0]; v[1] += a[1]; v[2] += a[2]; v[3] += a[3];
             v[4] += b[0]; v[5] += b[1]; v[6] += b[2]; v[7] += b[3];
         }
-        if (p.bias) {
+        if constexpr (EV) {
 #pragma unroll
-            for (int j = 0; j < 8; j++) v[j] += c0 + j < p.Cout ? p.bias[c0 + j] : 0.f;
+            for (int j = 0; j < 8; j++) {
+                float sc, sh;
+                eval_coeffs(p.ev, c0 + j, p.Cout, sc, sh);
+                v[j] = sc * v[j] + sh;
+            }
+            eval_act<8>(v, p.ev.act, eval_neg(p.ev));
+            if (p.ev.res) {      // forward launches only: pixel m of the output tensor
+                float rv[8];
+                unpack8(*(const i32x4*)(p.ev.res + (size_t)m * p.ev.ldr + p.ev.roff + c0), rv);
+#pragma unroll
+                for (int j = 0; j < 8; j++) v[j] += rv[j];
+            }
+        } else {
+            if (p.bias) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) v[j] += c0 + j < p.Cout ? p.bias[c0 + j] : 0.f;
+            }
+            apply_act8(v, v, p.act, p.slope);
         }
-        apply_act8(v, v, p.act, p.slope);
         if (c0 + 8 > p.Cout) {
 #pragma unroll
             for (int j = 0; j < 8; j++) if (c0 + j >= p.Cout) v[j] = 0.f;
@@ -728,7 +746,47 @@ int launch(const IgemmParams& p, int phases, int batch, hipStream_t st) {
         const size_t total = (size_t)p.rows_max * (ceil8(p.Cout) / 8);
         int blocks = (int)((total + 255) / 256);
         if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks, 1, phases), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(splitk_epilogue_kernel<false>, dim3(blocks, 1, phases), dim3(256), 0, st, p);
+        GCC_CHECK_LAUNCH();
+    }
+    return GCC_OK;
+}
+
+// the eval-mode epilogue's launches (gcc_conv_fprop_eval): 128-pixel tiles, forward, one phase; the loop forms of launch<128, BC>
+template <int BC>
+int launch_eval(const IgemmEvParams& p, hipStream_t st) {
+    using C = Cfg<128, BC>;
+    static std::once_flag attr_once;
+    std::call_once(attr_once, [] {
+        hipFuncSetAttribute((const void*)igemm_kernel<128, BC, true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+        hipFuncSetAttribute((const void*)igemm_kernel<128, BC, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
+    });
+    dim3 grid(p.mtiles_max * p.ntiles, p.ksplit > 1 ? p.ksplit : 1, 1);
+    const bool ut = (p.Ct % BK) == 0;
+    bool launched = false;
+    if constexpr (BC == 32 || BC == 64) {
+        if (ut) {
+            constexpr int LDS3 = 3 * (128 + BC) * BK * 2 > C::LDS_BYTES_EPI ? 3 * (128 + BC) * BK * 2 : C::LDS_BYTES_EPI;
+            static std::once_flag attr3;
+            std::call_once(attr3, [] {
+                hipFuncSetAttribute((const void*)igemm_kernel<128, BC, true, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS3);
+            });
+            hipLaunchKernelGGL((igemm_kernel<128, BC, true, 3, true>), grid, dim3(C::NT), LDS3, st, p);
+            launched = true;
+        }
+    }
+    if (!launched) {
+        if (ut)
+            hipLaunchKernelGGL((igemm_kernel<128, BC, true, 2, true>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
+        else
+            hipLaunchKernelGGL((igemm_kernel<128, BC, false, 2, true>), grid, dim3(C::NT), C::LDS_BYTES, st, p);
+    }
+    GCC_CHECK_LAUNCH();
+    if (p.ksplit > 1) {
+        const size_t total = (size_t)p.rows_max * (ceil8(p.Cout) / 8);
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 1024) blocks = 1024;
+        hipLaunchKernelGGL(splitk_epilogue_kernel<true>, dim3(blocks, 1, 1), dim3(256), 0, st, p);
         GCC_CHECK_LAUNCH();
     }
     return GCC_OK;
@@ -1971,4 +2029,96 @@ extern "C" int gcc_conv_dgrad(const gcc_conv_t* c, const void* dy, const void* w
                               const gcc_epilogue_t* ep, gcc_stream_t stream) {
     GCC_ENTER();
     return gcc_internal_igemm(c, 1, dy, wt, dx, ep, 1, 0, 0, 0, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Inference convolution with the eval-mode epilogue (include/gcc_hip.h gcc_conv_fprop_eval): the ring-walk route where its
+// geometry fits, igemm_kernel's 128-pixel tiles (split over K through the caller's workspace on small grids) everywhere else.
+int gcc_internal_ring3_eval(const gcc_conv_t* c, const void* src, const void* w, void* dst, const EvalEpi& ev, hipStream_t st);
+bool gcc_internal_ring3_eval_routed(const gcc_conv_t* c);
+
+namespace {
+// the eval route's tile and K split: the 128-pixel plan (the EV kernels exist for it alone)
+TilePlan eval_tile(const gcc_conv_t* c) {
+    gcc_conv_plan_t pl = c->plan;
+    pl.tile_families = 1;
+    return select_tile(pl, conv_max_rows(c, 0), c->Co, 1, conv_nk(c, 0), 1);
+}
+SplitPlan eval_split_plan(const gcc_conv_t* c, const TilePlan& tp) {
+    return plan_ksplit((long)tp.mtiles * tp.ntiles, conv_nk(c, 0), tp.max_slices);
+}
+size_t eval_split_bytes(const gcc_conv_t* c, const TilePlan& tp) {
+    const SplitPlan sp = eval_split_plan(c, tp);
+    return sp.ksplit > 1 ? (size_t)sp.ksplit * conv_max_rows(c, 0) * tp.ntiles * tp.BC * sizeof(float) : 0;
+}
+SplitPlan eval_split(const gcc_conv_t* c, const TilePlan& tp, const void* ws, size_t ws_bytes) {
+    const SplitPlan none = {1, conv_nk(c, 0)};
+    const size_t need = eval_split_bytes(c, tp);
+    if (!need || !ws || (((uintptr_t)ws) & 15) || need > ws_bytes) return none;
+    return eval_split_plan(c, tp);
+}
+
+int igemm_eval(const gcc_conv_t* c, const void* x, const void* w, void* y, const EvalEpi& ev, void* ws, size_t ws_bytes,
+               hipStream_t st) {
+    const int Ho = gcc_conv_out(c->H, c->KH, c->stride, c->pad), Wo = gcc_conv_out(c->W, c->KW, c->stride, c->pad);
+    IgemmEvParams p;
+    p.src = (const bf16_t*)x; p.wgt = (const bf16_t*)w; p.dst = (bf16_t*)y;
+    p.bias = nullptr; p.stats = nullptr; p.act = GCC_ACT_NONE; p.slope = 0.f;
+    p.N = c->N; p.KH = c->KH; p.KW = c->KW; p.stride = c->stride; p.pad = c->pad; p.dgrad = 0;
+    p.Hs = c->H; p.Ws = c->W; p.lds_ = c->ldx; p.soff = c->xoff;
+    p.Hd = Ho; p.Wd = Wo; p.ldd = c->ldy; p.doff = c->yoff;
+    p.Ct = ceil8(c->Ci); p.Cout = c->Co;
+    p.ldw = c->KH * c->KW * p.Ct;
+    const size_t max_rows = (size_t)c->N * Ho * Wo;
+    const size_t sb = (size_t)c->N * c->H * c->W * (size_t)p.lds_ * 2, wb = (size_t)p.Cout * p.ldw * 2;
+    const size_t db = max_rows * p.ldd * 2;
+    if (sb >= OOB || wb >= OOB || db >= (size_t)1 << 32 || max_rows >= (size_t)1 << 31) return GCC_ERR_UNSUPPORTED;
+    p.src_bytes = (uint32_t)sb; p.wgt_bytes = (uint32_t)wb;
+    p.src_bstride = p.wgt_bstride = p.dst_bstride = 0;
+    const TilePlan tp = eval_tile(c);
+    if (tp.BP != 128) return GCC_ERR_UNSUPPORTED;
+    p.ntiles = tp.ntiles; p.mtiles_max = tp.mtiles;
+    const SplitPlan sp = eval_split(c, tp, ws, ws_bytes);
+    p.ksplit = sp.ksplit; p.kper = sp.kper; p.partial = sp.ksplit > 1 ? (float*)ws : nullptr;
+    p.rows_max = (int)max_rows; p.Cpad = tp.ntiles * tp.BC; p.raw_partial = 0;
+    p.pair = 0; p.pair_slab = nullptr; p.pair_flags = nullptr;
+    p.debug = 0;
+    p.ev = ev;
+    switch (tp.BC) {
+        case 128: return launch_eval<128>(p, st);
+        case 64: return launch_eval<64>(p, st);
+        case 32: return launch_eval<32>(p, st);
+        default: return launch_eval<16>(p, st);
+    }
+}
+}  // namespace
+
+extern "C" size_t gcc_conv_eval_workspace(const gcc_conv_t* c) {
+    if (check_conv(c) || gcc_internal_ring3_eval_routed(c)) return 0;
+    return eval_split_bytes(c, eval_tile(c));
+}
+
+extern "C" int gcc_conv_eval_route(const gcc_conv_t* c, size_t workspace_bytes) {
+    if (check_conv(c)) return -1;
+    if (gcc_internal_ring3_eval_routed(c)) return 4;
+    const size_t need = eval_split_bytes(c, eval_tile(c));
+    return need && need <= workspace_bytes ? 5 : 0;
+}
+
+extern "C" int gcc_conv_fprop_eval(const gcc_conv_t* c, const void* x, const void* w, void* y, const gcc_eval_epilogue_t* ep,
+                                   gcc_stream_t stream) {
+    GCC_ENTER();
+    int rc = check_conv(c);
+    if (rc) return rc;
+    if (!x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    if (ep->act < GCC_EVAL_ACT_NONE || ep->act > GCC_EVAL_ACT_TANH || (ep->act == GCC_EVAL_ACT_PRELU && !ep->slope)) return GCC_ERR_BAD_ARG;
+    if (ep->residual && ((ep->ld_residual & 7) || (ep->residual_off & 7) || ep->ld_residual < ep->residual_off + ceil8(c->Co)))
+        return GCC_ERR_BAD_ARG;
+    EvalEpi ev;
+    ev.scale = ep->scale; ev.shift = ep->shift; ev.slope = ep->slope; ev.res = (const bf16_t*)ep->residual;
+    ev.ldr = ep->ld_residual; ev.roff = ep->residual_off; ev.act = ep->act;
+    const hipStream_t st = (hipStream_t)stream;
+    rc = gcc_internal_ring3_eval(c, x, w, y, ev, st);
+    if (rc != GCC_ERR_UNSUPPORTED) return rc;
+    return igemm_eval(c, x, w, y, ev, ep->workspace, ep->workspace_bytes, st);
 }

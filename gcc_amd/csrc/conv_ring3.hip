@@ -14,12 +14,14 @@
 // leave as ONE row per workgroup.  The data gradient is the same kernel over dY with the taps mirrored (flip) and the dgrad packing.
 #include <stdlib.h>
 #include <mutex>
+#include <type_traits>
 #include "common.hpp"
 #include "igemm_common.hpp"
 
 namespace {
 using gcc_igemm::OOB;
 using gcc_igemm::TailFin;
+using gcc_igemm::EvalEpi;
 
 constexpr int R3_D = 3;                 // rows in flight ahead of the row the products need
 constexpr int R3_RING = R3_D + 3;       // + the three rows being multiplied
@@ -37,6 +39,11 @@ struct Ring3Args {
     uint32_t src_bytes, dst_bytes;
     TailFin fin;            // tickets != NULL: the BatchNorm behind the conv is finalized by the last-arriving workgroups (igemm_common.hpp)
 };
+// the arguments of the EV instantiations: the eval-mode epilogue of gcc_conv_fprop_eval (bias / act / stats unused).  A type of its
+// own, so that the training instantiations keep their argument layout.
+struct Ring3EvArgs : Ring3Args {
+    EvalEpi ev;
+};
 
 // physical byte offset of logical 16-byte chunk `ch` of pixel row `r` (rows of RS = 64 or 128 bytes): 32-byte windows XOR-swizzled
 // with the row (conv_thinout.hip's image layout)
@@ -52,8 +59,9 @@ __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :
 
 // RS: bytes of a staged source pixel (64: <= 32 channels, 128: <= 64).  NBW: 16-pixel blocks per wave (strip = 32 NBW pixels).
 // DB: 32-channel halves of the destination (waves 0/1 -> wm: channels 16 DB wm ..; waves -> wn = wave >> 1: pixels 16 NBW wn ..)
-template <int RS, int NBW, int DB>
-__global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
+// EV: y = act(scale acc + shift) (+ residual) -- forward calls of gcc_conv_fprop_eval, no statistics
+template <int RS, int NBW, int DB, bool EV = false>
+__global__ __launch_bounds__(256, 2) void ring3_kernel(const typename std::conditional<EV, Ring3EvArgs, Ring3Args>::type a) {
     constexpr int SW = 32 * NBW;                                  // output pixels of a strip
     constexpr int PXR = 1024 / RS;                                // pixels per LDS-DMA piece
     constexpr int SWP = ((SW + 2 + PXR - 1) / PXR) * PXR;         // staged pixels: SW + 2, rounded up to whole pieces
@@ -98,7 +106,8 @@ __global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int c = (wm * MBW + mb) * 16 + 4 * g + r;
-            bv[mb][r] = (a.bias && c < a.Cd) ? a.bias[c] : 0.f;
+            if constexpr (EV) bv[mb][r] = 0.f;          // EV: coefficients read per row (the weights fill the registers)
+            else bv[mb][r] = (a.bias && c < a.Cd) ? a.bias[c] : 0.f;
         }
     }
     float st_s[8], st_q[8];
@@ -178,6 +187,36 @@ __global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
                 __builtin_amdgcn_sched_group_barrier(0x008, MBW, 0);
                 if (k + PF < NI) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
+            if constexpr (EV) {
+                // y = act(scale acc + shift) + residual, one rounding.  The residual is read here, after the products: the wait the
+                // compiler puts in front of its use (it does not see the LDS-DMA pieces) also waits for the row staged above, so a
+                // conv with a residual keeps one row of look-ahead less.  Channels >= Cd stay exact zeros.
+                const float neg = gcc_igemm::eval_neg(a.ev);
+#pragma unroll
+                for (int mb = 0; mb < MBW; mb++) {
+                    const int chunk = (wm * MBW + mb) * 2 + (g >> 1);
+                    const int c0 = (wm * MBW + mb) * 16 + 4 * g;
+#pragma unroll
+                    for (int nb = 0; nb < NBW; nb++) {
+                        const int px = (wn * NBW + nb) * 16 + i;
+                        float v[4];
+#pragma unroll
+                        for (int r = 0; r < 4; r++) {
+                            float sc, sh;
+                            gcc_igemm::eval_coeffs(a.ev, c0 + r, a.Cd, sc, sh);
+                            v[r] = sc * acc[mb][nb][r] + sh;
+                        }
+                        gcc_igemm::eval_act<4>(v, a.ev.act, neg);
+                        if (a.ev.res && xs + px < a.W && c0 < a.Cd) {
+                            float rv[4];
+                            gcc_igemm::unpack4(*(const i32x2*)(a.ev.res + ((size_t)(n * a.H + y) * a.W + xs + px) * a.ev.ldr + a.ev.roff + c0), rv);
+#pragma unroll
+                            for (int r = 0; r < 4; r++) v[r] += c0 + r < a.Cd ? rv[r] : 0.f;
+                        }
+                        *(i32x2*)(sO + px * R3_OROW + ((chunk ^ (px & 7)) << 4) + (g & 1) * 8) = i32x2{(int)pack2bf(v[0], v[1]), (int)pack2bf(v[2], v[3])};
+                    }
+                }
+            } else {
             // lane (i, g): pixel 16 (NBW wn + nb) + i, channels 16 (MBW wm + mb) + 4 g + r
 #pragma unroll
             for (int mb = 0; mb < MBW; mb++) {
@@ -191,6 +230,7 @@ __global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
                     *(i32x2*)(sO + px * R3_OROW + ((chunk ^ (px & 7)) << 4) + (g & 1) * 8) = i32x2{(int)pack2bf(v[0], v[1]), (int)pack2bf(v[2], v[3])};
                 }
             }
+            }
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < S; q++) {
@@ -198,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
                 const int px = e / NCH, chunk = e % NCH;
                 const bool ok = e < ITEMS && xs + px < a.W && chunk * 8 < a.Cd;
                 const i32x4 v = *(const i32x4*)(sO + (px & (SW - 1)) * R3_OROW + ((chunk ^ (px & 7)) << 4));
-                if (a.stats && ok) {
+                if (!EV && a.stats && ok) {
                     float f[8];
                     unpack8(v, f);
 #pragma unroll
@@ -210,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void ring3_kernel(const Ring3Args a) {
         }
         wait_vm<0>();
     }
-    if (a.stats) {
+    if (!EV && a.stats) {
         // one row of partial sums per workgroup: thread tid owns channels 8 (tid mod NCH) .. + 7 over its pixels
         __syncthreads();
         float* sR = (float*)smem;
@@ -292,11 +332,16 @@ bool gcc_internal_ring3_routed(const gcc_conv_t* c, int dgrad, const gcc_epilogu
     return ring3_plan(c, dgrad).ok && ring3_epilogue_ok(ep);
 }
 
-// route of gcc_conv_fprop / gcc_conv_dgrad (conv_igemm.hip): GCC_ERR_UNSUPPORTED = not this route's geometry / epilogue
-int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep, hipStream_t st) {
+namespace {
+// ev != NULL: the eval-mode epilogue (forward; ep ignored)
+int ring3_run(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep, const EvalEpi* ev,
+              hipStream_t st) {
     const Ring3Plan p = ring3_plan(c, dgrad);
-    if (!p.ok || !ring3_epilogue_ok(ep)) return GCC_ERR_UNSUPPORTED;
-    Ring3Args a;
+    if (ev) ep = nullptr;
+    if (!p.ok || !ring3_epilogue_ok(ep) || (ev && dgrad)) return GCC_ERR_UNSUPPORTED;
+    Ring3EvArgs ea;
+    ea.ev = ev ? *ev : EvalEpi{};
+    Ring3Args& a = ea;
     a.src = (const bf16_t*)src; a.w = (const bf16_t*)w; a.dst = (bf16_t*)dst;
     a.bias = ep ? ep->bias : nullptr; a.stats = ep ? ep->stats_partial : nullptr;
     a.N = c->N; a.H = c->H; a.W = c->W;
@@ -322,15 +367,20 @@ int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const vo
             tail = true;
         }
     }
-#define GCC_R3_LAUNCH(RS_, NBW_, DB_)                                                                                            \
+#define GCC_R3_LAUNCH1(RS_, NBW_, DB_, EV_, ARGS_)                                                                               \
     do {                                                                                                                          \
         static std::once_flag once;                                                                                               \
         static hipError_t attr_err = hipSuccess;                                                                                  \
         std::call_once(once, [] {                                                                                                 \
-            attr_err = hipFuncSetAttribute((const void*)ring3_kernel<RS_, NBW_, DB_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+            attr_err = hipFuncSetAttribute((const void*)ring3_kernel<RS_, NBW_, DB_, EV_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
         });                                                                                                                       \
         if (attr_err != hipSuccess) return GCC_ERR_LAUNCH;                                                                        \
-        hipLaunchKernelGGL((ring3_kernel<RS_, NBW_, DB_>), dim3(p.wgs), dim3(256), p.lds, st, a);                                 \
+        hipLaunchKernelGGL((ring3_kernel<RS_, NBW_, DB_, EV_>), dim3(p.wgs), dim3(256), p.lds, st, ARGS_);                        \
+    } while (0)
+#define GCC_R3_LAUNCH(RS_, NBW_, DB_)                                                                                            \
+    do {                                                                                                                          \
+        if (ev) GCC_R3_LAUNCH1(RS_, NBW_, DB_, true, ea);                                                                         \
+        else GCC_R3_LAUNCH1(RS_, NBW_, DB_, false, a);                                                                            \
     } while (0)
     const int key = (p.rs == 128 ? 4 : 0) + (p.nbw == 2 ? 2 : 0) + (p.db == 2 ? 1 : 0);
     switch (key) {
@@ -344,6 +394,7 @@ int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const vo
         default: GCC_R3_LAUNCH(64, 1, 1); break;
     }
 #undef GCC_R3_LAUNCH
+#undef GCC_R3_LAUNCH1
     GCC_CHECK_LAUNCH();
     if (bn && !tail) {
         return gcc_bn_finalize(a.stats, p.wgs, a.Cd, bn->count, bn->gamma, bn->beta, bn->eps, bn->momentum, bn->running_mean, bn->running_var,
@@ -351,3 +402,14 @@ int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const vo
     }
     return GCC_OK;
 }
+}  // namespace
+
+// route of gcc_conv_fprop / gcc_conv_dgrad (conv_igemm.hip): GCC_ERR_UNSUPPORTED = not this route's geometry / epilogue
+int gcc_internal_ring3(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep, hipStream_t st) {
+    return ring3_run(c, dgrad, src, w, dst, ep, nullptr, st);
+}
+// route of gcc_conv_fprop_eval (conv_igemm.hip)
+int gcc_internal_ring3_eval(const gcc_conv_t* c, const void* src, const void* w, void* dst, const EvalEpi& ev, hipStream_t st) {
+    return ring3_run(c, 0, src, w, dst, nullptr, &ev, st);
+}
+bool gcc_internal_ring3_eval_routed(const gcc_conv_t* c) { return ring3_plan(c, 0).ok != 0; }

@@ -1,6 +1,7 @@
 // Shared pieces of the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm_pp.hip): launch parameters, tile
 // constants and the epilogue (bias + activation + bf16 rounding, NHWC store through an LDS transpose, BatchNorm partial sums).
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 
 // named (not anonymous) namespace: hipcc fails to emit the host stub of a kernel template with internal
@@ -91,6 +92,36 @@ __device__ __forceinline__ void stats_tail(const TailFin& f, const float* stats,
     for (int i = tid; i <= G; i += NT) __hip_atomic_store((gu32*)f.tickets + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// eval-mode epilogue of gcc_conv_fprop_eval (include/gcc_hip.h): y = act(scale[c] acc + shift[c]) (+ res), fp32 until the one
+// bf16 rounding of the store.  Only the kernels instantiated with EV = true read it.
+struct EvalEpi {
+    const float* scale; const float* shift; const float* slope; const bf16_t* res;
+    int ldr, roff, act;
+};
+// the activation's negative-side factor: a launch constant, read once (PReLU: the device scalar)
+__device__ __forceinline__ float eval_neg(const EvalEpi& e) {
+    return e.act == GCC_EVAL_ACT_PRELU ? *e.slope : 1.f;
+}
+template <int N>
+__device__ __forceinline__ void eval_act(float* v, int act, float neg) {
+    if (act == GCC_EVAL_ACT_TANH) {
+#pragma unroll
+        for (int j = 0; j < N; j++) v[j] = tanhf(v[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) v[j] = v[j] > 0.f ? v[j] : v[j] * neg;
+    }
+}
+__device__ __forceinline__ void unpack4(const i32x2& v, float* f) {
+    f[0] = __uint_as_float((uint32_t)v[0] << 16); f[1] = __uint_as_float((uint32_t)v[0] & 0xffff0000u);
+    f[2] = __uint_as_float((uint32_t)v[1] << 16); f[3] = __uint_as_float((uint32_t)v[1] & 0xffff0000u);
+}
+// per-channel coefficients of channel c (channels >= C: exact zeros, so the pad channels stay zero)
+__device__ __forceinline__ void eval_coeffs(const EvalEpi& e, int c, int C, float& sc, float& sh) {
+    sc = c < C ? (e.scale ? e.scale[c] : 1.f) : 0.f;
+    sh = (c < C && e.shift) ? e.shift[c] : 0.f;
+}
+
 struct IgemmParams {
     const bf16_t* src;   // gather source (x for fprop, dy for dgrad)
     const bf16_t* wgt;   // packed weights, rows = output channels of this GEMM
@@ -126,6 +157,13 @@ struct IgemmParams {
     int debug = 0;               // diagnostic-build ablations (common.hpp: GCC_DIAG) (timing diagnostics only)
     TailFin fin = {};            // BatchNorm finalize by the last-arriving workgroups (tickets NULL: a separate gcc_bn_finalize)
 };
+// the parameters of the EV instantiations (gcc_conv_fprop_eval): a type of its own, so that every other kernel keeps its
+// argument layout
+struct IgemmEvParams : IgemmParams {
+    EvalEpi ev = {};
+};
+template <bool EV>
+using IgemmArgs = typename std::conditional<EV, IgemmEvParams, IgemmParams>::type;
 
 constexpr int BK = 64;   // k per step
 
@@ -170,8 +208,8 @@ struct Cfg {
 // epilogue shared by the igemm kernels: fp32 partial tiles (split-K / raw route) or bias + activation + bf16 rounding,
 // NHWC store through an LDS transpose, BatchNorm partial statistics.  C carries the tile constants (NT, CB, PB, TC, TP,
 // OSTRIDE); acc[i][j][r]: channel = wc*TC + i*16 + 4*lq + r ; pixel = wp*TP + j*16 + lr
-template <class C, int BP, int BC>
-__device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc)[C::CB][C::PB], char* smem, int tid, int lr,
+template <class C, int BP, int BC, bool EV = false>
+__device__ __forceinline__ void igemm_epilogue(const IgemmArgs<EV>& p, f32x4 (&acc)[C::CB][C::PB], char* smem, int tid, int lr,
                                                int lq, int wc, int wp, int m0, int n0, int M, int Hg, int Wg, int ostr, int py,
                                                int px, int mt, int ks_idx, bf16_t* dstp) {
     constexpr int NT = C::NT;
@@ -193,11 +231,17 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
         return;
     }
     char* sO = smem;
+    float ev_neg = 1.f;
+    if constexpr (EV) ev_neg = eval_neg(p.ev);
 #pragma unroll
     for (int i = 0; i < C::CB; i++) {
         const int cl = wc * C::TC + i * 16 + 4 * lq;
         float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (p.bias) {
+        float sv[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (EV) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) eval_coeffs(p.ev, n0 + cl + r, p.Cout, sv[r], bv[r]);
+        } else if (p.bias) {
 #pragma unroll
             for (int r = 0; r < 4; r++) bv[r] = (n0 + cl + r < p.Cout) ? p.bias[n0 + cl + r] : 0.f;
         }
@@ -208,9 +252,22 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmParams& p, f32x4 (&acc
             // of the tile, and a bias would otherwise leak into them)
             const bool live = !p.stats || (m0 + pl < M);
             float v[4];
+            if constexpr (EV) {
 #pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = acc[i][j][r] + bv[r];
-            apply_actN<4>(v, v, p.act, p.slope);
+                for (int r = 0; r < 4; r++) v[r] = sv[r] * acc[i][j][r] + bv[r];
+                eval_act<4>(v, p.ev.act, ev_neg);
+                // residual: pixel m of a forward launch is pixel m of the output tensor; channels >= Cout stay exact zeros
+                if (p.ev.res && m0 + pl < M && n0 + cl < p.Cout) {
+                    float rv[4];
+                    unpack4(*(const i32x2*)(p.ev.res + (size_t)(m0 + pl) * p.ev.ldr + p.ev.roff + n0 + cl), rv);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[r] += n0 + cl + r < p.Cout ? rv[r] : 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = acc[i][j][r] + bv[r];
+                apply_actN<4>(v, v, p.act, p.slope);
+            }
             if (!live) v[0] = v[1] = v[2] = v[3] = 0.f;
             i32x2 pk;
             pk[0] = (int)pack2bf(v[0], v[1]);

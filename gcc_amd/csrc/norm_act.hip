@@ -2035,6 +2035,32 @@ extern "C" int gcc_bn_eval_coeffs(const float* gamma, const float* beta, const f
     return GCC_OK;
 }
 
+// eval-mode coefficients of a group of BatchNorms / conv biases, one workgroup per item (include/gcc_hip.h)
+__global__ __launch_bounds__(256) void bn_eval_coeffs_group_kernel(const gcc_bn_eval_item_t* items) {
+    const gcc_bn_eval_item_t it = items[blockIdx.x];
+    for (int c = threadIdx.x; c < it.C; c += 256) {
+        const float bias = it.bias ? it.bias[c] : 0.f;
+        if (!it.running_var) {
+            it.scale[c] = 1.f;
+            it.shift[c] = bias;
+            continue;
+        }
+        const float r = 1.f / sqrtf(it.running_var[c] + it.eps);
+        const float g = it.gamma ? it.gamma[c] : 1.f, b = it.beta ? it.beta[c] : 0.f;
+        const float sc = g * r;
+        it.scale[c] = sc;
+        it.shift[c] = b + (bias - (it.running_mean ? it.running_mean[c] : 0.f)) * sc;
+    }
+}
+
+extern "C" int gcc_bn_eval_coeffs_group(const gcc_bn_eval_item_t* items, int n, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!items || n <= 0) return GCC_ERR_BAD_ARG;
+    hipLaunchKernelGGL(bn_eval_coeffs_group_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, items);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
 extern "C" int gcc_bnact_fwd(const gcc_bnact_t* p, const void* x, int ldx, int xoff, void* y, int ldy, int yoff,
                              void* y2, int ldy2, int y2off, int C, size_t pixels, gcc_stream_t stream) {
     GCC_ENTER();

@@ -1640,6 +1640,84 @@ class SRResNetEngine:
         self.last.forward(h, c.out, act=ACT_TANH)
         return c
 
+    # ---- inference: eval-mode BatchNorm folded into the conv epilogues (gcc_conv_fprop_eval) ------------------------------
+    # Separate from the training contexts above: its activations live in ONE grow-only slab sized by the largest N * H * W seen
+    # (two regions the layers alternate between), its coefficients in one table filled by one launch (eval_coeffs), its split-K
+    # scratch in a workspace slot of its own.  It reads the packed bf16 weights of the last repack() and nothing it writes is
+    # read by the training path.
+
+    def eval_coeffs(self):
+        """scale / shift of the 33 BatchNorms (conv bias folded in) and the biases of the first and subpixel convs from the
+        current parameters and running statistics: ONE launch.  Call once per evaluation, before infer()."""
+        if getattr(self, '_ev_table', None) is None:
+            bias = lambda conv: conv.bias.data if conv.bias is not None else None
+            entries = [(None, bias(self.first), self.first.rows)]
+            for b in self.blocks:
+                entries += [(b.bn1.bn, bias(b.conv1), b.conv1.rows), (b.bn2.bn, bias(b.conv2), b.conv2.rows)]
+            entries.append((self.mid_bn.bn, bias(self.mid), self.mid.rows))
+            entries += [(None, bias(conv), conv.rows) for conv, _ in self.sub]
+            self._ev_table = ops.BNEvalTable(entries, self.device)
+        self._ev_table.run()
+
+    def _infer_bufs(self, N, h, w):
+        """views of the inference slab for an N x h x w input: region A holds the trunk (h0, two block outputs, the inner
+        activation), then the shuffled subpixel activations; region B the input, then the subpixel convs' outputs and the image"""
+        P, C8 = N * h * w, ops.ceil8(self.C)
+        ci8 = max([ops.ceil8(b.conv1.rows) for b in self.blocks] or [C8])
+        S8 = ops.ceil8(4 * self.C)
+        size_a = max(3 * C8 + ci8, 16 * C8) * P
+        size_b = max(8, 4 * S8, 16 * 8) * P
+        if getattr(self, '_ev_slab', None) is None or self._ev_slab.numel() < size_a + size_b:
+            self._ev_slab = None
+            self._ev_slab = torch.zeros(size_a + size_b, dtype=torch.bfloat16, device=self.device)
+        slab = self._ev_slab
+
+        def view(off, Cc, ld, s=1):
+            n = N * h * s * w * s * ld
+            return slab[off:off + n].view(N, h * s, w * s, ld).permute(0, 3, 1, 2)[:, :Cc]
+        B = size_a
+        v = type('SRInferBufs', (), {})()
+        v.h0, v.h = view(0, self.C, C8), [view(C8 * P, self.C, C8), view(2 * C8 * P, self.C, C8)]
+        v.a1 = [view(3 * C8 * P, b.conv1.rows, ops.ceil8(b.conv1.rows)) for b in self.blocks]
+        v.s_act = [view(0, self.C, C8, 2), view(0, self.C, C8, 4)]
+        v.x_in = view(B, 3, 8)
+        v.s_raw = [view(B, 4 * self.C, S8), view(B, 4 * self.C, S8, 2)]
+        v.out = view(B, 3, 8, 4)
+        return v
+
+    def infer_input(self, N, h, w):
+        """the slab's input view (NHWC bf16, 3 channels): fill it, then infer(it)"""
+        return self._infer_bufs(N, h, w).x_in
+
+    def infer(self, x):
+        """eval-mode generator forward of an NHWC bf16 LR batch x [N, 3, h, w]: k9 conv + PReLU | blocks (conv+BN+PReLU,
+        conv+BN + x) | conv+BN + long skip | 2 x (conv -> PixelShuffle(2) -> PReLU) | k9 conv + tanh.  One launch per conv
+        (two per subpixel block).  Returns the NHWC bf16 image [N, 3, 4h, 4w], a view of the slab valid until the next call.
+        Needs eval_coeffs() of the current parameters."""
+        if getattr(self, '_ev_table', None) is None:
+            raise _lib.GccError('SRResNetEngine.infer: eval_coeffs() first')
+        N, _, h, w = x.shape
+        v = self._infer_bufs(N, h, w)
+        T, PRELU = self._ev_table, _lib.EVAL_ACT_PRELU
+        conv = lambda op, src, dst, i, **kw: ops.conv_fprop_eval(src, op.w, op.rows_k, op.k, op.stride, op.pad, dst,
+                                                                 shift=T.shift[i], **kw)
+        conv(self.first, x, v.h0, 0, act=PRELU, slope=self.first_slope.data)
+        h, nxt, i = v.h0, 0, 1
+        for b, a1 in zip(self.blocks, v.a1):
+            conv(b.conv1, h, a1, i, scale=T.scale[i], act=PRELU, slope=b.slope.data)
+            conv(b.conv2, a1, v.h[nxt], i + 1, scale=T.scale[i + 1], residual=h)
+            h, nxt, i = v.h[nxt], 1 - nxt, i + 2
+        conv(self.mid, h, v.h[nxt], i, scale=T.scale[i], residual=v.h0)
+        h, i = v.h[nxt], i + 1
+        for j, (op, slope) in enumerate(self.sub):
+            conv(op, h, v.s_raw[j], i + j)
+            ops.prelu_fwd(v.s_raw[j], slope.data, v.s_act[j], shuffle=2)
+            h = v.s_act[j]
+        last = self.last
+        ops.conv_fprop(h, last.w, last.rows_k, last.k, last.stride, last.pad, out=v.out,
+                       bias=last.bias.data if last.bias is not None else None, act=ACT_TANH, ws_slot=None)
+        return v.out
+
     def backward(self, c, g_feat=None, wgrad=True):
         """c.g_out holds dL/d(image); g_feat: optional gradients w.r.t. features(c)"""
         G = self._gbufs(c.N, c.H, c.W)

@@ -5,6 +5,7 @@ import torch
 
 from .fid_score import _compute_statistics_of_ims, calculate_frechet_distance
 from .mIoU_score import test
+from .sr_eval import test_srgan_psnr  # noqa: F401
 from ..utils import util
 
 

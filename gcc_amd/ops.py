@@ -560,12 +560,12 @@ class PackPlan:
               'gcc_pack_weights_multi')
 
 
-def _epilogue(bias, act, slope, stats, d=None, dgrad=0, device=None, bn=None):
+def _epilogue(bias, act, slope, stats, d=None, dgrad=0, device=None, bn=None, ws_slot='splitk'):
     wsp, wsb = None, 0
-    if d is not None:
+    if d is not None and ws_slot is not None:
         need = lib().gcc_conv_workspace(C.byref(d), dgrad)
         if need:
-            ws = workspace(need, device, 'splitk')
+            ws = workspace(need, device, ws_slot)
             wsp, wsb = ws.data_ptr(), ws.numel()
     return _lib.epilogue_t(bias.data_ptr() if bias is not None else None, act, slope,
                            stats.data_ptr() if stats is not None else None, wsp, wsb,
@@ -577,8 +577,10 @@ CONV_Y2 = True      # False (tests' reference): always the separate gcc_bnact_fw
 
 
 def conv_fprop(x, w, Co, k, stride, pad, out=None, bias=None, act=ACT_NONE, slope=0.2, want_stats=False, bn=None,
-               y2=None, y2_mode=0, y2_gate=None):
+               y2=None, y2_mode=0, y2_gate=None, ws_slot='splitk'):
     """bn: a gcc_bn_t (bn_desc) -- the BatchNorm behind this conv is finalized inside the call (needs want_stats).
+    ws_slot: the grow-only workspace slot of the split-K scratch; None: no split (the inference path: no workspace of its own
+    grows per image size).
     y2: a second output f(out) -- Y2_RELU: relu(out); Y2_GATE: out * y2_gate[c] -- written by the conv launch itself where the
     library can (the thin image-layer route), by a gcc_bnact_fwd launch behind it otherwise."""
     xp, N, Ci, H, W, ldx = geom(x)
@@ -591,7 +593,7 @@ def conv_fprop(x, w, Co, k, stride, pad, out=None, bias=None, act=ACT_NONE, slop
     if want_stats:
         tiles = lib().gcc_conv_stat_tiles(C.byref(d), 0)
         stats = torch.empty((tiles, 2, Co), dtype=torch.float32, device=x.device)
-    ep = _epilogue(bias, act, slope, stats, d, 0, x.device, bn)
+    ep = _epilogue(bias, act, slope, stats, d, 0, x.device, bn, ws_slot)
     y2_after = False
     if y2 is not None:
         y2p, _, _, _, _, ldy2 = geom(y2)
@@ -610,6 +612,26 @@ def conv_fprop(x, w, Co, k, stride, pad, out=None, bias=None, act=ACT_NONE, slop
         PROFILE.end(_ROUTE_KIND[lib().gcc_conv_route(C.byref(d), 0, C.byref(ep))], 2.0 * N * Ho * Wo * Co * k * k * Ci, e0,
                     shape=('fprop', N, Ho, Wo, Ci, Co, k, stride))
     return (out, stats) if want_stats else out
+
+
+def conv_fprop_eval(x, w, Co, k, stride, pad, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slope=None, residual=None,
+                    slot='eval'):
+    """inference conv (gcc_conv_fprop_eval): out = act(scale[c] conv(x, w) + shift[c]) (+ residual), one bf16 rounding, no
+    statistics.  slope: the PReLU slope as a DEVICE tensor (never read on the host).  Split-K scratch comes from the grow-only
+    workspace `slot` (not the training path's)."""
+    xp, N, Ci, H, W, ldx = geom(x)
+    yp, _, _, _, _, ldy = geom(out)
+    d = conv_desc(N, H, W, Ci, Co, k, stride, pad, ldx, ldy)
+    ep = _lib.eval_epilogue_t(_p(scale), _p(shift), _p(slope), None, 0, 0, act, 0, None, 0)
+    if residual is not None:
+        rp, _, _, _, _, ldr = geom(residual)
+        ep.residual, ep.ld_residual = rp, ldr
+    need = lib().gcc_conv_eval_workspace(C.byref(d))
+    if need:
+        ws = workspace(need, x.device, slot)
+        ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib().gcc_conv_fprop_eval(C.byref(d), xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_fprop_eval')
+    return out
 
 
 def conv_dgrad(dy, wt, Ci, H, W, k, stride, pad, out=None, bias=None, act=ACT_NONE, slope=0.2, want_stats=False, bn=None):
@@ -835,6 +857,40 @@ def bn_eval_coeffs(gamma, beta, running_mean, running_var, st, eps=1e-5):
 
 def _p(t):
     return t.data_ptr() if t is not None else None
+
+
+class BNEvalTable:
+    """eval-mode scale / shift of a list of (BatchNorm2d or None, conv bias or None, channels) entries in ONE launch
+    (gcc_bn_eval_coeffs_group).  The device item table is built once and again only when a parameter moved."""
+
+    def __init__(self, entries, device):
+        self.entries = list(entries)
+        self.C = [c for _, _, c in self.entries]
+        self.table = torch.zeros((2, sum(self.C)), dtype=torch.float32, device=device)
+        offs = [0]
+        for c in self.C:
+            offs.append(offs[-1] + c)
+        self.scale = [self.table[0, offs[i]:offs[i + 1]] for i in range(len(self.C))]
+        self.shift = [self.table[1, offs[i]:offs[i + 1]] for i in range(len(self.C))]
+        self.device, self._ptrs, self._items = device, None, None
+
+    def _pointers(self):
+        out = []
+        for bn, bias, _ in self.entries:
+            out.append((_p(bn.weight) if bn is not None else None, _p(bn.bias) if bn is not None else None,
+                        _p(bn.running_mean) if bn is not None else None, _p(bn.running_var) if bn is not None else None,
+                        _p(bias), float(bn.eps) if bn is not None else 0.0))
+        return out
+
+    def run(self):
+        ptrs = self._pointers()
+        if ptrs != self._ptrs:
+            items = (_lib.bn_eval_item_t * len(ptrs))()
+            for i, (g, b, rm, rv, bias, eps) in enumerate(ptrs):
+                items[i] = _lib.bn_eval_item_t(g, b, rm, rv, bias, self.scale[i].data_ptr(), self.shift[i].data_ptr(), self.C[i], eps)
+            self._items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
+            self._ptrs = ptrs
+        check(lib().gcc_bn_eval_coeffs_group(self._items.data_ptr(), len(ptrs), stream()), 'gcc_bn_eval_coeffs_group')
 
 
 def reflect_pad(src, dst, pad, backward=False):

@@ -110,6 +110,19 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
     return [v for v, _ in scores]
 
 
+def builtin_evaluator(opt, logger):
+    """the evaluation a run gets without an explicit evaluate=: SRGAN's PSNR / SSIM on the reference's test sets found under
+    <dataroot>/test (train.py:37-56); None otherwise -- FID and mIoU need evaluator networks the caller provides"""
+    if opt.model != 'srgan' or str(opt.dataroot).startswith('synthetic'):
+        return None
+    from .metric.sr_eval import available_sets, srgan_evaluator
+    sets = available_sets(opt)
+    if not sets:
+        return None
+    logger.info('SRGAN evaluation every %d epochs on: %s' % (opt.save_epoch_freq, ', '.join(sets)))
+    return srgan_evaluator(logger, sets)
+
+
 STATE_FILE = 'training_state.pth'
 # options that may differ between the run that wrote a training state and the run that resumes from it: they change neither the
 # arithmetic nor the data of an epoch (save_epoch_freq only how often the state is written)
@@ -190,6 +203,8 @@ def main(argv=None, datasets=None, evaluate=None):
         model.load_models(opt.initial_path, load_discriminator=False)
     train_set, val_set = datasets if datasets is not None else make_datasets(opt)
     logger.info('The number of training images = %d' % len(train_set))
+    if evaluate is None:
+        evaluate = builtin_evaluator(opt, logger)
     total_iters = 0
     best, last_scores = BestRecord(opt), None
     first_epoch = opt.epoch_count

@@ -44,7 +44,7 @@ enum { GCC_ACT_NONE = 0, GCC_ACT_LRELU = 1, GCC_ACT_RELU = 2, GCC_ACT_TANH = 3 }
 /* ABI generation of this header: bumped whenever a struct layout, an enum numbering or a prototype below changes.  gcc_version()
  * of the library a host loads must return exactly this number (gcc_amd/_lib.py refuses any other; an external host should check it
  * the same way): a stale .so reads gcc_conv_t.plan past its struct and sets the wrong option ids without any error. */
-#define GCC_HIP_ABI 604
+#define GCC_HIP_ABI 605
 
 const char* gcc_strerror(int code);
 int gcc_version(void); /* == GCC_HIP_ABI of the header the library was built from */
@@ -374,6 +374,50 @@ size_t gcc_conv_bn_act_workspace(const gcc_conv_t* c, int dgrad);
 int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, const void* w, void* y_raw, const gcc_bn_t* bn,
                     const gcc_bnact_t* act, void* y, int ldy, int yoff, void* y2, int ldy2, int y2off, void* ws,
                     size_t ws_bytes, gcc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Inference (eval-mode) convolution: the layers of SRGAN's generator (models/SRGAN.py:19-199) with BatchNorm in eval mode, i.e.
+ * a per-channel affine map, folded into the conv's epilogue:
+ *     y[p][c] = act(scale[c] * acc[p][c] + shift[c])  (+ residual[p][c])
+ * in fp32 registers with ONE bf16 rounding on store; no statistics.  act: GCC_EVAL_ACT_*; the PReLU slope is a DEVICE scalar
+ * (nn.PReLU() is learned: no host read).  Served by the ring-walk route (3 x 3 stride-1 layers between <= 64-channel tensors
+ * of >= 8192 pixels, conv_ring3.hip) and by igemm_kernel (128-pixel tiles, split-K through `workspace` for small grids with a
+ * long K loop) for every other forward geometry; forward only.  An internal route that cannot serve the epilogue declines
+ * it (GCC_ERR_UNSUPPORTED) before it launches anything: the epilogue is never applied in part.
+ * ------------------------------------------------------------------------------------------- */
+enum { GCC_EVAL_ACT_NONE = 0, GCC_EVAL_ACT_PRELU = 1, GCC_EVAL_ACT_TANH = 2 };
+typedef struct {
+    const float* scale;       /* [Co] or NULL (1) */
+    const float* shift;       /* [Co] or NULL (0): conv bias and BatchNorm shift, folded (gcc_bn_eval_coeffs_group) */
+    const float* slope;       /* DEVICE scalar, GCC_EVAL_ACT_PRELU only */
+    const void* residual;     /* NULL, or NHWC bf16 [N, Ho, Wo, ld_residual] added after the activation (channels < Co only:
+                                 the output's pad channels stay zero whatever the residual's hold) */
+    int ld_residual, residual_off;    /* multiples of 8 */
+    int act;                  /* GCC_EVAL_ACT_* */
+    int pad_;
+    void* workspace;          /* NULL, or gcc_conv_eval_workspace(c) bytes (16-byte aligned): split-K of small grids */
+    size_t workspace_bytes;
+} gcc_eval_epilogue_t;
+int gcc_conv_fprop_eval(const gcc_conv_t* c, const void* x, const void* w, void* y, const gcc_eval_epilogue_t* ep,
+                        gcc_stream_t stream);
+/* scratch gcc_conv_fprop_eval can use for a geometry (its own tile plan: 128-pixel tiles): split-K partial tiles of a small grid
+ * with a long K loop; 0 when the call never splits */
+size_t gcc_conv_eval_workspace(const gcc_conv_t* c);
+/* route gcc_conv_fprop_eval takes for a geometry given `workspace_bytes` of scratch: 4 the ring-walk kernel, 5 igemm_kernel
+ * split over K, 0 igemm_kernel un-split; < 0 for an invalid geometry.  Introspection for tests and profilers. */
+int gcc_conv_eval_route(const gcc_conv_t* c, size_t workspace_bytes);
+
+/* Eval-mode coefficients of many BatchNorms (and plain conv biases) in ONE launch: item i writes
+ *     scale[c] = gamma[c] / sqrt(running_var[c] + eps)          (1 when running_var is NULL)
+ *     shift[c] = beta[c] + (bias[c] - running_mean[c]) * scale[c]   (bias[c] when running_var is NULL)
+ * gamma / beta / bias NULL: 1 / 0 / 0.  `items` is a DEVICE array of n entries (built once while the pointers stay valid). */
+typedef struct {
+    const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+    const float* bias;
+    float* scale; float* shift;
+    int C; float eps;
+} gcc_bn_eval_item_t;
+int gcc_bn_eval_coeffs_group(const gcc_bn_eval_item_t* items, int n, gcc_stream_t stream);
 
 /* Backward of y = act(gate(bn(x))) [dropout] given up to two upstream gradients:
  *   g  = g1 * act'(y)  +  g2 * act2'(y)     (g2 from the skip/concat path, may be NULL)
