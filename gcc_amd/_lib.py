@@ -63,6 +63,14 @@ class eval_epilogue_t(C.Structure):
 
 
 EVAL_ACT_NONE, EVAL_ACT_PRELU, EVAL_ACT_TANH = 0, 1, 2     # include/gcc_hip.h GCC_EVAL_ACT_*
+EVAL_ACT_RELU, EVAL_ACT_LRELU = 3, 4                       # gcc_conv_eval_ex only
+
+
+class eval_ex_epilogue_t(C.Structure):
+    """include/gcc_hip.h gcc_eval_ex_epilogue_t: the epilogue of gcc_conv_eval_ex (forward / transposed, second output)"""
+    _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('y2', C.c_void_p), ('ldy2', C.c_int), ('y2off', C.c_int),
+                ('act', C.c_int), ('act2', C.c_int), ('slope', C.c_float), ('pad_', C.c_int),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
 class bn_eval_item_t(C.Structure):
@@ -185,6 +193,10 @@ PROTOTYPES = {
     'gcc_conv_eval_route': (_I, [C.POINTER(conv_t), _Z]),
     'gcc_conv_eval_workspace': (_Z, [C.POINTER(conv_t)]),
     'gcc_bn_eval_coeffs_group': (_I, [_P, _I, _P]),
+    'gcc_conv_eval_ex': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(eval_ex_epilogue_t), _P]),
+    'gcc_conv_eval_ex_workspace': (_Z, [C.POINTER(conv_t), _I]),
+    'gcc_conv_eval_ex_route': (_I, [C.POINTER(conv_t), _I, _Z]),
+    'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_conv_bn_act': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(bn_t), C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_bnact_bwd_workspace': (_Z, [_I, _Z]),
     'gcc_bnact_bwd': (_I, [C.POINTER(bnact_bwd_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I,

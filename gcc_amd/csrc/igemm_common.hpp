@@ -165,6 +165,37 @@ struct IgemmEvParams : IgemmParams {
 template <bool EV>
 using IgemmArgs = typename std::conditional<EV, IgemmEvParams, IgemmParams>::type;
 
+// eval-mode epilogue of gcc_conv_eval_ex (include/gcc_hip.h): z = scale[c] acc + shift[c]; y = act(z), y2 = act2(z) (y2 NULL: none)
+struct EvalExEpi {
+    const float* scale; const float* shift;
+    bf16_t* y2;
+    int ldy2, y2off, act, act2;
+    float slope;
+};
+// the activation of a GCC_EVAL_ACT_* id; `act` is a launch constant (uniform branch)
+template <int N>
+__device__ __forceinline__ void eval_ex_act(const float* z, float* v, int act, float slope) {
+    if (act == GCC_EVAL_ACT_TANH) {
+#pragma unroll
+        for (int j = 0; j < N; j++) v[j] = tanhf(z[j]);
+    } else {
+        const float neg = act == GCC_EVAL_ACT_LRELU ? slope : (act == GCC_EVAL_ACT_RELU ? 0.f : 1.f);
+#pragma unroll
+        for (int j = 0; j < N; j++) v[j] = z[j] > 0.f ? z[j] : z[j] * neg;
+    }
+}
+__device__ __forceinline__ void eval_ex_coeffs(const EvalExEpi& e, int c, int C, float& sc, float& sh) {
+    sc = c < C ? (e.scale ? e.scale[c] : 1.f) : 0.f;
+    sh = (c < C && e.shift) ? e.shift[c] : 0.f;
+}
+// the parameters of the gcc_conv_eval_ex instantiations (igemm_ex_kernel, splitk_eval_ex_kernel)
+struct IgemmExParams : IgemmParams {
+    EvalExEpi ex = {};
+};
+// epilogue kinds of the igemm kernel body: 0 training (bias / activation / statistics), 1 gcc_conv_fprop_eval, 2 gcc_conv_eval_ex
+template <int EPI>
+using IgemmEpiArgs = typename std::conditional<EPI == 2, IgemmExParams, IgemmArgs<EPI == 1>>::type;
+
 constexpr int BK = 64;   // k per step
 
 // conv_halo.hip: k4 s2 p1 convolutions with the tile's input neighbourhood resident in LDS
@@ -205,11 +236,69 @@ struct Cfg {
     static constexpr int LDS_BYTES = LDS_BYTES_LOOP > LDS_BYTES_EPI ? LDS_BYTES_LOOP : LDS_BYTES_EPI;
 };
 
+// the NHWC store of one bf16 tile staged in LDS (rows = pixels of the phase, 16-B chunks of BC channels) to dst at (ld, off)
+template <class C, int BP, int BC>
+__device__ __forceinline__ void igemm_store_tile(const char* sO, int tid, int m0, int n0, int M, int Hg, int Wg, int ostr, int py,
+                                                 int px, int N_Hd, int Wd, int Cout, bf16_t* dst, int ld, int off) {
+    constexpr int CPR = BC / 8;
+    constexpr int NCH = BP * CPR;
+    const int cend = ceil8(Cout);
+    for (int q = tid; q < NCH; q += C::NT) {
+        const int row = q / CPR;
+        const int cch = q - row * CPR;
+        const int m = m0 + row;
+        const int ch = n0 + cch * 8;
+        if (m < M && ch < cend) {
+            const int n = m / (Hg * Wg);
+            const int r = m - n * (Hg * Wg);
+            const int oy = r / Wg;
+            const int ox = r - oy * Wg;
+            const size_t o = ((size_t)(n * N_Hd + oy * ostr + py) * Wd + (ox * ostr + px)) * ld + off + ch;
+            *(i32x4*)(dst + o) = *(const i32x4*)(sO + row * C::OSTRIDE + cch * 16);
+        }
+    }
+}
+
+// the gcc_conv_eval_ex epilogue of an un-split tile: y = act(z) through the LDS transpose, then (y2) act2(z) through it again
+template <class C, int BP, int BC>
+__device__ __forceinline__ void igemm_epilogue_ex(const IgemmExParams& p, f32x4 (&acc)[C::CB][C::PB], char* smem, int tid, int lr,
+                                                  int lq, int wc, int wp, int m0, int n0, int M, int Hg, int Wg, int ostr, int py,
+                                                  int px, bf16_t* dstp) {
+    char* sO = smem;
+    const EvalExEpi& e = p.ex;
+    for (int out = 0; out < (e.y2 ? 2 : 1); out++) {
+        const int act = out ? e.act2 : e.act;
+        if (out) __syncthreads();          // every thread's stores of y have read the tile
+#pragma unroll
+        for (int i = 0; i < C::CB; i++) {
+            const int cl = wc * C::TC + i * 16 + 4 * lq;
+            float sv[4], bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) eval_ex_coeffs(e, n0 + cl + r, p.Cout, sv[r], bv[r]);
+#pragma unroll
+            for (int j = 0; j < C::PB; j++) {
+                const int pl = wp * C::TP + j * 16 + lr;
+                float z[4], v[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) z[r] = sv[r] * acc[i][j][r] + bv[r];
+                eval_ex_act<4>(z, v, act, e.slope);
+                i32x2 pk;
+                pk[0] = (int)pack2bf(v[0], v[1]);
+                pk[1] = (int)pack2bf(v[2], v[3]);
+                *(i32x2*)(sO + pl * C::OSTRIDE + cl * 2) = pk;
+            }
+        }
+        __syncthreads();
+        if (out == 0) igemm_store_tile<C, BP, BC>(sO, tid, m0, n0, M, Hg, Wg, ostr, py, px, p.Hd, p.Wd, p.Cout, dstp, p.ldd, p.doff);
+        else igemm_store_tile<C, BP, BC>(sO, tid, m0, n0, M, Hg, Wg, ostr, py, px, p.Hd, p.Wd, p.Cout, e.y2, e.ldy2, e.y2off);
+    }
+}
+
 // epilogue shared by the igemm kernels: fp32 partial tiles (split-K / raw route) or bias + activation + bf16 rounding,
 // NHWC store through an LDS transpose, BatchNorm partial statistics.  C carries the tile constants (NT, CB, PB, TC, TP,
 // OSTRIDE); acc[i][j][r]: channel = wc*TC + i*16 + 4*lq + r ; pixel = wp*TP + j*16 + lr
-template <class C, int BP, int BC, bool EV = false>
-__device__ __forceinline__ void igemm_epilogue(const IgemmArgs<EV>& p, f32x4 (&acc)[C::CB][C::PB], char* smem, int tid, int lr,
+template <class C, int BP, int BC, int EPI = 0>
+__device__ __forceinline__ void igemm_epilogue(const IgemmEpiArgs<EPI>& p, f32x4 (&acc)[C::CB][C::PB], char* smem, int tid, int lr,
                                                int lq, int wc, int wp, int m0, int n0, int M, int Hg, int Wg, int ostr, int py,
                                                int px, int mt, int ks_idx, bf16_t* dstp) {
     constexpr int NT = C::NT;
@@ -231,6 +320,11 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs<EV>& p, f32x4 (&a
         return;
     }
     char* sO = smem;
+    constexpr bool EV = EPI == 1;
+    if constexpr (EPI == 2) {
+        igemm_epilogue_ex<C, BP, BC>(p, acc, smem, tid, lr, lq, wc, wp, m0, n0, M, Hg, Wg, ostr, py, px, dstp);
+        return;
+    }
     float ev_neg = 1.f;
     if constexpr (EV) ev_neg = eval_neg(p.ev);
 #pragma unroll

@@ -2061,6 +2061,33 @@ extern "C" int gcc_bn_eval_coeffs_group(const gcc_bn_eval_item_t* items, int n, 
     return GCC_OK;
 }
 
+// util.tensor2im of an NHWC bf16 image: ((x + 1) * 0.5) * 255 in fp32 with explicitly rounded operations (no contraction into
+// an fma, no reassociation), truncated to uint8 -- the bytes numpy computes from the same fp32 values.  One thread per pixel.
+__global__ __launch_bounds__(256) void image_to_u8_kernel(const bf16_t* __restrict__ x, int ld, int off, size_t pixels,
+                                                          uint8_t* __restrict__ out) {
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (size_t)gridDim.x * 256) {
+        const bf16_t* px = x + p * ld + off;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float v = bf2f(px[k]);
+            float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.f), 0.5f), 255.f);
+            t = t > 0.f ? (t < 255.f ? t : 255.f) : 0.f;          // also maps NaN to 0
+            out[p * 3 + k] = (uint8_t)t;
+        }
+    }
+}
+
+extern "C" int gcc_image_to_u8(const void* x, int ld, int off, size_t pixels, void* out, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!x || !out || ld <= 0 || off < 0 || (ld & 7) || (off & 7) || ld < off + 8) return GCC_ERR_BAD_ARG;
+    if (!pixels) return GCC_OK;
+    const size_t blocks = (pixels + 255) / 256;
+    hipLaunchKernelGGL(image_to_u8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ld, off, pixels, (uint8_t*)out);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
 extern "C" int gcc_bnact_fwd(const gcc_bnact_t* p, const void* x, int ldx, int xoff, void* y, int ldy, int yoff,
                              void* y2, int ldy2, int y2off, int C, size_t pixels, gcc_stream_t stream) {
     GCC_ENTER();

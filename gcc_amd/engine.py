@@ -605,6 +605,121 @@ class UnetEngine:
         self.up[0].forward(c.rcat[1], c.out, act=ACT_TANH)
         return c
 
+    # ---- inference: eval-mode BatchNorm folded into the conv epilogues (gcc_conv_eval_ex) ------------------------------------
+    # Separate from the training contexts: the input, two regions the down path alternates between and the concat buffers live
+    # in ONE grow-only slab sized by the largest N * H * W seen; the coefficients in one table filled by one launch
+    # (eval_coeffs); split-K scratch in the 'eval' workspace slot.  It reads the packed bf16 weights of the last repack() and
+    # nothing it writes is read by the training path; self.ctx and self.seed are left alone.
+
+    def _ev_layers(self):
+        """(conv, BatchNorm or None) of the layers infer() runs through gcc_conv_eval_ex: down 1 .. D-1, up D-1 .. 1"""
+        D = self.D
+        return [(self.down[d], self.down_bn[d]) for d in range(1, D)] + [(self.up[d], self.up_bn[d]) for d in range(D - 1, 0, -1)]
+
+    def eval_coeffs(self):
+        """scale / shift of every BatchNorm of the generator (conv bias folded in) and the bias of the innermost conv from the
+        current parameters and running statistics: ONE launch.  Call after the parameters or running statistics changed,
+        before infer()."""
+        if getattr(self, '_ev_table', None) is None:
+            entries = []
+            for conv, bn in self._ev_layers():
+                C = conv.cols_k if conv.transposed else conv.rows_k
+                entries.append((bn.bn if bn is not None else None, conv.bias.data if conv.bias is not None else None, C))
+            self._ev_table = ops.BNEvalTable(entries, self.device)
+        self._ev_table.run()
+
+    def _infer_bufs(self, N, H, W):
+        """views of the inference slab for an N x H x W input: the input (its pad channels stay zero), two regions (the
+        down path's LeakyReLU outputs alternate between them; the innermost output and the image reuse them), the concat
+        buffers rcat[1 .. D-1] (skip | up path)"""
+        D, wd = self.D, self.width
+        hs = [(H >> (d + 1), W >> (d + 1)) for d in range(D)]
+        P = [N * h * w for h, w in hs]
+        size_x = N * H * W * 8
+        size_r = max([size_x] + [P[d] * ops.ceil8(wd[d]) for d in range(D)])
+        cat_off = [0] * D
+        total = size_x + 2 * size_r
+        for d in range(1, D):
+            cat_off[d] = total
+            total += P[d - 1] * self.catw[d]
+        if getattr(self, '_ev_slab', None) is None or self._ev_slab.numel() < total:
+            self._ev_slab = None
+            self._ev_slab = torch.zeros(total, dtype=torch.bfloat16, device=self.device)
+        slab = self._ev_slab
+
+        def view(off, Cc, ld, h, w):
+            return slab[off:off + N * h * w * ld].view(N, h, w, ld).permute(0, 3, 1, 2)[:, :Cc]
+        v = type('UnetInferBufs', (), {})()
+        v.hs = hs
+        v.x_in = view(0, 3, 8, H, W)
+        region = [size_x, size_x + size_r]
+        # lin[d + 1] (input of down conv d + 1) in region (d + 1) % 2; the innermost output in the other one than its input
+        v.lin = [None] + [view(region[(d + 1) % 2], wd[d], ops.ceil8(wd[d]), *hs[d]) for d in range(D - 1)]
+        v.e_act = view(region[D % 2], wd[D - 1], ops.ceil8(wd[D - 1]), *hs[D - 1])
+        v.rcat = [None] + [view(cat_off[d], self.catc[d], self.catw[d], *hs[d - 1]) for d in range(1, D)]
+        v.out = view(region[0], 3, 8, H, W)
+        return v
+
+    def infer_input(self, N, H, W):
+        """the slab's input view (NHWC bf16, 3 channels): fill it, then infer(it)"""
+        return self._infer_bufs(N, H, W).x_in
+
+    def _infer(self, x, count_only=False):
+        N, _, H, W = x.shape
+        D, wd, uw = self.D, self.width, self.uwidth
+        if H % (1 << D) or W % (1 << D):
+            raise _lib.GccError('UnetEngine.infer: H, W must be multiples of %d' % (1 << D))
+        v = self._infer_bufs(N, H, W)
+        T, E = self._ev_table, _lib
+        launches = 0
+        d0 = self.down[0]
+        if count_only:
+            launches += 1 if ops.conv_y2_in_launch(x, d0.w, d0.rows_k, d0.k, d0.stride, d0.pad, v.lin[1]) else 2
+        else:
+            ops.conv_fprop(x, d0.w, d0.rows_k, d0.k, d0.stride, d0.pad, out=v.lin[1],
+                           bias=d0.bias.data if d0.bias is not None else None, act=ACT_LRELU, slope=LRELU,
+                           y2=ops.cslice(v.rcat[1], 0, wd[0]), y2_mode=ops.Y2_RELU, ws_slot=None)
+
+        def ev(i, op, src, dst, act, y2=None):
+            bn = T.scale[i] if self._ev_layers()[i][1] is not None else None
+            return ops.conv_eval_ex(src, op.wt if op.transposed else op.w, op.cols_k if op.transposed else op.rows_k, op.k,
+                                    op.stride, op.pad, dst, transposed=op.transposed, scale=bn, shift=T.shift[i], act=act,
+                                    y2=y2, act2=E.EVAL_ACT_RELU, slope=LRELU, route_only=count_only)
+        i = 0
+        for d in range(1, D - 1):
+            r = ev(i, self.down[d], v.lin[d], v.lin[d + 1], E.EVAL_ACT_LRELU, ops.cslice(v.rcat[d + 1], 0, wd[d]))
+            launches, i = launches + (r if count_only else 0), i + 1
+        # innermost: conv + ReLU, or (a block around Identity) conv + BatchNorm + ReLU
+        r = ev(i, self.down[D - 1], v.lin[D - 1], v.e_act, E.EVAL_ACT_RELU)
+        launches, i = launches + (r if count_only else 0), i + 1
+        src = v.e_act
+        for d in range(D - 1, 0, -1):
+            r = ev(i, self.up[d], src, ops.cslice(v.rcat[d], self.uoff[d], uw[d]), E.EVAL_ACT_RELU)
+            launches, i = launches + (r if count_only else 0), i + 1
+            src = v.rcat[d]
+        if count_only:
+            return launches + 1
+        u0 = self.up[0]
+        ops.conv_dgrad(v.rcat[1], u0.wt, u0.cols_k, H, W, u0.k, u0.stride, u0.pad, out=v.out,
+                       bias=u0.bias.data if u0.bias is not None else None, act=ACT_TANH, slope=LRELU, ws_slot=None)
+        return v.out
+
+    def infer(self, x):
+        """eval-mode generator forward of an NHWC bf16 batch x [N, 3, H, W] (H, W multiples of 2^D): d0 conv + bias with its
+        LeakyReLU and ReLU copies | down convs + BatchNorm, LeakyReLU and a ReLU copy into the concat buffer | innermost conv
+        (+ BatchNorm) + ReLU | up convs + BatchNorm + ReLU into the concat buffers | u0 + bias + tanh.  One launch per conv
+        (two where K is split; infer_launches() says how many).  Returns the NHWC bf16 image [N, 3, H, W], a view of the slab
+        valid until the next call.  Needs eval_coeffs() of the current parameters and running statistics."""
+        if getattr(self, '_ev_table', None) is None:
+            raise _lib.GccError('UnetEngine.infer: eval_coeffs() first')
+        return self._infer(x)
+
+    def infer_launches(self, N, H, W):
+        """kernel launches infer() makes for an N x H x W batch, from the library's route introspection (launches nothing)"""
+        if getattr(self, '_ev_table', None) is None:
+            raise _lib.GccError('UnetEngine.infer_launches: eval_coeffs() first')
+        return self._infer(self.infer_input(N, H, W), count_only=True)
+
     # ---------------------------------------------------------------------------------------
     def backward(self, c, g_feat=None, wgrad=True):
         """c.g_out holds dL/d(out).  g_feat: optional list of 4 gradients w.r.t. features(c).

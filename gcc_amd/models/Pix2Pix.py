@@ -478,6 +478,7 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def refresh_weights(self):
         """re-derive the bf16 weight packings from the fp32 masters (after init / load / Adam)"""
+        self._g_generation = getattr(self, '_g_generation', 0) + 1
         self.G.repack()
         self.D.repack()
         self.D.mask_dirty = True
@@ -516,12 +517,48 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         N, _, H, W = self._A.shape
         c = self.G._ctx(N, H, W, 'main' if self.resnet else 0)
         ops.nhwc_copy(self._A, 0, c.x_in, 0, 3, cfill=8)
+        if self.netG.training:
+            self._g_generation = getattr(self, '_g_generation', 0) + 1     # running statistics move
         if self.resnet:
             self._gctx = self.G.forward(c, train=self.netG.training)
         else:
             self._gctx = self.G.forward(N, H, W, train=self.netG.training)
         self._fake = self._gctx.out
         self._fake_nchw = None
+
+    def infer_nhwc(self, real):
+        """the generator in eval mode on `real` (NCHW fp32: the generator's input, real_A; or a dataset batch dict, whose input
+        is picked by --direction as set_input does) through the fused inference path (UnetEngine.infer): an NHWC bf16
+        [N, 3, H, W] view valid until the next call.  Refreshes the eval-mode coefficients (one launch) when the parameters or
+        running statistics changed since the last call.  The resnet backbone (InstanceNorm) has no fused path: forward()."""
+        if isinstance(real, dict):
+            real = real['A' if self.opt.direction == 'AtoB' else 'B']
+        real = real.to(self.device, torch.float32).contiguous()
+        N, _, H, W = real.shape
+        if self.resnet:
+            was = self.netG.training
+            self.netG.eval()
+            A = ops.new_act(N, 3, H, W, self.device)
+            ops.nchw_to_nhwc(real, A)
+            prev, self._A = getattr(self, '_A', None), A
+            try:
+                self.forward()
+            finally:
+                self._A = prev
+                self.netG.train(was)
+            return self._fake
+        self.finish_G_update()
+        if getattr(self, '_ev_generation', None) != self._g_generation:
+            self.G.eval_coeffs()
+            self._ev_generation = self._g_generation
+        x = self.G.infer_input(N, H, W)
+        ops.nchw_to_nhwc(real, x, cfill=8)
+        return self.G.infer(x)
+
+    def infer(self, real):
+        """fake_B = G(real) in eval mode as NCHW fp32 (see infer_nhwc), whatever mode the model is in; forward() in eval mode
+        keeps its own route.  --backbone resnet: through forward() in eval mode (no fused path)."""
+        return ops.nhwc_to_nchw(self.infer_nhwc(real), 3)
 
     @property
     def fake_B(self):
@@ -844,6 +881,7 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def _apply_G_update(self):
         self.optimizer_G.step()          # L1_sparsity() (:554-563) is fused into the Adam kernel
+        self._g_generation = getattr(self, '_g_generation', 0) + 1
         if self.T and isinstance(self.G, engine.UnetEngine):     # generator + transform convs: one repack launch (on the iteration's critical chain)
             if getattr(self, '_g_pack', None) is None:
                 self._g_pack = ops.PackPlan(list(self.G.convs()) + list(self.T), self.device)

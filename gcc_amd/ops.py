@@ -614,6 +614,17 @@ def conv_fprop(x, w, Co, k, stride, pad, out=None, bias=None, act=ACT_NONE, slop
     return (out, stats) if want_stats else out
 
 
+def conv_y2_in_launch(x, w, Co, k, stride, pad, out):
+    """does conv_fprop(x, ..., out=out, y2=<ReLU copy>) write its second output from the conv launch itself (one launch)
+    rather than by a gcc_bnact_fwd launch behind it?"""
+    xp, N, Ci, H, W, ldx = geom(x)
+    yp, _, _, _, _, ldy = geom(out)
+    d = conv_desc(N, H, W, Ci, Co, k, stride, pad, ldx, ldy)
+    ep = _epilogue(None, ACT_LRELU, 0.2, None)
+    ep.y2, ep.ldy2, ep.y2off, ep.y2_mode = yp, ldy, 0, Y2_RELU
+    return bool(CONV_Y2 and lib().gcc_conv_y2_supported(C.byref(d), 0, C.byref(ep)))
+
+
 def conv_fprop_eval(x, w, Co, k, stride, pad, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slope=None, residual=None,
                     slot='eval'):
     """inference conv (gcc_conv_fprop_eval): out = act(scale[c] conv(x, w) + shift[c]) (+ residual), one bf16 rounding, no
@@ -634,8 +645,45 @@ def conv_fprop_eval(x, w, Co, k, stride, pad, out, scale=None, shift=None, act=_
     return out
 
 
-def conv_dgrad(dy, wt, Ci, H, W, k, stride, pad, out=None, bias=None, act=ACT_NONE, slope=0.2, want_stats=False, bn=None):
-    """dx [N,Ci,H,W] = conv_backward_data(dy) == ConvTranspose2d forward."""
+def conv_eval_ex(x, w, Co, k, stride, pad, out, transposed=False, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, y2=None,
+                 act2=_lib.EVAL_ACT_NONE, slope=0.2, slot='eval', route_only=False):
+    """inference conv, forward or transposed (gcc_conv_eval_ex): z = scale[c] conv(x, w) + shift[c]; out = act(z), y2 = act2(z),
+    one bf16 rounding each, no statistics.  Forward: w = W, Co output channels.  Transposed (ConvTranspose2d forward, what
+    conv_dgrad computes): w = Wt, Co = channels of `out`.  Split-K scratch from the grow-only workspace `slot`.
+    route_only: return the launches the call would make (1 or 2: split-K partials + fold) without launching."""
+    xp, N, Cx, Hx, Wx, ldx = geom(x)
+    yp, _, Cy, Hy, Wy, ldy = geom(out)
+    if not transposed:
+        d = conv_desc(N, Hx, Wx, Cx, Co, k, stride, pad, ldx, ldy)
+    else:
+        d = conv_desc(N, Hy, Wy, Co, Cx, k, stride, pad, ldy, ldx)
+    tr = 1 if transposed else 0
+    need = lib().gcc_conv_eval_ex_workspace(C.byref(d), tr)
+    ws = workspace(need, x.device, slot) if need else None
+    if route_only:
+        return 2 if lib().gcc_conv_eval_ex_route(C.byref(d), tr, ws.numel() if ws is not None else 0) == 5 else 1
+    ep = _lib.eval_ex_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, act2, slope, 0, None, 0)
+    if y2 is not None:
+        y2p, _, _, _, _, ldy2 = geom(y2)
+        ep.y2, ep.ldy2 = y2p, ldy2
+    if ws is not None:
+        ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib().gcc_conv_eval_ex(C.byref(d), tr, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_ex')
+    return out
+
+
+def image_to_u8(x, out=None):
+    """uint8 [N, H, W, 3] of an NHWC bf16 image (gcc_image_to_u8): the bytes of the reference's util.tensor2im"""
+    xp, N, Cx, H, W, ld = geom(x)
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    check(lib().gcc_image_to_u8(xp, ld, 0, N * H * W, out.data_ptr(), stream()), 'gcc_image_to_u8')
+    return out
+
+
+def conv_dgrad(dy, wt, Ci, H, W, k, stride, pad, out=None, bias=None, act=ACT_NONE, slope=0.2, want_stats=False, bn=None,
+               ws_slot='splitk'):
+    """dx [N,Ci,H,W] = conv_backward_data(dy) == ConvTranspose2d forward.  ws_slot: as conv_fprop's."""
     yp, N, Co, Ho, Wo, ldy = geom(dy)
     assert Ho == (H + 2 * pad - k) // stride + 1 and Wo == (W + 2 * pad - k) // stride + 1
     if out is None:
@@ -646,7 +694,7 @@ def conv_dgrad(dy, wt, Ci, H, W, k, stride, pad, out=None, bias=None, act=ACT_NO
     if want_stats:
         tiles = lib().gcc_conv_stat_tiles(C.byref(d), 1)
         stats = torch.empty((tiles, 2, Ci), dtype=torch.float32, device=dy.device)
-    ep = _epilogue(bias, act, slope, stats, d, 1, dy.device, bn)
+    ep = _epilogue(bias, act, slope, stats, d, 1, dy.device, bn, ws_slot)
     e0 = PROFILE.begin() if PROFILE.active else None
     check(lib().gcc_conv_dgrad(C.byref(d), yp, wt.data_ptr(), xp, C.byref(ep), stream()), 'gcc_conv_dgrad')
     if e0 is not None:

@@ -385,7 +385,8 @@ int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, const void* w
  * long K loop) for every other forward geometry; forward only.  An internal route that cannot serve the epilogue declines
  * it (GCC_ERR_UNSUPPORTED) before it launches anything: the epilogue is never applied in part.
  * ------------------------------------------------------------------------------------------- */
-enum { GCC_EVAL_ACT_NONE = 0, GCC_EVAL_ACT_PRELU = 1, GCC_EVAL_ACT_TANH = 2 };
+enum { GCC_EVAL_ACT_NONE = 0, GCC_EVAL_ACT_PRELU = 1, GCC_EVAL_ACT_TANH = 2,
+       GCC_EVAL_ACT_RELU = 3, GCC_EVAL_ACT_LRELU = 4 /* gcc_conv_eval_ex only: gcc_conv_fprop_eval rejects them */ };
 typedef struct {
     const float* scale;       /* [Co] or NULL (1) */
     const float* shift;       /* [Co] or NULL (0): conv bias and BatchNorm shift, folded (gcc_bn_eval_coeffs_group) */
@@ -418,6 +419,41 @@ typedef struct {
     int C; float eps;
 } gcc_bn_eval_item_t;
 int gcc_bn_eval_coeffs_group(const gcc_bn_eval_item_t* items, int n, gcc_stream_t stream);
+
+/* Inference convolution, forward or transposed, with up to two activated outputs: the U-Net's layers with eval-mode BatchNorm
+ * (models/Pix2Pix.py:40-118).  With z = scale[c] * acc[p][c] + shift[c] in fp32:
+ *     y [p][c] = act (z)    at (c->ldy, c->yoff)   -- transposed: at (c->ldx, c->xoff)
+ *     y2[p][c] = act2(z)    at (ldy2, y2off)       (y2 NULL: no second store)
+ * each rounded to bf16 once; no statistics.  act / act2: GCC_EVAL_ACT_NONE, _RELU, _LRELU (host `slope`) or _TANH.
+ * transposed = 0: Conv2d forward (x: c->ldx / xoff, weights W).  transposed = 1: ConvTranspose2d forward, i.e. what
+ * gcc_conv_dgrad computes from the same arguments (x plays dy: c->ldy / yoff; y plays dx: c->ldx / xoff; weights Wt), over the
+ * stride^2 output parity phases.  Served by igemm_kernel's 128-pixel tiles, split over K through `workspace` on small grids.
+ * Channels >= Co of y and y2 (up to the next multiple of 8) are written as zeros.  GCC_ERR_BAD_ARG: misaligned ldy2 / y2off, an
+ * unknown or PReLU act, y2 overlapping y's channels.  A geometry no route serves returns GCC_ERR_UNSUPPORTED before anything is
+ * launched. */
+typedef struct {
+    const float* scale;       /* [Co] or NULL (1) */
+    const float* shift;       /* [Co] or NULL (0): conv bias and BatchNorm shift, folded (gcc_bn_eval_coeffs_group) */
+    void* y2;                 /* NULL, or NHWC bf16 with the output's geometry: the second activated copy */
+    int ldy2, y2off;          /* multiples of 8 */
+    int act, act2;            /* GCC_EVAL_ACT_NONE / _RELU / _LRELU / _TANH */
+    float slope;              /* negative-side slope of GCC_EVAL_ACT_LRELU (both outputs) */
+    int pad_;
+    void* workspace;          /* NULL, or gcc_conv_eval_ex_workspace(c, transposed) bytes (16-byte aligned): split-K */
+    size_t workspace_bytes;
+} gcc_eval_ex_epilogue_t;
+int gcc_conv_eval_ex(const gcc_conv_t* c, int transposed, const void* x, const void* w, void* y, const gcc_eval_ex_epilogue_t* ep,
+                     gcc_stream_t stream);
+/* split-K scratch gcc_conv_eval_ex can use for a geometry; 0 when the call never splits */
+size_t gcc_conv_eval_ex_workspace(const gcc_conv_t* c, int transposed);
+/* route of gcc_conv_eval_ex given `workspace_bytes`: 5 igemm_kernel split over K (two launches: partial tiles, then the fold
+ * with the whole epilogue), 0 igemm_kernel un-split (one launch); < 0 for an invalid geometry */
+int gcc_conv_eval_ex_route(const gcc_conv_t* c, int transposed, size_t workspace_bytes);
+
+/* Image bytes of the reference's util.tensor2im: out[p][k] = (uint8)(((x + 1) * 0.5) * 255) of channel k < 3 of pixel p of an
+ * NHWC bf16 tensor (ld, off: multiples of 8), evaluated in fp32 in that order with no contraction, then truncated (values
+ * outside [-1, 1] are clamped to 0 / 255).  out: DEVICE uint8 [pixels][3]. */
+int gcc_image_to_u8(const void* x, int ld, int off, size_t pixels, void* out, gcc_stream_t stream);
 
 /* Backward of y = act(gate(bn(x))) [dropout] given up to two upstream gradients:
  *   g  = g1 * act'(y)  +  g2 * act2'(y)     (g2 from the skip/concat path, may be NULL)
