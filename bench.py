@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/s of the Pix2Pix GCC iteration at 256x256 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A step = one pass of the hot path over one synthetic batch of 16 paired 256x256 images per GPU:
@@ -12,8 +12,13 @@ teacher ngf 64 / ndf 128, hinge GAN loss, lambda_L1 100, content 50, gram 1e4, b
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
 The timed region is exactly K steps of the production schedule: `ms_per_step` = its wall time / K.  Weights and batches are
 seeded, so the same arguments give the same inputs on every run; --dump-outputs DIR writes what the last timed step computed.
+A plain run does only that: set up, warm up, time the K steps, dump, print the line.  --full adds the side measurements below
+(roofline, loss_check_step1, other_configs, cpu_baseline and, at N > 1, the all-reduce table) to the same line; each of the
+--no-* switches drops one of them again.
 
-roofline: the dominant kernel family is the implicit-GEMM convolution (igemm_kernel / igemm_halo_kernel: conv fprop /
+loss_check_step1 (--full): the first warm-up step's losses against tests/golden/bench_step1_losses.json (world 1).
+
+roofline (--full): the dominant kernel family is the implicit-GEMM convolution (igemm_kernel / igemm_halo_kernel: conv fprop /
 dgrad / ConvTranspose).  Every launch of it inside one step run just before the timed region is bracketed by HIP
 events on the launch stream (bracketing all steps costs ~6% throughput); achieved = sum of algorithmic FLOPs
 (2*M*Cout*taps*Cin, padding excluded) / sum of measured durations; peak = 2.5 PFLOP/s dense bf16 MFMA
@@ -22,10 +27,11 @@ gradients) folded onto one, so that a launch's duration is the kernel's own and 
 under the tile plan the production schedule uses (`roofline.frac`); one more such step AFTER the timed region runs the
 plan for launches that have the chip to themselves (pair split, full-chip weight-gradient splits:
 `roofline.frac_alone_plan`).  The steps of the timed region run the production schedule (profiles/: rocprofv3 summaries of `bench.py
---serialize-streams`, which agree with these durations, and of the default command).
-other_configs: after the timed region and outside `value`, one short run each of BASELINE.json configs 3-5 (CycleGAN,
+--serialize-streams`, which agree with these durations, and of the default command).  The bracketed step before the timed
+region runs without --full too, unreported (only --no-roofline drops it): the timed steps start from the weights it leaves.
+other_configs (--full): after the timed region and outside `value`, one short run each of BASELINE.json configs 3-5 (CycleGAN,
 SAGAN, SRGAN at their reference widths, synthetic batches, 10 warm-up + 30 timed iterations).
-cpu_baseline: the oracle (CPU restatement pinned to the reference) timed on this host's cores on a
+cpu_baseline (--full): the oracle (CPU restatement pinned to the reference) timed on this host's cores on a
 bounded sample (N=1, same architecture, 1 warm-up + 16 timed iterations, about 10 s), rank 0 at --gpus 1 only.
 """
 import argparse
@@ -412,9 +418,13 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=16, help='images per GPU per step')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also take the side measurements (roofline, loss_check_step1, '
+                         'other_configs, cpu_baseline, the all-reduce table at N > 1); off: only what the headline needs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
+    ap.add_argument('--no-roofline', action='store_true',
+                    help='skip the bracketed step before the timed region (and, with --full, the roofline block)')
+    ap.add_argument('--no-other-configs', action='store_true', help='with --full: skip other_configs')
     ap.add_argument('--serialize-streams', action='store_true',
                     help='run every step on one HIP stream (as the profiled steps do): for rocprofv3 runs whose per-kernel '
                          'average must be the kernel\'s own duration')
@@ -456,7 +466,8 @@ def main():
         if i == 0:
             torch.cuda.synchronize()
             log('first step done')
-            first_losses = dict(model.get_current_losses())
+            if args.full:
+                first_losses = dict(model.get_current_losses())
     torch.cuda.synchronize()
     log('warm-up done')
     from gcc_amd import engine
@@ -467,7 +478,8 @@ def main():
     gen_tags = None
     if n_prof:
         # profiled step, before the timed region (it runs on one stream and pays two events per launch, so it is not a step of
-        # the production schedule): a launch's duration is its own; the tile plan is the production schedule's
+        # the production schedule): a launch's duration is its own; the tile plan is the production schedule's.  Taken
+        # without --full too: the timed steps start from the weights it leaves
         torch.cuda.synchronize()
         serialize_streams(model, engine, True, 'production')
         ops.PROFILE.start(steps=1)          # HIP events bracket the MFMA-kernel launches of this step
@@ -497,7 +509,7 @@ def main():
     dt = time.perf_counter() - t0
     log('timed region: %.3f s (%.1f ms/step)' % (dt, 1000 * dt / args.steps))
     dumped = dump_outputs(model, args.dump_outputs, rank) if args.dump_outputs else None
-    if n_prof:
+    if n_prof and args.full:
         # after the timed region: one more single-stream step under the plan for launches that have the chip to themselves
         serialize_streams(model, engine, True, 'alone')
         one_step(model, train, val)                  # the split plan changes workspace sizes: one untimed step first
@@ -515,7 +527,7 @@ def main():
             roofs[0]['generator'] = generator_block(gen_tags, args.batch, spans)
         serialize_streams(model, engine, args.serialize_streams)
     roof = None
-    if roofs and roofs[0] is not None:
+    if args.full and roofs and roofs[0] is not None:
         roof = roofs[0]
         roof['plan'] = 'production tile plan (no pair split, half-chip weight-gradient splits), one stream'
         if len(roofs) > 1 and roofs[1] is not None:
@@ -542,7 +554,7 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     losses = model.get_current_losses()
-    comm = allreduce_table(model, device) if world > 1 else None
+    comm = allreduce_table(model, device) if world > 1 and args.full else None
     from gcc_amd import dist as gdist
     rccl_ranks = gdist.rccl_ranks() if world > 1 else 1          # collective: every rank calls it
     if rank != 0:
@@ -562,11 +574,13 @@ def main():
         'step_tflops': round(FLOP_PER_IMG * args.batch * args.steps / dt / 1e12, 2),
         'step_mfma_frac': round(FLOP_PER_IMG * args.batch * args.steps / dt / PEAK_BF16, 4),
         'loss_check': {k: round(v, 4) for k, v in losses.items()},
-        'loss_check_step1': loss_check_step1(first_losses, args.batch, world),
         'launches_per_step': launches_per_step,
         'library': {'so': os.path.basename(_lib.LIB_PATH), 'tuning_hooks_at_default': options_default, 'tuning_hooks': option_vector,
                     'tile_plan_pinned_by_env': dict(ops._plan_pinned), 'tile_plan_of_the_step': ops.current_plan()},
+        'full': args.full,
     }
+    if args.full:
+        out['loss_check_step1'] = loss_check_step1(first_losses, args.batch, world)
     if roof is not None:
         if 'conv_roofline' in roof:       # north_star: throughput as a fraction of the conv roofline
             roof['conv_roofline']['frac_of_step'] = round(roof['conv_roofline']['bound_ms'] / (1000.0 * dt / args.steps), 4)
@@ -576,11 +590,11 @@ def main():
         out['outputs_dumped'] = dumped
     if comm is not None:
         out['allreduce'] = comm
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
         n4 = cpu_baseline(iters=4, batch=4, budget=20.0)          # SURVEY 8(d) / BASELINE.md: N=1 and N=4
         out['cpu_baseline']['n4'] = {k: n4[k] for k in ('value', 'unit', 'sample')}
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         del model
         torch.cuda.empty_cache()
         out['other_configs'] = other_configs()

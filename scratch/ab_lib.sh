@@ -6,7 +6,7 @@ out=gpurun_out/$tag; mkdir -p $out
 for rep in 1 2; do
   for v in base new; do
     [ $v = base ] && export GCC_HIP_LIB=$PWD/$base || unset GCC_HIP_LIB
-    timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null > $out/${v}_r$rep.json
+    timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null > $out/${v}_r$rep.json
     python - <<PY
 import json
 d=json.load(open('$out/${v}_r$rep.json')); r=d['roofline']; g=r['generator']

@@ -14,9 +14,9 @@ tests)
   export GCC_TEST_REPORT=$PWD/$out/test_report.txt; rm -f $GCC_TEST_REPORT
   timeout 3000 python -m pytest tests -q -m gpu --durations=15 -p no:cacheprovider > $out/pytest.log 2>&1; echo "pytest exit $?" >> $out/pytest.log; tail -5 $out/pytest.log;;
 bench)
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench exit $?"; cat $out/bench.json | head -c 3000;;
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench exit $?"; cat $out/bench.json | head -c 3000;;
 prof)
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/prof_serialized -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --serialize-streams > $GRAFT_REPO_ROOT/$out/prof_serialized.log 2>&1)
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$out/prof_serialized -- python3 $OLDPWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --serialize-streams > $OLDPWD/$out/prof_serialized.log 2>&1)
   find $out/prof_serialized -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} $out/kernel_stats_serialized.csv
   find $out/prof_serialized -name '*kernel_trace.csv' -delete
   head -25 $out/kernel_stats_serialized.csv;;
@@ -30,7 +30,7 @@ profdefault)
   python scratch/trace_timeline.py $f 22 100 > $out/trace_timeline_default.txt 2>&1
   rm -f $f;;
 shapes)
-  GCC_PROFILE_SHAPES=1 timeout 600 python bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-other-configs > $out/shapes.json 2> $out/shapes.txt; grep -c . $out/shapes.txt;;
+  GCC_PROFILE_SHAPES=1 timeout 600 python bench.py --full --steps 3 --warmup 3 --no-cpu-baseline --no-other-configs > $out/shapes.json 2> $out/shapes.txt; grep -c . $out/shapes.txt;;
 graph)
   timeout 600 python scratch/probe_graph_pix2pix.py > $out/graph_probe.txt 2>&1; tail -8 $out/graph_probe.txt;;
 dp)

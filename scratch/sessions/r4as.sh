@@ -7,7 +7,7 @@ for v in 2 3; do
 done
 for v in 2 3; do
   echo "== GCC_IGEMM_HALO=$v"
-  env GCC_IGEMM_HALO=$v GCC_BENCH_OTHER=srgan_96_to_384,srgan timeout 600 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-roofline 2> $out/err.txt | python -c "
+  env GCC_IGEMM_HALO=$v GCC_BENCH_OTHER=srgan_96_to_384,srgan timeout 600 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-roofline 2> $out/err.txt | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 for k, v in d['other_configs'].items(): print('  ', k, 'eager', v['ms_per_step'], 'replay', v['replay'].get('ms_per_step'))"

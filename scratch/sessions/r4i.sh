@@ -10,7 +10,7 @@ for cfg in "-" "GCC_BN_BWD_TAIL=1"; do
   env $envs timeout 300 python scratch/unet_ab.py 2>/dev/null | grep "U-Net" | tee -a $out/unet_ab.txt
 done
 bash scratch/ab_quick.sh r4i "-" "GCC_BN_BWD_TAIL=1"
-timeout 900 python bench.py --no-other-configs --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench exit $?"
+timeout 900 python bench.py --full --no-other-configs --no-cpu-baseline > $out/bench.json 2> $out/bench.err; echo "bench exit $?"
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r4i/bench.json'))

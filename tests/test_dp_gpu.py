@@ -309,12 +309,14 @@ def test_replay_composes_with_data_parallel_native_route(bf16):
 @pytest.mark.timeout(1500)
 def test_bench_two_ranks_driver_command_line():
     """the driver's multi-GPU invocation of bench.py, rehearsed with two ranks on this box's one GPU (gloo in place of
-    RCCL, which refuses duplicate devices): barrier / max-over-ranks timing / rank-0 JSON line"""
+    RCCL, which refuses duplicate devices): barrier / max-over-ranks timing / rank-0 JSON line; --full, so that the
+    roofline block and the per-bucket all-reduce table run on both ranks too"""
     import json
     import subprocess
     env = dict(os.environ, GCC_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1']
+           '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
+           '--full']
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1400)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
