@@ -73,6 +73,18 @@ class eval_ex_epilogue_t(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
+DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
+DW_INORM_WORKSPACE_BYTES = 4096 + (3 << 20)                # include/gcc_hip.h GCC_DW_INORM_WORKSPACE_BYTES
+
+
+class dw_inorm_t(C.Structure):
+    """include/gcc_hip.h gcc_dw_inorm_t: depthwise 3x3 + InstanceNorm in one launch (gcc_dw_inorm_fwd)"""
+    _fields_ = [('mode', C.c_int), ('x', C.c_void_p), ('ldx', C.c_int), ('r', C.c_void_p), ('ldr', C.c_int),
+                ('u_out', C.c_void_p), ('ldu', C.c_int), ('w', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p),
+                ('ldy', C.c_int), ('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('eps', C.c_float),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+
+
 class bn_eval_item_t(C.Structure):
     """include/gcc_hip.h gcc_bn_eval_item_t: one entry of gcc_bn_eval_coeffs_group"""
     _fields_ = [('gamma', C.c_void_p), ('beta', C.c_void_p), ('running_mean', C.c_void_p), ('running_var', C.c_void_p),
@@ -197,6 +209,8 @@ PROTOTYPES = {
     'gcc_conv_eval_ex_workspace': (_Z, [C.POINTER(conv_t), _I]),
     'gcc_conv_eval_ex_route': (_I, [C.POINTER(conv_t), _I, _Z]),
     'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),
+    'gcc_dw_inorm_fwd': (_I, [C.POINTER(dw_inorm_t), _P]),
+    'gcc_dw_inorm_route': (_I, [C.POINTER(dw_inorm_t)]),
     'gcc_conv_bn_act': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(bn_t), C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_bnact_bwd_workspace': (_Z, [_I, _Z]),
     'gcc_bnact_bwd': (_I, [C.POINTER(bnact_bwd_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I,

@@ -1048,6 +1048,7 @@ constexpr unsigned GCC_DEVERR_INORM_SPIN = 0x1401u;
 // The statistics hand-off of the grid kernels (inorm_grid_kernel, bn_fold_grid_kernel): this workgroup's per-lane sums v[2][8]
 // -> the (image, channel group) domain's totals tot[V] (double), identical in every workgroup of the domain.
 #define IN_STAMP(k) do { if (GCC_DIAG(ga.clk != nullptr) && t == 0 && dom == 0) ga.clk[s * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+template <unsigned SPIN_ERR = GCC_DEVERR_INORM_SPIN>      // the code an expired spin stores (GCC_DEVERR_DWIN_SPIN: dw_inorm_kernel)
 __device__ __forceinline__ void grid_exchange(const InGridArgs& ga, float (&v)[2][8], double* smem_d, float* red, double* tot, int s,
                                               size_t dom, __attribute__((address_space(1))) unsigned int* cnt, unsigned epoch, int t,
                                               int lane, int wave, int ch) {
@@ -1123,7 +1124,7 @@ __device__ __forceinline__ void grid_exchange(const InGridArgs& ga, float (&v)[2
                         if ((pending & (1u << u)) && (unsigned)pr[u][1] == tag) pending &= ~(1u << u);
                     if (pending) __builtin_amdgcn_s_sleep(1);
                 }
-                if (pending && ga.err) __hip_atomic_store(ga.err, GCC_DEVERR_INORM_SPIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (pending && ga.err) __hip_atomic_store(ga.err, SPIN_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #pragma unroll
                 for (int u = 0; u < FB; u++)
                     if (qb + u * nq < g_hi) sum += (double)__uint_as_float((unsigned)pr[u][0]);
@@ -1161,7 +1162,7 @@ __device__ __forceinline__ void grid_exchange(const InGridArgs& ga, float (&v)[2
                         if ((unsigned)v4[1] == tag && (unsigned)v4[3] == tag) { got = true; break; }
                         __builtin_amdgcn_s_sleep(1);
                     }
-                    if (!got && ga.err) __hip_atomic_store(ga.err, GCC_DEVERR_INORM_SPIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (!got && ga.err) __hip_atomic_store(ga.err, SPIN_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     const i32x2 bits = {v4[0], v4[2]};
                     tsum += __builtin_bit_cast(double, bits);
                 }
@@ -1600,11 +1601,12 @@ static int grid_family_wgs() {
     }();
     return v;
 }
-static bool inorm_grid_plan(int C, int HW, int N, int px, size_t ws_bytes, InGridArgs* ga) {
+// chg_max: at most that many 16-byte chunks per channel group (dw_inorm_kernel: DWIN_CHG, its LDS tile holds a group's channels)
+static bool inorm_grid_plan(int C, int HW, int N, int px, size_t ws_bytes, InGridArgs* ga, int chg_max = 16) {
     const int CH = (C + 7) / 8;
     const int cus = grid_family_wgs();
     if (CH > 256 || N > 64) return false;
-    const int CHg = CH >= 16 ? 8 : CH;              // 64-channel groups (128-byte segments of a pixel) once an image has 128 channels
+    const int CHg = std::min(CH >= 16 ? 8 : CH, chg_max);   // 64-channel groups (128-byte segments of a pixel) once an image has 128 channels
     const int CG = (CH + CHg - 1) / CHg;
     if (N * CG > cus) return false;
     int CHP = 1, sh = 0;
@@ -1678,6 +1680,218 @@ bool inorm_launch(const InFusedArgs& a, int N, hipStream_t st, void* ws, size_t 
     if (big) GCC_IN_LAUNCH(1024); else GCC_IN_LAUNCH(256);
 #undef GCC_IN_LAUNCH
     return false;
+}
+
+
+// ---- depthwise 3x3 (ReflectionPad2d(1)) + InstanceNorm in ONE launch: the MobileResnet blocks' inference ----------------------
+// (models/Pix2Pix.py:132-197, models/CycleGAN.py:77-138; gcc_dw_inorm_fwd in include/gcc_hip.h.)  The plan, the residency rule
+// and the statistics hand-off are those of inorm_grid_kernel: S workgroups of an (image, 16-channel group) domain own `rows`
+// whole pixels each and meet at grid_exchange.  NORM_RELU / RESIDUAL take the InstanceNorm statistics of p (the raw output of the
+// 1x1 conv in front) first; the conv's own input u is then made from p (and r) and rounded to bf16 as the training route stores
+// it.  Each sweep walks the workgroup's pixels in LDS tiles: u of a tile and of the rows above and below it is made ONCE into LDS
+// (one or two 16-byte loads and one normalisation per pixel, RESIDUAL storing its own pixels' u), and every pixel reads its nine
+// taps from there.  The conv output d is never stored: the first sweep sums d and d^2 (second exchange), the last one makes the
+// tiles again, recomputes d and writes the normalised value.  The conv bias is not read: it cancels under the InstanceNorm.  The
+// two exchanges of a launch use two halves of the workspace (a workgroup may publish its second partials while a slower one still
+// polls the first ones) and two epochs of the domain (tags stay unique: the domain's counter advances by two per launch).
+constexpr unsigned GCC_DEVERR_DWIN_SPIN = 0x1402u;
+struct DwInArgs {
+    InGridArgs g1, g2;                  // same plan; partials / level-2 sums of the first and of the second exchange
+    const bf16_t* x; int ldx;           // PLAIN: u ; otherwise p
+    const bf16_t* r; int ldr;           // RESIDUAL: the previous block's input
+    bf16_t* u; int ldu;                 // RESIDUAL: u stored
+    bf16_t* y; int ldy;
+    const float* w;                     // [C][9] fp32
+    int H, W, C; float eps;
+    int tile;                           // pixels per LDS tile of a sweep (a multiple of the lanes per chunk)
+};
+
+__device__ __forceinline__ int dw_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
+
+// LDS: the exchange's words (as inorm_grid_kernel's) and, between exchanges, the u tile of a sweep share one region; the taps follow
+constexpr int DWIN_LDS_DOUBLES = 4800;                   // 38.4 KB: four workgroups per CU fit the 160 KB of LDS
+constexpr int DWIN_CHG = 2;                              // 16-byte chunks per channel group (16 channels): a pixel of u is 32 B in LDS
+constexpr int DWIN_TAP_DOUBLES = 9 * DWIN_CHG * 8 / 2;
+constexpr int DWIN_TILE_BYTES = (DWIN_LDS_DOUBLES - DWIN_TAP_DOUBLES) * 8;
+
+template <int MODE>      // GCC_DWIN_PLAIN / _NORM_RELU / _RESIDUAL
+__global__ __launch_bounds__(256, 4) void dw_inorm_kernel(const DwInArgs da) {   // <= 128 VGPRs: the residency the exchange counts on
+    __shared__ double smem_d[DWIN_LDS_DOUBLES];
+    float* red = (float*)smem_d;
+    double* tot = smem_d + 2048;
+    i32x4* ut = (i32x4*)smem_d;                          // u tile: [pixel - lo][CHg] 16-byte chunks (aliases the exchange's words)
+    float* wl = (float*)(smem_d + DWIN_LDS_DOUBLES - DWIN_TAP_DOUBLES);     // taps [9][CHg * 8]
+    const InGridArgs& ga = da.g1;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int ch = t & (ga.CHP - 1), pl = t >> ga.sh, PL = 256 >> ga.sh;
+    const int s = blockIdx.x, cg = blockIdx.y;
+    const size_t g = blockIdx.z;
+    const size_t dom = g * ga.CG + cg;
+    const bool live = ch < ga.CHg && cg * ga.CHg + ch < ga.CH;
+    const int CW = ga.CHg * 8, c0 = (cg * ga.CHg + ch) * 8;
+    const int H = da.H, W = da.W, HW = H * W;
+    const int p0 = s * ga.rows, p1 = min(p0 + ga.rows, HW);
+    const bf16_t* xg = da.x + g * (size_t)HW * da.ldx + c0;
+    const bf16_t* rg = MODE == GCC_DWIN_RESIDUAL ? da.r + g * (size_t)HW * da.ldr + c0 : nullptr;
+    for (int i = t; i < 9 * CW; i += 256) {
+        const int tap = i / CW, c = cg * CW + (i - tap * CW);
+        wl[i] = c < da.C ? da.w[(size_t)c * 9 + tap] : 0.f;
+    }
+    typedef __attribute__((address_space(1))) unsigned int gu32;
+    gu32* cnt = (gu32*)ga.cnt + dom * 4;
+    unsigned epoch = 0;
+    if (t == 0 && ga.S > 1) epoch = __hip_atomic_load(cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double inv_hw = 1.0 / (double)HW;
+    float v[2][8];
+    // (tot -> sc, sf): y = x sc + sf normalises, as inorm_grid_kernel's coefficients; zero for the pad channels
+    auto coeffs = [&](float* sc, float* sf) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            sc[j] = 0.f; sf[j] = 0.f;
+            if (live && c0 + j < da.C) {
+                const double m = tot[ch * 16 + j] * inv_hw;
+                double var = tot[ch * 16 + 8 + j] * inv_hw - m * m;
+                if (var < 0.0) var = 0.0;
+                const float r = (float)(1.0 / sqrt(var + (double)da.eps));
+                sc[j] = r; sf[j] = 0.f - (float)m * r;
+            }
+        }
+    };
+    float usc[8], usf[8];
+    if (MODE != GCC_DWIN_PLAIN) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[0][j] = v[1][j] = 0.f;
+        if (live) {
+            for (int p = p0 + pl; p < p1; p += PL) {
+                float f[8];
+                unpack8(*(const i32x4*)(xg + (size_t)p * da.ldx), f);
+#pragma unroll
+                for (int j = 0; j < 8; j++) { v[0][j] += f[j]; v[1][j] += f[j] * f[j]; }
+            }
+        }
+        grid_exchange<GCC_DEVERR_DWIN_SPIN>(ga, v, smem_d, red, tot, s, dom, cnt, epoch, t, lane, wave, ch);
+        coeffs(usc, usf);
+    }
+    __syncthreads();          // the taps; tot read before the first tile overwrites it
+    // u at pixel q of the image, rounded to bf16 once (the packed value is what RESIDUAL stores and the tile holds)
+    auto load_u = [&](int q) -> i32x4 {
+        const i32x4 rx = *(const i32x4*)(xg + (size_t)q * da.ldx);
+        if (MODE == GCC_DWIN_PLAIN) return rx;
+        float o[8];
+        unpack8(rx, o);
+#pragma unroll
+        for (int j = 0; j < 8; j++) o[j] = o[j] * usc[j] + usf[j];
+        if (MODE == GCC_DWIN_NORM_RELU) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) o[j] = fmaxf(o[j], 0.f);
+        }
+        if (MODE == GCC_DWIN_RESIDUAL) {
+            float rv[8];
+            unpack8(*(const i32x4*)(rg + (size_t)q * da.ldr), rv);
+#pragma unroll
+            for (int j = 0; j < 8; j++) o[j] = c0 + j < da.C ? o[j] + rv[j] : 0.f;
+        }
+        return pack8(o);
+    };
+    // One sweep over this workgroup's pixels in tiles of da.tile: u of the tile and its neighbour rows [lo, hi) is made once
+    // into LDS, then every pixel of the tile reads its nine taps from there (taps in the order of dwconv_kernel, no bias).
+    auto sweep = [&](bool last, const float* dsc, const float* dsf) {
+        for (int t0 = p0; t0 < p1; t0 += da.tile) {
+            const int t1 = min(t0 + da.tile, p1);
+            const int lo = max(t0 - W - 1, 0), hi = min(t1 + W + 1, HW);
+            if (live) {
+                for (int q = lo + pl; q < hi; q += PL) {
+                    const i32x4 pk = load_u(q);
+                    ut[(q - lo) * ga.CHg + ch] = pk;
+                    if (MODE == GCC_DWIN_RESIDUAL && !last && q >= t0 && q < t1)
+                        *(i32x4*)(da.u + (g * (size_t)HW + q) * da.ldu + c0) = pk;
+                }
+            }
+            __syncthreads();
+            if (live) {
+                for (int p = t0 + pl; p < t1; p += PL) {
+                    const int py = p / W, px = p - py * W;
+                    float d[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) d[j] = 0.f;
+#pragma unroll 1
+                    for (int ky = 0; ky < 3; ky++) {
+                        const int sy = dw_reflect(py + ky - 1, H);
+#pragma unroll
+                        for (int kx = 0; kx < 3; kx++) {
+                            const int q = sy * W + dw_reflect(px + kx - 1, W);
+                            float u[8];
+                            unpack8(ut[(q - lo) * ga.CHg + ch], u);
+                            const float* wt = wl + (ky * 3 + kx) * CW + ch * 8;
+#pragma unroll
+                            for (int j = 0; j < 8; j++) d[j] += wt[j] * u[j];
+                        }
+                    }
+                    if (!last) {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) { v[0][j] += d[j]; v[1][j] += d[j] * d[j]; }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) d[j] = d[j] * dsc[j] + dsf[j];
+                        *(i32x4*)(da.y + (g * (size_t)HW + p) * da.ldy + c0) = pack8(d);
+                    }
+                }
+            }
+            __syncthreads();      // the next tile (or the exchange) overwrites the tile
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[0][j] = v[1][j] = 0.f;
+    sweep(false, nullptr, nullptr);
+    grid_exchange<GCC_DEVERR_DWIN_SPIN>(da.g2, v, smem_d, red, tot, s, dom, cnt, MODE == GCC_DWIN_PLAIN ? epoch : epoch + 1u, t,
+                                        lane, wave, ch);
+    float sc[8], sf[8];
+    coeffs(sc, sf);
+    __syncthreads();          // tot read before the first tile overwrites it
+    sweep(true, sc, sf);      // d recomputed from the tiles, normalised, written
+}
+
+// the checks of gcc_dw_inorm_fwd / _route and the launch's arguments (nothing launched)
+int dw_inorm_prepare(const gcc_dw_inorm_t* d, DwInArgs* da) {
+    if (!d || d->mode < GCC_DWIN_PLAIN || d->mode > GCC_DWIN_RESIDUAL || !d->x || !d->w || !d->y || d->N <= 0 || d->H <= 0 ||
+        d->W <= 0 || d->C <= 0 || (d->ldx & 7) || (d->ldy & 7) || d->ldx < ((d->C + 7) & ~7) || d->ldy < ((d->C + 7) & ~7))
+        return GCC_ERR_BAD_ARG;
+    if (d->mode == GCC_DWIN_RESIDUAL && (!d->r || !d->u_out || (d->ldr & 7) || (d->ldu & 7) || d->ldr < ((d->C + 7) & ~7) ||
+                                         d->ldu < ((d->C + 7) & ~7)))
+        return GCC_ERR_BAD_ARG;
+    if (d->H < 2 || d->W < 2 || (size_t)d->H * d->W >= ((size_t)1 << 31)) return GCC_ERR_UNSUPPORTED;
+    const int HW = d->H * d->W;
+    constexpr int PX = 2;       // pixels per lane the plan aims at
+    InGridArgs probe;
+    if (!inorm_grid_plan(d->C, HW, d->N, PX, (size_t)1 << 60, &probe, DWIN_CHG)) return GCC_ERR_UNSUPPORTED;
+    // a sweep's LDS tile: `tile` pixels and the rows above and below them; planes too wide for one lane row of pixels are declined
+    const int PL = 256 / probe.CHP;
+    const int tile = ((DWIN_TILE_BYTES / (probe.CHg * 16) - 2 * d->W - 2) / PL) * PL;
+    if (tile < PL) return GCC_ERR_UNSUPPORTED;
+    // more than 8 pixels per lane and sweep (the plan's grid capped by the residency rule, e.g. 8 images of 256 channels): the
+    // launch no longer beats the two or three it replaces (profiles/r7_resnet_infer_ab.txt) -- declined, the caller keeps those
+    if (probe.rows > 8 * PL) return GCC_ERR_UNSUPPORTED;
+    if (!d->workspace || d->workspace_bytes < INORM_WS_HEADER + 16384) return GCC_ERR_WORKSPACE;
+    const size_t half = ((d->workspace_bytes - INORM_WS_HEADER) / 2) & ~(size_t)15;
+    if (!da) return inorm_grid_plan(d->C, HW, d->N, PX, INORM_WS_HEADER + half, &probe, DWIN_CHG) ? GCC_OK : GCC_ERR_WORKSPACE;
+    *da = DwInArgs{};
+    InGridArgs& ga = da->g1;
+    if (!inorm_grid_plan(d->C, HW, d->N, PX, INORM_WS_HEADER + half, &ga, DWIN_CHG)) return GCC_ERR_WORKSPACE;
+    da->tile = tile;
+    ga.cnt = (unsigned*)d->workspace;
+    ga.partial = (float*)((char*)d->workspace + INORM_WS_HEADER);
+    ga.level2 = (float*)((char*)d->workspace + INORM_WS_HEADER + (size_t)d->N * ga.CG * ga.S * ga.V * 8);
+    ga.clk = nullptr;
+    ga.err = gcc_device_error_word();
+    ga.spin_limit = 1 << 20;
+    ga.mute = 0;
+    da->g2 = ga;
+    da->g2.partial = (float*)((char*)ga.partial + half);
+    da->g2.level2 = (float*)((char*)ga.level2 + half);
+    da->x = (const bf16_t*)d->x; da->ldx = d->ldx; da->r = (const bf16_t*)d->r; da->ldr = d->ldr;
+    da->u = (bf16_t*)d->u_out; da->ldu = d->ldu; da->y = (bf16_t*)d->y; da->ldy = d->ldy;
+    da->w = d->w; da->H = d->H; da->W = d->W; da->C = d->C; da->eps = d->eps;
+    return GCC_OK;
 }
 
 }  // namespace
@@ -1956,6 +2170,27 @@ extern "C" int gcc_inorm_bwd(const void* x, int ldx, const void* y, int ldy, con
     a.out = (bf16_t*)dx; a.ldout = lddx; a.C = C; a.HW = HW; a.act = act; a.slope = slope;
     a.mean = (float*)mean; a.rstd = (float*)rstd;
     inorm_launch<true>(a, N, (hipStream_t)stream, workspace, workspace_bytes);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_dw_inorm_route(const gcc_dw_inorm_t* d) {
+    const int rc = dw_inorm_prepare(d, nullptr);
+    return rc == GCC_OK ? 1 : rc;
+}
+
+extern "C" int gcc_dw_inorm_fwd(const gcc_dw_inorm_t* d, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (gcc_device_error(0)) return GCC_ERR_LAUNCH;      // a bounded spin of an earlier launch expired: its results were wrong
+    DwInArgs da;
+    const int rc = dw_inorm_prepare(d, &da);
+    if (rc != GCC_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (da.g1.S > 1) inorm_ws_scrub(d->workspace, d->workspace_bytes, st);
+    const dim3 grid(da.g1.S, da.g1.CG, d->N);
+    if (d->mode == GCC_DWIN_PLAIN) hipLaunchKernelGGL(dw_inorm_kernel<GCC_DWIN_PLAIN>, grid, dim3(256), 0, st, da);
+    else if (d->mode == GCC_DWIN_NORM_RELU) hipLaunchKernelGGL(dw_inorm_kernel<GCC_DWIN_NORM_RELU>, grid, dim3(256), 0, st, da);
+    else hipLaunchKernelGGL(dw_inorm_kernel<GCC_DWIN_RESIDUAL>, grid, dim3(256), 0, st, da);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }

@@ -11,6 +11,8 @@ inside the concat buffer of the up path).
 Reference anchors: U-Net models/Pix2Pix.py:20-130, PatchGAN :267-348, hooks :363-373,702-727.
 """
 
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -1219,6 +1221,172 @@ class MobileResnetEngine:
         ops.reflect_pad(src, c.ypad, 3)
         self.last.forward(c.ypad, c.out, act=ACT_TANH)
         return c
+
+    # ---------------------------------------------------------------------------------------
+    # Eval-mode inference (infer): the stem and the up path as in forward(), each block as dw_inorm, pw1, dw_inorm(NORM_RELU),
+    # pw2 -- the depthwise conv and the InstanceNorm behind it are one launch (gcc_dw_inorm_fwd), which also takes the statistics
+    # of the 1x1 conv's output in front of it (and, from the second block on, adds the residual and stores the block input).  The
+    # trunk's last block ends in gcc_inorm_fwd(p2, residual).  4B + 14 launches against 8B + 13.  Buffers: one grow-only slab
+    # sized by the largest N * H * W seen; nothing of self.ctx / self.gbuf is read or written.
+
+    def _infer_bufs(self, N, H, W):
+        """views of the inference slab for an N x H x W input.  Building them writes nothing (infer_launches); infer() zero-fills
+        the slab behind the input when the previous pass wrote it in another geometry's layout (the pad channels every kernel
+        reads as zero)."""
+        h, w = H // 4, W // 4
+        tw = max([self.stem[2].rows] + [c for b in self.blocks for c in (b.dw1.C, b.pw2.rows)])       # trunk width
+        mw = max([8] + [b.pw1.rows for b in self.blocks])
+        L = ops.ceil8
+        shapes = [('x_in', self.in_nc, H, W), ('xpad', self.in_nc, H + 6, W + 6)]
+        shapes += [('s_raw%d' % i, self.stem[i].rows, H >> i, W >> i) for i in range(3)]
+        shapes += [('s_act%d' % i, self.stem[i].rows, H >> i, W >> i) for i in range(2)]
+        shapes += [('u0', tw, h, w), ('u1', tw, h, w), ('n', max(tw, mw), h, w), ('p1', mw, h, w), ('p2', tw, h, w)]
+        shapes += [('fa', max(tw, mw), h, w), ('fb', max(tw, mw), h, w)]       # a declined dw_inorm's u and conv output
+        shapes += [('t_raw%d' % i, self.ups[i].cols, H >> (1 - i), W >> (1 - i)) for i in range(2)]
+        shapes += [('t_act%d' % i, self.ups[i].cols, H >> (1 - i), W >> (1 - i)) for i in range(2)]
+        shapes += [('ypad', self.ups[1].cols, H + 6, W + 6), ('out', self.out_nc, H, W)]
+        offs, total = {}, 0
+        for name, Cc, hh, ww in shapes:
+            offs[name] = (total, Cc, hh, ww)
+            total += N * hh * ww * L(Cc)
+        key = (N, H, W)
+        if getattr(self, '_ev_slab', None) is None or self._ev_slab.numel() < total:
+            self._ev_slab = self._ev_views = self._ev_written = None
+            self._ev_slab = torch.zeros(total, dtype=torch.bfloat16, device=self.device)
+        st_need = 4 * N * max([tw, mw] + [op.rows for op in self.stem] + [op.cols for op in self.ups])
+        if getattr(self, '_ev_st', None) is None or self._ev_st.numel() < st_need:
+            self._ev_st = self._ev_views = None
+            self._ev_st = torch.zeros(st_need, dtype=torch.float32, device=self.device)
+        if getattr(self, '_ev_key', None) != key or getattr(self, '_ev_views', None) is None:
+            slab = self._ev_slab
+            v = type('ResnetInferBufs', (), {})()
+            for name, (off, Cc, hh, ww) in offs.items():
+                setattr(v, name, slab[off:off + N * hh * ww * L(Cc)].view(N, hh, ww, L(Cc)).permute(0, 3, 1, 2)[:, :Cc])
+            # the InstanceNorm launches' mean / rstd / scale / shift rows: written, never read
+            q = self._ev_st.numel() // 4
+            v.st = type('ResnetInferStats', (), {})()
+            v.st.ptrs = tuple(self._ev_st[i * q:].data_ptr() for i in range(4))
+            v.dw = {}          # (block, layer), stream -> (gcc_dw_inorm_t, served): see _dw_in
+            v.key, v.zero_from = key, offs['xpad'][0]
+            self._ev_views, self._ev_key = v, key
+        return self._ev_views
+
+    def infer_input(self, N, H, W):
+        """the slab's input view (NHWC bf16, in_nc channels): fill it, then infer(it)"""
+        return self._infer_bufs(N, H, W).x_in
+
+    def _dw_in(self, slot, mode, dw, x, y, r=None, u_out=None, count_only=False):
+        """depthwise conv + InstanceNorm of one block: one gcc_dw_inorm_fwd launch, or -- a geometry it declines -- the launches of
+        forward(): the InstanceNorm that makes u, the depthwise conv, the InstanceNorm behind it.  The descriptor and the
+        library's answer are made once per (block, layer) and stream and kept with the slab's views."""
+        E = _lib
+        v = self._ev_views
+        key = (slot, ops.stream())
+        got = v.dw.get(key)
+        if got is None:
+            d = ops.dw_inorm_desc(mode, x, dw.weight.data, y, r, u_out)
+            got = v.dw[key] = (d, ops.lib().gcc_dw_inorm_route(ctypes.byref(d)) == 1)
+        d, served = got
+        if served:
+            if not count_only:
+                _lib.check(ops.lib().gcc_dw_inorm_fwd(ctypes.byref(d), ops.stream()), 'gcc_dw_inorm_fwd')
+            return 1
+        if count_only:
+            return 3 if mode != E.DWIN_PLAIN else 2
+        Cc = dw.C
+        u = x
+        if mode == E.DWIN_NORM_RELU:
+            u = ops.cslice(v.fa, 0, Cc)
+            ops.inorm_fwd(x, u, v.st, act=ACT_RELU)
+        elif mode == E.DWIN_RESIDUAL:
+            u = u_out
+            ops.inorm_fwd(x, u, v.st, residual=r)
+        d = ops.cslice(v.fb, 0, Cc)
+        dw.forward(u, d)
+        ops.inorm_fwd(d, y, v.st)
+        return 3 if mode != E.DWIN_PLAIN else 2
+
+    def _infer(self, x, count_only=False):
+        N, _, H, W = x.shape
+        if H % 4 or W % 4:
+            raise _lib.GccError('MobileResnetEngine.infer: H, W must be multiples of 4')
+        v = self._infer_bufs(N, H, W)
+        E = _lib
+        launches = 0
+        if not count_only and getattr(self, '_ev_written', None) not in (None, v.key):
+            self._ev_slab[v.zero_from:].zero_()
+        if not count_only:
+            self._ev_written = v.key
+
+        def inorm(src, dst, act=ACT_NONE, residual=None):
+            if not count_only:
+                ops.inorm_fwd(src, dst, v.st, act=act, residual=residual)
+            return 1
+
+        def conv(op, src, dst, act=ACT_NONE):
+            if not count_only:
+                b = op.bias.data if op.bias is not None else None
+                if op.transposed:
+                    ops.conv_dgrad(src, op.wt, op.cols_k, dst.shape[2], dst.shape[3], op.k, op.stride, op.pad, out=dst, bias=b,
+                                   act=act, ws_slot=None)
+                else:
+                    ops.conv_fprop(src, op.w, op.rows_k, op.k, op.stride, op.pad, out=dst, bias=b, act=act, ws_slot=None)
+            return 1
+
+        if not count_only:
+            ops.reflect_pad(x, v.xpad, 3)
+        launches += 1
+        src = v.xpad
+        for i in range(3):
+            launches += conv(self.stem[i], src, getattr(v, 's_raw%d' % i))
+            if i < 2:
+                launches += inorm(getattr(v, 's_raw%d' % i), getattr(v, 's_act%d' % i), act=ACT_RELU)
+                src = getattr(v, 's_act%d' % i)
+        if self.blocks:
+            launches += inorm(v.s_raw2, v.u0, act=ACT_RELU)
+        else:
+            launches += inorm(v.s_raw2, v.u1, act=ACT_RELU)
+        u, unext = v.u0, v.u1
+        for bi, b in enumerate(self.blocks):
+            cin, cmid = b.dw1.C, b.pw1.rows
+            n1, n2 = ops.cslice(v.n, 0, cin), ops.cslice(v.n, 0, cmid)
+            p1, p2 = ops.cslice(v.p1, 0, cmid), ops.cslice(v.p2, 0, b.pw2.rows)
+            if bi == 0:
+                launches += self._dw_in((bi, 1), E.DWIN_PLAIN, b.dw1, ops.cslice(u, 0, cin), n1, count_only=count_only)
+            else:
+                launches += self._dw_in((bi, 1), E.DWIN_RESIDUAL, b.dw1, p2, n1, r=ops.cslice(u, 0, cin), u_out=ops.cslice(unext, 0, cin),
+                                        count_only=count_only)
+                u, unext = unext, u
+            launches += conv(b.pw1, n1, p1)
+            launches += self._dw_in((bi, 2), E.DWIN_NORM_RELU, b.dw2, p1, n2, count_only=count_only)
+            launches += conv(b.pw2, n2, p2)
+        if self.blocks:
+            last = self.blocks[-1]
+            launches += inorm(ops.cslice(v.p2, 0, last.pw2.rows), ops.cslice(unext, 0, last.pw2.rows),
+                              residual=ops.cslice(u, 0, last.pw2.rows))
+            src = ops.cslice(unext, 0, last.pw2.rows)
+        else:
+            src = v.u1
+        for i in range(2):
+            launches += conv(self.ups[i], src, getattr(v, 't_raw%d' % i))
+            launches += inorm(getattr(v, 't_raw%d' % i), getattr(v, 't_act%d' % i), act=ACT_RELU)
+            src = getattr(v, 't_act%d' % i)
+        if not count_only:
+            ops.reflect_pad(src, v.ypad, 3)
+        launches += 1
+        launches += conv(self.last, v.ypad, v.out, act=ACT_TANH)
+        return launches if count_only else v.out
+
+    def infer(self, x):
+        """eval-mode generator forward of an NHWC bf16 batch x [N, in_nc, H, W] (H, W multiples of 4) with the packed weights of
+        the last repack(): 4B + 14 launches for B residual blocks (infer_launches() says how many).  Returns the NHWC bf16 image
+        [N, out_nc, H, W], a view of the slab valid until the next call."""
+        return self._infer(x)
+
+    def infer_launches(self, N, H, W):
+        """kernel launches infer() makes for an N x H x W batch, from the library's route introspection (launches nothing and
+        writes nothing: an image an earlier infer() returned stays valid)"""
+        return self._infer(self.infer_input(N, H, W), count_only=True)
 
     # ---------------------------------------------------------------------------------------
     def backward(self, c, g_feat=None, wgrad=True, need_dx=False):

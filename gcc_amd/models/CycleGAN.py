@@ -383,6 +383,27 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             self._nchw[name] = ops.nhwc_to_nchw(self._ctx[name].out, 3)
         return self._nchw[name]
 
+    def infer_nhwc(self, real, generator='A'):
+        """one generator in eval mode on `real` through the fused inference path (MobileResnetEngine.infer): 'A' = netG_A
+        (A -> B), 'B' = netG_B (B -> A).  real: NCHW fp32, or a dataset batch dict -- the generator's own domain is picked the
+        way set_input picks real_A / real_B.  Uses the weights of the last finished optimizer step; touches no training buffer.
+        Returns an NHWC bf16 [N, 3, H, W] view valid until the next call of the same generator."""
+        if generator not in ('A', 'B'):
+            raise ValueError("generator must be 'A' or 'B'")
+        if isinstance(real, dict):
+            AtoB = self.opt.direction == 'AtoB'
+            real = real[('A' if AtoB else 'B') if generator == 'A' else ('B' if AtoB else 'A')]
+        real = real.to(self.device, torch.float32).contiguous()
+        N, _, H, W = real.shape
+        G = self.G[generator]
+        x = G.infer_input(N, H, W)
+        ops.nchw_to_nhwc(real, x, cfill=8)
+        return G.infer(x)
+
+    def infer(self, real, generator='A'):
+        """infer_nhwc as NCHW fp32"""
+        return ops.nhwc_to_nchw(self.infer_nhwc(real, generator), 3)
+
     fake_A = property(lambda self: self._image('fake_A'))
     fake_B = property(lambda self: self._image('fake_B'))
     rec_A = property(lambda self: self._image('rec_A'))

@@ -530,23 +530,17 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         """the generator in eval mode on `real` (NCHW fp32: the generator's input, real_A; or a dataset batch dict, whose input
         is picked by --direction as set_input does) through the fused inference path (UnetEngine.infer): an NHWC bf16
         [N, 3, H, W] view valid until the next call.  Refreshes the eval-mode coefficients (one launch) when the parameters or
-        running statistics changed since the last call.  The resnet backbone (InstanceNorm) has no fused path: forward()."""
+        running statistics changed since the last call.  --backbone resnet: MobileResnetEngine.infer."""
         if isinstance(real, dict):
             real = real['A' if self.opt.direction == 'AtoB' else 'B']
         real = real.to(self.device, torch.float32).contiguous()
         N, _, H, W = real.shape
         if self.resnet:
-            was = self.netG.training
-            self.netG.eval()
-            A = ops.new_act(N, 3, H, W, self.device)
-            ops.nchw_to_nhwc(real, A)
-            prev, self._A = getattr(self, '_A', None), A
-            try:
-                self.forward()
-            finally:
-                self._A = prev
-                self.netG.train(was)
-            return self._fake
+            # InstanceNorm without running statistics: nothing to refresh (MobileResnetEngine.infer)
+            self.finish_G_update()
+            x = self.G.infer_input(N, H, W)
+            ops.nchw_to_nhwc(real, x, cfill=8)
+            return self.G.infer(x)
         self.finish_G_update()
         if getattr(self, '_ev_generation', None) != self._g_generation:
             self.G.eval_coeffs()
@@ -557,7 +551,7 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def infer(self, real):
         """fake_B = G(real) in eval mode as NCHW fp32 (see infer_nhwc), whatever mode the model is in; forward() in eval mode
-        keeps its own route.  --backbone resnet: through forward() in eval mode (no fused path)."""
+        keeps its own route."""
         return ops.nhwc_to_nchw(self.infer_nhwc(real), 3)
 
     @property

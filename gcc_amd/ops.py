@@ -1095,6 +1095,34 @@ def inorm_fwd(x, y, st, act=ACT_NONE, slope=0.2, residual=None, eps=1e-5):
         check(rc, 'gcc_inorm_fwd')
 
 
+def dw_inorm_desc(mode, x, w, y, r=None, u_out=None, eps=1e-5, workspace=None):
+    """gcc_dw_inorm_t of a depthwise 3x3 (ReflectionPad2d(1)) + InstanceNorm launch; workspace: a uint8 tensor (default: the
+    stream's zero-filled 'dw_inorm' workspace)"""
+    xp, N, Cc, H, W, ldx = geom(x)
+    yp, _, _, _, _, ldy = geom(y)
+    d = _lib.dw_inorm_t(mode, xp, ldx, None, 0, None, 0, w.data_ptr(), None, yp, ldy, N, H, W, Cc, eps, None, 0)
+    if r is not None:
+        d.r, d.ldr = geom(r)[0], geom(r)[5]
+    if u_out is not None:
+        d.u_out, d.ldu = geom(u_out)[0], geom(u_out)[5]
+    ws = workspace if workspace is not None else zeroed_workspace(x.device, 'dw_inorm', _lib.DW_INORM_WORKSPACE_BYTES)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    return d
+
+
+def dw_inorm_route(mode, x, w, y, r=None, u_out=None, workspace=None):
+    """1: dw_inorm serves this geometry in one launch; otherwise the (negative) code gcc_dw_inorm_fwd would return"""
+    return lib().gcc_dw_inorm_route(C.byref(dw_inorm_desc(mode, x, w, y, r, u_out, workspace=workspace)))
+
+
+def dw_inorm(mode, x, w, y, r=None, u_out=None, eps=1e-5, workspace=None):
+    """y = InstanceNorm(dw3x3(ReflectionPad2d(1)(u))) in one launch (gcc_dw_inorm_fwd).  mode DWIN_PLAIN: u = x;
+    DWIN_NORM_RELU: u = relu(IN(x)); DWIN_RESIDUAL: u = r + IN(x), stored to u_out.  w: the fp32 master [C, 1, 3, 3]"""
+    d = dw_inorm_desc(mode, x, w, y, r, u_out, eps, workspace)
+    check(lib().gcc_dw_inorm_fwd(C.byref(d), stream()), 'gcc_dw_inorm_fwd')
+    return y
+
+
 def inorm_bwd(x, y, g, dx, st, act=ACT_NONE, slope=0.2):
     xp, N, Cc, H, W, ldx = geom(x)
     yp, ldy = (None, 0)

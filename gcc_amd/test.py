@@ -155,9 +155,7 @@ def run(opt, model):
         if opt.model == 'pix2pix':
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A)}
         elif opt.model == 'cyclegan':
-            with torch.no_grad():
-                model.visual_forward()
-            visuals = {'real_A': model.real_A, 'fake_B': _nhwc(model.fake_B)}
+            visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A, 'A')}
         else:
             with torch.no_grad():
                 model.forward()

@@ -53,7 +53,8 @@ long long gcc_launch_count(int reset);
 /* Device-side error word.  The kernels that wait for other workgroups inside a launch (the grid InstanceNorm's tagged exchange,
  * gcc_inorm_fwd / gcc_inorm_bwd / gcc_bn_bwd_one_launch) bound every spin; a spin that expires stores a non-zero code into a
  * pinned host word, the launch's results are wrong, and every later call of those entry points returns GCC_ERR_LAUNCH.
- * Returns the word (0: no error; 0x1401: InstanceNorm exchange timed out); clear != 0 resets it.  Never synchronises. */
+ * Returns the word (0: no error; 0x1401: InstanceNorm exchange timed out; 0x1402: gcc_dw_inorm_fwd exchange timed out); clear
+ * != 0 resets it.  Never synchronises. */
 int gcc_device_error(int clear);
 
 /* ---------------------------------------------------------------------------------------------
@@ -309,6 +310,41 @@ int gcc_in_finalize(const float* stats_partial, int tiles_per_group, int groups,
 int gcc_inorm_fwd(const void* x, int ldx, void* y, int ldy, const void* residual, int ld_residual, int C, int HW, int N,
                   int act, float slope, float eps, float* mean, float* rstd, float* scale, float* shift,
                   void* workspace, size_t workspace_bytes, gcc_stream_t stream);
+/* Depthwise 3x3 convolution behind a ReflectionPad2d(1) and the InstanceNorm2d(affine=False) after it in ONE launch: the
+ * MobileResnet blocks' eval-mode forward (models/Pix2Pix.py:132-197, models/CycleGAN.py:77-138; MobileResnetEngine.infer).
+ * Added without a GCC_HIP_ABI bump (additions only, no existing layout or numbering changed): a host built against this
+ * header that loads an older library fails when it binds gcc_dw_inorm_fwd, not at the gcc_version() check.
+ * Per image n and channel c < C, NHWC bf16, statistics over the H x W plane (biased variance, no affine):
+ *   u = x                                   (GCC_DWIN_PLAIN: x is the block input)
+ *   u = relu((p - mu_p) rho_p)              (GCC_DWIN_NORM_RELU: x = p, the raw output of the 1x1 conv in front)
+ *   u = r + (p - mu_p) rho_p                (GCC_DWIN_RESIDUAL: x = p, r = the previous block's input; u is stored to u_out)
+ *   d = dw3x3(ReflectionPad2d(1)(u)),  y = (d - mu_d) rho_d,  rho = 1 / sqrt(var + eps)
+ * u is rounded to bf16 once (as the training route stores it) and the conv reads that value; d is never stored; y is rounded
+ * once.  `bias` is not read: it cancels under the InstanceNorm (may be NULL).  Channels C .. ceil8(C) - 1 of y and u_out are
+ * written as zeros.  Statistics: fp32 partials folded in double in one fixed order (the same bits on every run).  The
+ * workgroups of an image meet at one (PLAIN) or two in-launch exchanges of the grid InstanceNorm (gcc_inorm_fwd); every spin
+ * is bounded, an expired one stores 0x1402 into the device error word (gcc_device_error) and later calls return
+ * GCC_ERR_LAUNCH.  Workspace contract as gcc_inorm_fwd's (zero-filled once, used by ONE stream), GCC_DW_INORM_WORKSPACE_BYTES
+ * serves every geometry the plan takes.  GCC_ERR_BAD_ARG: unknown mode, a missing pointer the mode needs, an ld that is not a
+ * multiple of 8 or below ceil8(C); GCC_ERR_UNSUPPORTED (nothing launched): the geometry is outside the grid plan (N > 64,
+ * C > 2048, H or W < 2, more (image, 16-channel group) domains than the grid budget, planes wider than an LDS tile's rows,
+ * about 500 pixels, more than 8 pixels per lane and sweep, where it no longer beats the launches it replaces);
+ * GCC_ERR_WORKSPACE: workspace too small.
+ * gcc_dw_inorm_route answers without launching: 1 (one launch) or the error code gcc_dw_inorm_fwd would return. */
+enum { GCC_DWIN_PLAIN = 0, GCC_DWIN_NORM_RELU = 1, GCC_DWIN_RESIDUAL = 2 };
+#define GCC_DW_INORM_WORKSPACE_BYTES ((size_t)4096 + ((size_t)3 << 20))
+typedef struct {
+    int mode;                           /* GCC_DWIN_* */
+    const void* x; int ldx;             /* PLAIN: the block input u; otherwise p, the raw output of the preceding 1x1 conv */
+    const void* r; int ldr;             /* RESIDUAL only: the previous block's input */
+    void* u_out; int ldu;               /* RESIDUAL only: u stored (the next block's residual) */
+    const float* w; const float* bias;  /* fp32 masters of nn.Conv2d(C, C, 3, groups=C): [C][9], [C] (bias not read) */
+    void* y; int ldy;
+    int N, H, W, C; float eps;
+    void* workspace; size_t workspace_bytes;
+} gcc_dw_inorm_t;
+int gcc_dw_inorm_fwd(const gcc_dw_inorm_t* d, gcc_stream_t stream);
+int gcc_dw_inorm_route(const gcc_dw_inorm_t* d);   /* 1: one launch; < 0: the code gcc_dw_inorm_fwd returns (nothing launched) */
 /* its backward: dx = rstd (dz - mean(dz) - xhat mean(dz xhat)) with dz = g act'(y) (y NULL: the activation output is
  * recomputed from x); dx may alias g. */
 int gcc_inorm_bwd(const void* x, int ldx, const void* y, int ldy, const void* g, int ldg, void* dx, int lddx, int C, int HW,
