@@ -49,6 +49,14 @@ class sn_item_t(C.Structure):
                 ('t_out', C.c_void_p), ('sigma_out', C.c_void_p), ('w', C.c_void_p), ('wt', C.c_void_p)]
 
 
+class sn_eval_item_t(C.Structure):
+    """include/gcc_hip.h gcc_sn_eval_item_t: one layer of gcc_spectral_eval_coeffs_group"""
+    _fields_ = [('w_bar', C.c_void_p), ('u', C.c_void_p), ('v', C.c_void_p), ('R', C.c_int), ('C', C.c_int), ('T', C.c_int),
+                ('t_out', C.c_void_p), ('sigma_out', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p),
+                ('running_mean', C.c_void_p), ('running_var', C.c_void_p), ('bias', C.c_void_p), ('eps', C.c_float),
+                ('pad_', C.c_int), ('scale', C.c_void_p), ('shift', C.c_void_p)]
+
+
 class epilogue_t(C.Structure):
     _fields_ = [('bias', C.c_void_p), ('act', C.c_int), ('slope', C.c_float), ('stats_partial', C.c_void_p),
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('bn', C.c_void_p),
@@ -229,6 +237,8 @@ PROTOTYPES = {
     'gcc_spectral_power_iteration_pack': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     'gcc_spectral_group_workspace': (_Z, [C.POINTER(sn_item_t), _I]),
     'gcc_spectral_power_iteration_pack_group': (_I, [C.POINTER(sn_item_t), _I, _P, _Z, _P]),
+    'gcc_spectral_eval_coeffs_workspace': (_Z, [C.POINTER(sn_eval_item_t), _I]),
+    'gcc_spectral_eval_coeffs_group': (_I, [C.POINTER(sn_eval_item_t), _I, _P, _Z, _P]),
     'gcc_spectral_grad': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     'gcc_resample_u8': (_I, [_P, _I, _I, _Z, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
     'gcc_crop_flip_normalize': (_I, [_P, _I, _I, _Z, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
@@ -244,6 +254,9 @@ PROTOTYPES = {
     'gcc_frechet_distance': (_I, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'gcc_attention_fwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_bwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    'gcc_attention_infer': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
+    'gcc_attention_infer_workspace': (_Z, [_I, _I, _I, _I]),
+    'gcc_attention_infer_route': (_I, [_I, _I, _I, _I, _Z]),
     'gcc_l1_loss': (_I, [_P, _I, _I, _P, _I, _I, _I, _Z, _F, _P, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_mse_loss': (_I, [_P, _I, _I, _P, _I, _I, _I, _Z, _F, _P, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_loss_workspace': (_Z, [_Z, _I]),

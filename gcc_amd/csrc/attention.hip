@@ -415,7 +415,185 @@ __global__ __launch_bounds__(256) void attn_bwd_k_kernel(const AttnArgs a) {
         }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Eval-only forward (gcc_attention_infer): y = gamma * softmax(q k^T) v + x with ONE pass over the keys -- an online softmax
+// (running row maximum m and sum l; O rescaled in fp32 when m moves) -- and nothing written but y: no o, no statistics, no map.
+// K and V rows of a 32-key step go through LDS once per workgroup (K as [key][channel] rows, V transposed as in the training
+// kernels), double-buffered with one barrier per step.  S > 1 splits the keys over S workgroups per (query block, channel
+// block, image); each writes its fp32 (m, l, O) partials and attn_infer_fold_kernel merges them and applies the epilogue.
+constexpr int KSTRIDE = 72;      // bf16 per LDS key row: 64 channels + 8 pad (144 bytes: 16-byte aligned reads)
+
+struct AttnInferArgs {
+    const bf16_t* qkv; int ldq, qoff, koff, voff;
+    const bf16_t* x; int ldx;
+    bf16_t* y; int ldy;
+    const float* gamma;
+    int B, N, C, C8;
+    int S, sps;                  // key slices and 32-key steps per slice; S == 1: the epilogue is applied in the pass
+    float* part_o;               // S > 1: [S][B*N][ceil8(C)] unnormalised O of each slice
+    float* part_ml;              // S > 1: [S][B*N][2] its row maximum and row sum
+};
+
+// 32 key rows x 64 channels (registers of stage_load) -> LDS [key][channel]: one 16-byte store per thread
+__device__ __forceinline__ void kstage_store(bf16_t (*K)[KSTRIDE], const i32x4& v) {
+    *(i32x4*)(&K[threadIdx.x >> 3][(threadIdx.x & 7) * 8]) = v;
+}
+
+// grid (ceil(N / 64), ceil(C / 64), B * S): 4 waves x 16 queries, 64 output channels, keys [sl * sps, (sl + 1) * sps) steps
+template <int DKS>
+__global__ __launch_bounds__(256) void attn_infer_kernel(const AttnInferArgs a) {
+    __shared__ __attribute__((aligned(16))) bf16_t KS[2][32][KSTRIDE];
+    __shared__ __attribute__((aligned(16))) bf16_t VT[2][64][TSTRIDE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, g = lane >> 4;
+    const int b = blockIdx.z / a.S, sl = blockIdx.z - b * a.S;
+    const int q0 = blockIdx.x * 64 + wave * 16, cb0 = blockIdx.y * 64;
+    const int N = a.N, C = a.C, dk8 = ceil8(a.C8), c8 = ceil8(C);
+    const bf16_t* base = a.qkv + (size_t)b * N * a.ldq;
+    bf16x8 qf[DKS];
+#pragma unroll
+    for (int kk = 0; kk < DKS; kk++) {
+        const int d = kk * 32 + g * 8;
+        qf[kk] = ldfrag(base + (size_t)(q0 + lr) * a.ldq + a.qoff + d, q0 + lr < N && d < dk8);
+    }
+    const int t_beg = sl * a.sps, t_end = min(t_beg + a.sps, cdiv(N, 32));
+    i32x4 kreg = stage_load(base, a.ldq, a.koff, 0, dk8, t_beg * 32, N);
+    i32x4 vreg = stage_load(base, a.ldq, a.voff, cb0, c8, t_beg * 32, N);
+    kstage_store(KS[0], kreg);
+    stage_store(VT[0], vreg);
+    __syncthreads();
+    float m = NEG, l = 0.f;
+    f32x4 O[4];
+#pragma unroll
+    for (int cb = 0; cb < 4; cb++) O[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = t_beg; t < t_end; t++) {
+        const int buf = (t - t_beg) & 1;
+        if (t + 1 < t_end) {
+            kreg = stage_load(base, a.ldq, a.koff, 0, dk8, (t + 1) * 32, N);
+            vreg = stage_load(base, a.ldq, a.voff, cb0, c8, (t + 1) * 32, N);
+        }
+        // transposed score tiles: s[4h + i] = q_(q0 + lr) . k_(32t + 16h + 4g + i)
+        float s[8];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < DKS; kk++)
+                acc = mma(__builtin_bit_cast(bf16x8, *(const i32x4*)(&KS[buf][h * 16 + lr][kk * 32 + g * 8])), qf[kk], acc);
+#pragma unroll
+            for (int i = 0; i < 4; i++) s[h * 4 + i] = (t * 32 + h * 16 + g * 4 + i < N) ? acc[i] : NEG;
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int e = 1; e < 8; e++) mx = fmaxf(mx, s[e]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));           // the step's maximum of row q0 + lr (a valid key in every step)
+        const float mn = fmaxf(m, mx), al = __expf(m - mn);
+        float p[8], sum = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            p[e] = s[e] > -1.0e38f ? __expf(s[e] - mn) : 0.f;
+            sum += p[e];
+        }
+        l = l * al + sum;                                 // this lane's share of the row sum (its 8 keys of every step)
+        // accumulator row 4g + i of O is query q0 + 4g + i, whose factor lives in lane 4g + i; skipped (exactly) when no row
+        // maximum of the wave moved
+        if (__any(mn != m)) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float ai = __shfl(al, g * 4 + i, 64);
+#pragma unroll
+                for (int cb = 0; cb < 4; cb++) O[cb][i] *= ai;
+            }
+        }
+        m = mn;
+        const bf16x8 pf = frag_of(p);
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++)
+            if (cb0 + cb * 16 < c8) O[cb] = mma(pf, tfrag(VT[buf], cb * 16 + lr, g), O[cb]);
+        if (t + 1 < t_end) {
+            kstage_store(KS[buf ^ 1], kreg);
+            stage_store(VT[buf ^ 1], vreg);
+        }
+        __syncthreads();
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    if (a.S > 1) {
+        const size_t rows = (size_t)a.B * N, r0 = (size_t)sl * rows + (size_t)b * N;
+        if (blockIdx.y == 0 && g == 0 && q0 + lr < N) {
+            float* ml = a.part_ml + (r0 + q0 + lr) * 2;
+            ml[0] = m; ml[1] = l;
+        }
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int q = q0 + g * 4 + i, c = cb0 + cb * 16 + lr;
+                if (q < N && c < c8) a.part_o[(r0 + q) * c8 + c] = O[cb][i];
+            }
+        return;
+    }
+    const float gm = a.gamma[0], il = 1.f / l;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const float ili = __shfl(il, g * 4 + i, 64);
+        const int q = q0 + g * 4 + i;
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++) {
+            const int c = cb0 + cb * 16 + lr;
+            if (q < N && c < c8) {
+                const size_t pix = (size_t)b * N + q;
+                a.y[pix * a.ldy + c] = f2bf(c < C ? gm * (O[cb][i] * ili) + bf2f(a.x[pix * a.ldx + c]) : 0.f);
+            }
+        }
+    }
+}
+
+// the S slices' partials of one (pixel, 8 channels) per thread: M = max m_s, L = sum l_s e^(m_s - M), O = sum O_s e^(m_s - M);
+// y = gamma O / L + x (channels C .. ceil8(C) - 1: zeros), one 16-byte store
+__global__ __launch_bounds__(256) void attn_infer_fold_kernel(const AttnInferArgs a) {
+    const int c8 = ceil8(a.C), G8 = c8 >> 3;
+    const size_t rows = (size_t)a.B * a.N;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * G8) return;
+    const size_t row = idx / G8;
+    const int c = (int)(idx - row * G8) * 8;
+    float M = NEG;
+    for (int s = 0; s < a.S; s++) M = fmaxf(M, a.part_ml[((size_t)s * rows + row) * 2]);
+    float L = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < a.S; s++) {
+        const float* ml = a.part_ml + ((size_t)s * rows + row) * 2;
+        const float w = __expf(ml[0] - M);
+        L += ml[1] * w;
+        const f32x4* po = (const f32x4*)(a.part_o + ((size_t)s * rows + row) * c8 + c);
+        const f32x4 u0 = po[0], u1 = po[1];
+#pragma unroll
+        for (int j = 0; j < 4; j++) { o[j] += w * u0[j]; o[4 + j] += w * u1[j]; }
+    }
+    const float gm = a.gamma[0], il = 1.f / L;
+    const bf16_t* xr = a.x + row * a.ldx;
+    float out[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[j] = c + j < a.C ? gm * (o[j] * il) + bf2f(xr[c + j]) : 0.f;
+    *(i32x4*)(a.y + row * a.ldy + c) = pack8(out);
+}
+
 bool ok_geom(int B, int N, int C, int C8) { return B > 0 && N > 0 && C > 0 && C <= 512 && C8 > 0 && C8 <= 64 && C8 <= C; }
+
+// key slices of the split route: only grids that leave most of the 256 CUs idle are split, into slices of >= 2 steps, up to
+// ~256 workgroups
+int attn_infer_slices(int B, int N, int C) {
+    const int grid = cdiv(N, 64) * cdiv(C, 64) * B, nsteps = cdiv(N, 32);
+    if (grid >= 128 || nsteps < 4) return 1;
+    int S = min(min(cdiv(256, grid), nsteps / 2), 16);
+    if (S < 2) return 1;
+    const int sps = cdiv(nsteps, S);
+    return cdiv(nsteps, sps);
+}
+size_t attn_infer_ws(int B, int N, int C, int S) {
+    return S > 1 ? (size_t)S * B * N * (ceil8(C) + 2) * sizeof(float) : 0;
+}
 
 }  // namespace
 
@@ -475,5 +653,48 @@ extern "C" int gcc_attention_bwd(const void* qkv, int ldq, int qoff, int koff, i
     }
 #undef GCC_ATTN_BWD
     GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" size_t gcc_attention_infer_workspace(int B, int N, int C, int C8) {
+    if (!ok_geom(B, N, C, C8) || N > 1024) return 0;
+    return attn_infer_ws(B, N, C, attn_infer_slices(B, N, C));
+}
+
+extern "C" int gcc_attention_infer_route(int B, int N, int C, int C8, size_t ws_bytes) {
+    if (!ok_geom(B, N, C, C8) || N > 1024) return GCC_ERR_UNSUPPORTED;
+    const int S = attn_infer_slices(B, N, C);
+    return (S > 1 && ws_bytes >= attn_infer_ws(B, N, C, S)) ? 2 : 1;
+}
+
+extern "C" int gcc_attention_infer(const void* qkv, int ldq, int qoff, int koff, int voff, const void* x, int ldx,
+                                   const float* gamma, int B, int N, int C, int C8, void* y, int ldy, void* ws, size_t ws_bytes,
+                                   gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!qkv || !x || !gamma || !y) return GCC_ERR_BAD_ARG;
+    if (!ok_geom(B, N, C, C8) || N > 1024) return GCC_ERR_UNSUPPORTED;
+    if ((ldq | qoff | koff | voff | ldx | ldy) & 7 || ldq < voff + ceil8(C) || ldy < ceil8(C)) return GCC_ERR_BAD_ARG;
+    if (ws && (((uintptr_t)ws) & 15)) return GCC_ERR_BAD_ARG;
+    AttnInferArgs a = {};
+    a.qkv = (const bf16_t*)qkv; a.ldq = ldq; a.qoff = qoff; a.koff = koff; a.voff = voff;
+    a.x = (const bf16_t*)x; a.ldx = ldx; a.y = (bf16_t*)y; a.ldy = ldy; a.gamma = gamma;
+    a.B = B; a.N = N; a.C = C; a.C8 = C8;
+    const int nsteps = cdiv(N, 32);
+    a.S = gcc_attention_infer_route(B, N, C, C8, ws ? ws_bytes : 0) == 2 ? attn_infer_slices(B, N, C) : 1;
+    a.sps = cdiv(nsteps, a.S);
+    if (a.S > 1) {
+        a.part_o = (float*)ws;
+        a.part_ml = a.part_o + (size_t)a.S * B * N * ceil8(C);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(cdiv(N, 64), cdiv(C, 64), B * a.S);
+    if (C8 <= 32) hipLaunchKernelGGL((attn_infer_kernel<1>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_infer_kernel<2>), grid, dim3(256), 0, st, a);
+    GCC_CHECK_LAUNCH();
+    if (a.S > 1) {
+        const size_t threads = (size_t)B * N * (ceil8(C) >> 3);
+        hipLaunchKernelGGL(attn_infer_fold_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, a);
+        GCC_CHECK_LAUNCH();
+    }
     return GCC_OK;
 }

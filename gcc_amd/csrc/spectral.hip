@@ -198,6 +198,36 @@ __global__ __launch_bounds__(256) void sn_scale_pack_group_kernel(const SnGroupA
     sn_scale_pack_body(it.a.w, it.a.scal, it.a.R, it.a.T, it.a.C, it.colsp, it.rowsp, it.pw, it.pwt, bx, by, tap, t);
 }
 
+// ---- eval-mode coefficients (gcc_spectral_eval_coeffs_group): the grouped power iteration's first three launches, the third one
+// also writing every layer's eval coefficients with 1/sigma folded in -- its workgroups all form the same |t|^2 (sn_finalize_body),
+// so each derives sigma itself, in the body's own arithmetic, and covers its share of the output channels; no weight is written.
+struct SnEvalExtra {
+    const float* gamma; const float* beta; const float* rm; const float* rv; const float* bias;
+    float* scale; float* shift;
+    int C; float eps;
+};
+struct SnEvalArgs { SnGroupArgs g; SnEvalExtra e[GCC_SPECTRAL_GROUP_MAX]; };
+__global__ __launch_bounds__(256) void sn_finalize_coeffs_group_kernel(const SnEvalArgs ga) {
+    __shared__ float sh[4];
+    const SnGroupArgs& g = ga.g;
+    const int i = sn_group_find(g, blockIdx.x, 3);
+    const SnGroupItem& it = g.it[i];
+    const int block = blockIdx.x - it.b3;
+    sn_finalize_body(it.a, block, it.n3, sh);
+    float t2 = 0.f;
+    for (int r = threadIdx.x; r < it.a.R; r += 256) t2 += it.a.t[r] * it.a.t[r];
+    t2 = block_sum(t2, sh);
+    const float sigma = t2 * (1.f / (sqrtf(t2) + 1e-12f));
+    const SnEvalExtra& e = ga.e[i];
+    for (int c = block * 256 + threadIdx.x; c < e.C; c += it.n3 * 256) {
+        const float gm = e.gamma ? e.gamma[c] : 1.f;
+        const float r = e.rv ? gm / sqrtf(e.rv[c] + e.eps) : gm;
+        const float b = e.bias ? e.bias[c] : 0.f;
+        e.scale[c] = r / sigma;
+        e.shift[c] = (e.beta ? e.beta[c] : 0.f) + (b - (e.rm ? e.rm[c] : 0.f)) * r;
+    }
+}
+
 __global__ __launch_bounds__(256) void sn_scale_kernel(const float* __restrict__ w, const float* scal, float* __restrict__ w_eff,
                                                        size_t n) {
     const float inv = 1.f / scal[2];
@@ -389,5 +419,55 @@ extern "C" int gcc_spectral_grad(const float* g_eff, const float* w_bar, const f
                            (const float*)partial, nb, C, T, dv);
         GCC_CHECK_LAUNCH();
     }
+    return GCC_OK;
+}
+
+static size_t sn_eval_item_ws(const gcc_sn_eval_item_t& it) { return (gcc_spectral_workspace(it.R, it.C, it.T) + 255) & ~(size_t)255; }
+extern "C" size_t gcc_spectral_eval_coeffs_workspace(const gcc_sn_eval_item_t* items, int n) {
+    if (!items || n < 1 || n > GCC_SPECTRAL_GROUP_MAX) return 0;
+    size_t total = 0;
+    for (int i = 0; i < n; i++) {
+        if (items[i].R <= 0 || items[i].C <= 0 || items[i].T <= 0) return 0;
+        total += sn_eval_item_ws(items[i]);
+    }
+    return total;
+}
+
+extern "C" int gcc_spectral_eval_coeffs_group(const gcc_sn_eval_item_t* items, int n, void* ws, size_t ws_bytes,
+                                              gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!items || n < 1 || n > GCC_SPECTRAL_GROUP_MAX || !ws || (((uintptr_t)ws) & 15)) return GCC_ERR_BAD_ARG;
+    const size_t need = gcc_spectral_eval_coeffs_workspace(items, n);
+    if (!need) return GCC_ERR_BAD_ARG;
+    if (ws_bytes < need) return GCC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    SnEvalArgs ga;
+    SnGroupArgs& g = ga.g;
+    g.n = n; g.pad = 0;
+    int b1 = 0, b2 = 0, b3 = 0;
+    char* wsp = (char*)ws;
+    for (int i = 0; i < n; i++) {
+        const gcc_sn_eval_item_t& q = items[i];
+        if (!q.w_bar || !q.u || !q.v || !q.t_out || !q.sigma_out || !q.scale || !q.shift || !(q.eps >= 0.f)) return GCC_ERR_BAD_ARG;
+        SnGroupItem& it = g.it[i];
+        float* scal = (float*)wsp;
+        it.a.w = q.w_bar; it.a.u = q.u; it.a.v = q.v; it.a.R = q.R; it.a.C = q.C; it.a.T = q.T;
+        it.a.vt = scal + 64; it.a.t = q.t_out; it.a.scal = scal; it.a.w_eff = nullptr; it.a.sigma_out = q.sigma_out;
+        it.pw = nullptr; it.pwt = nullptr;
+        it.K = q.C * q.T; it.colsp = 0; it.rowsp = 0; it.gx = 0; it.gy = 0;
+        it.b1 = b1; it.b2 = b2; it.b3 = b3; it.b4 = 0;
+        it.n3 = nblocks(it.K, 64);
+        b1 += (it.K + 63) / 64; b2 += q.R; b3 += it.n3;
+        SnEvalExtra& e = ga.e[i];
+        e.gamma = q.gamma; e.beta = q.beta; e.rm = q.running_mean; e.rv = q.running_var; e.bias = q.bias;
+        e.scale = q.scale; e.shift = q.shift; e.C = q.C; e.eps = q.eps;
+        wsp += sn_eval_item_ws(q);
+    }
+    hipLaunchKernelGGL(sn_wtu_group_kernel, dim3(b1), dim3(1024), 0, st, g);
+    GCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sn_wv_group_kernel, dim3(b2), dim3(256), 0, st, g);
+    GCC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sn_finalize_coeffs_group_kernel, dim3(b3), dim3(256), 0, st, ga);
+    GCC_CHECK_LAUNCH();
     return GCC_OK;
 }

@@ -1615,6 +1615,7 @@ class SaganGeneratorEngine:
         if getattr(self, '_pack', None) is None:
             self._pack = ops.PackPlan(self.convs(), self.device)
         self._pack.run()
+        self.wgen = getattr(self, 'wgen', 0) + 1           # infer() rebuilds its own packings on the next call
 
     def _ctx(self, N, tag='main'):
         key = (N, tag)
@@ -1695,6 +1696,145 @@ class SaganGeneratorEngine:
             if i > 0:
                 self.sn[i].backward_data(c.sn[i], G.raw[i], G.y[i - 3] if i - 1 >= 2 else G.act[i - 1])
         ops.SideStream.get(self.device).join()
+
+
+    # ---- inference: eval mode through gcc_conv_eval_ex and gcc_attention_infer -------------------------------------------------
+    # One gcc_spectral_eval_coeffs_group (3 launches) runs the four power iterations -- u, v move exactly as in an eval forward()
+    # -- and writes each SN layer's BatchNorm coefficients with 1/sigma folded in, so l1..l4 convolve with bf16(W_bar) and apply
+    # scale / shift + ReLU in their epilogue; each attention block is one 1x1 conv into q | k | v and gcc_attention_infer; `last`
+    # is a conv + bias + tanh.  The bf16(W_bar) and q | k | v packings are the inference path's own, rebuilt when repack()
+    # moved the weight generation; BatchNorm parameters and running statistics, the SN and `last` biases and gamma are read on
+    # the device in every call.  Activations live in one grow-only slab; self.ctx, self.gbuf and the SNStates are never touched.
+
+    def _ev_weights(self):
+        """the inference path's bf16 packings and coefficient buffers (made once; filled by _ev_repack)"""
+        if getattr(self, '_ev_w', None) is not None:
+            return self._ev_w
+        dev, L = self.device, ops.ceil8
+        w = type('SaganInferWeights', (), {})()
+        w.wt = [torch.zeros((L(op.cols), 16, L(op.rows)), dtype=torch.bfloat16, device=dev) for op in self.sn]
+        w.t = [torch.zeros(op.rows, dtype=torch.float32, device=dev) for op in self.sn]
+        w.sigma = torch.zeros(4, dtype=torch.float32, device=dev)
+        w.scale = [torch.zeros(op.cols, dtype=torch.float32, device=dev) for op in self.sn]
+        w.shift = [torch.zeros(op.cols, dtype=torch.float32, device=dev) for op in self.sn]
+        w.items = None
+        # q | k | v as one 1x1 conv: rows [Wq; 0; Wk; 0; Wv] (zero rows up to the slice offsets), the biases concatenated alike
+        w.qkv_w = [torch.zeros((L(a.width), 1, L(a.convs[0].cols)), dtype=torch.bfloat16, device=dev) for a in self.attn]
+        w.qkv_b = [torch.zeros(a.width, dtype=torch.float32, device=dev) for a in self.attn]
+        w.gen = None
+        self._ev_w = w
+        return w
+
+    def _ev_repack(self, count_only=False):
+        """refresh the inference packings when the weight generation moved: library launches made (or, count_only, that would
+        be); the q | k | v biases are gathered by device copies beside them"""
+        w = self._ev_weights()
+        if w.gen == getattr(self, 'wgen', 0):
+            return 0
+        n = 0
+        for i, op in enumerate(self.sn):
+            if not count_only:
+                ops.pack_weights_into(op.w_bar.data, None, w.wt[i])
+            n += 1
+        for a, wq, bq in zip(self.attn, w.qkv_w, w.qkv_b):
+            for conv, (off, Cc) in zip(a.convs, a.slices):
+                if not count_only:
+                    ops.pack_weights_into(conv.weight.data, wq[off:off + Cc], None)
+                    bq[off:off + Cc].copy_(conv.bias.data)
+                n += 1
+        if not count_only:
+            # the descriptors of the coefficient launch, from the tensors' current addresses
+            w.items = ops.spectral_eval_items([(op.w_bar.data, op.u.data, op.v.data, w.t[i], w.sigma[i:i + 1], self.bn[i].bn,
+                                                op.bias.data if op.bias is not None else None, w.scale[i], w.shift[i])
+                                               for i, op in enumerate(self.sn)])
+            w.gen = getattr(self, 'wgen', 0)
+        return n
+
+    def _infer_bufs(self, N):
+        """views of the inference slab: the input z and three regions the layers rotate through (a layer never writes a region
+        it reads); the image lands in region 0"""
+        L = ops.ceil8
+        sizes = [(self.width[i], s) for i, s in enumerate((4, 8, 16, 32))]
+        per = [N * s * s * L(Cc) for Cc, s in sizes] + [N * 64 * 64 * 8]
+        per += [N * 256 * L(self.attn[0].width), N * 1024 * L(self.attn[1].width)]
+        size_z, size_r = N * L(self.z_dim), max(per)
+        total = size_z + 3 * size_r
+        if getattr(self, '_ev_slab', None) is None or self._ev_slab.numel() < total:
+            self._ev_slab = self._ev_views = None
+            self._ev_slab = torch.zeros(total, dtype=torch.bfloat16, device=self.device)
+        if getattr(self, '_ev_views', None) is not None and self._ev_views.N == N:
+            return self._ev_views
+        slab = self._ev_slab
+
+        def view(off, Cc, s):
+            return slab[off:off + N * s * s * L(Cc)].view(N, s, s, L(Cc)).permute(0, 3, 1, 2)[:, :Cc]
+        R = [size_z + i * size_r for i in range(3)]
+        v = type('SaganInferBufs', (), {})()
+        v.N = N
+        v.z = view(0, self.z_dim, 1)
+        v.act = [view(R[0], self.width[0], 4), view(R[1], self.width[1], 8), view(R[0], self.width[2], 16), None]
+        v.qkv = [view(R[1], self.attn[0].width, 16), view(R[1], self.attn[1].width, 32)]
+        v.y = [view(R[2], self.width[2], 16), view(R[2], self.width[3], 32)]
+        v.act[3] = view(R[0], self.width[3], 32)
+        v.out = view(R[0], 3, 64)
+        self._ev_views = v
+        return v
+
+    def infer_input(self, N):
+        """the slab's input view z [N, z_dim, 1, 1] (NHWC bf16): fill it, then infer(it)"""
+        return self._infer_bufs(N).z
+
+    def _infer(self, z, count_only=False):
+        N = z.shape[0]
+        v = self._infer_bufs(N)
+        E = _lib
+        w = self._ev_weights()
+        launches = self._ev_repack(count_only)
+        if not count_only:
+            ops.spectral_eval_coeffs_group(w.items, self.device)
+        launches += 3
+
+        def conv(op, wt, src, dst, scale, shift, act):
+            return ops.conv_eval_ex(src, wt, op.cols, op.k, op.stride, op.pad, dst, transposed=True, scale=scale, shift=shift,
+                                    act=act, route_only=count_only)
+        src = z
+        for i, op in enumerate(self.sn):
+            r = conv(op, w.wt[i], src, v.act[i], w.scale[i], w.shift[i], E.EVAL_ACT_RELU)
+            launches += r if count_only else 0
+            src = v.act[i]
+            if i >= 2:
+                a, j = self.attn[i - 2], i - 2
+                r = ops.conv_eval_ex(src, w.qkv_w[j], a.width, 1, 1, 0, v.qkv[j], shift=w.qkv_b[j], route_only=count_only)
+                launches += r if count_only else 0
+                r = ops.attention_infer(v.qkv[j], a.offs, src, a.module.gamma.data, a.C, a.C8, v.y[j], route_only=count_only)
+                launches += r if count_only else 0
+                src = v.y[j]
+        lo = self.last
+        r = ops.conv_eval_ex(src, lo.wt, lo.cols_k, lo.k, lo.stride, lo.pad, v.out, transposed=True,
+                             shift=lo.bias.data if lo.bias is not None else None, act=E.EVAL_ACT_TANH, route_only=count_only)
+        launches += r if count_only else 0
+        return launches if count_only else v.out
+
+    def infer(self, z):
+        """eval-mode generator forward of z [N, z_dim, 1, 1] (NHWC bf16, e.g. infer_input(N) filled): one power iteration of
+        every SN layer (u, v move as in an eval forward()), l1..l4 with BatchNorm and ReLU in the conv epilogue, each attention
+        block as a q | k | v conv and gcc_attention_infer, `last` + tanh.  Returns the NHWC bf16 image [N, 3, 64, 64], a view
+        of the slab valid until the next call (infer_launches() says how many launches it takes)."""
+        N = z.shape[0]
+        if N > getattr(self, '_ev_max_n', 0):
+            # the split-K and key-split scratch a batch needs is not monotonic in N (small grids split): size the grow-only
+            # workspaces for every batch up to N (only grids of < 128 workgroups split) so memory stays flat below it
+            self._infer_bufs(N)
+            for n in range(1, min(N, 128) + 1):
+                self.infer_launches(n)
+            self._ev_max_n = N
+        return self._infer(z)
+
+    def infer_launches(self, N):
+        """kernel launches infer() makes for a batch of N, from the library's route introspection (launches nothing and
+        writes nothing: an image an earlier infer() returned stays valid); includes the repacking a moved weight generation
+        costs the next call"""
+        return self._infer(self.infer_input(N), count_only=True)
 
 
 class SaganDiscriminatorEngine:

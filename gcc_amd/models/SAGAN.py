@@ -272,6 +272,22 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self._fake = self._gctx.out
         self._nchw = None
 
+    def infer_nhwc(self, z):
+        """fake_img = G(z) with the generator in eval mode, whatever mode the model is in, through the fused inference path
+        (SaganGeneratorEngine.infer): an NHWC bf16 [N, 3, 64, 64] view valid until the next call.  z: [N, z_dim] (or
+        [N, z_dim, 1, 1]) on the host or the device, or a dataset batch dict.  Like an eval forward() it advances the
+        generator's power iterations (u, v); it touches no training buffer.  forward() keeps its own route."""
+        if isinstance(z, dict):
+            z = z['z']
+        N = z.shape[0]
+        x = self.G.infer_input(N)
+        ops.nchw_to_nhwc(z.to(self.device, torch.float32).reshape(N, -1, 1, 1).contiguous(), x)
+        return self.G.infer(x)
+
+    def infer(self, z):
+        """infer_nhwc as NCHW fp32"""
+        return ops.nhwc_to_nchw(self.infer_nhwc(z), 3)
+
     @property
     def fake_img(self):
         if self._nchw is None:

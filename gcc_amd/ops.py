@@ -1302,6 +1302,28 @@ def spectral_power_iteration_pack_group(entries, slot='sn_group'):
               'gcc_spectral_power_iteration_pack_group')
 
 
+def spectral_eval_items(entries):
+    """[(w_bar, u, v, t_out, sigma_out, BatchNorm2d, bias or None, scale, shift)] -> the gcc_sn_eval_item_t array of
+    spectral_eval_coeffs_group (build once while the tensors stay where they are)"""
+    items = (_lib.sn_eval_item_t * len(entries))()
+    for it, (w_bar, u, v, t_out, sigma_out, bn, bias, scale, shift) in zip(items, entries):
+        R, Cc, kh, kw = w_bar.shape
+        it.w_bar, it.u, it.v, it.R, it.C, it.T = w_bar.data_ptr(), u.data_ptr(), v.data_ptr(), R, Cc, kh * kw
+        it.t_out, it.sigma_out = t_out.data_ptr(), sigma_out.data_ptr()
+        it.gamma, it.beta = _p(bn.weight.data if bn.weight is not None else None), _p(bn.bias.data if bn.bias is not None else None)
+        it.running_mean, it.running_var, it.eps = _p(bn.running_mean), _p(bn.running_var), float(bn.eps)
+        it.bias, it.scale, it.shift = _p(bias), scale.data_ptr(), shift.data_ptr()
+    return items
+
+
+def spectral_eval_coeffs_group(items, device, slot='sn_eval'):
+    """gcc_spectral_eval_coeffs_group on an array of spectral_eval_items: the power iterations (u, v, t, sigma as
+    spectral_power_iteration_pack_group) and every layer's eval-mode scale / shift with 1/sigma folded in, in three launches"""
+    ws = workspace(lib().gcc_spectral_eval_coeffs_workspace(items, len(items)), device, slot)
+    check(lib().gcc_spectral_eval_coeffs_group(items, len(items), ws.data_ptr(), ws.numel(), stream()),
+          'gcc_spectral_eval_coeffs_group')
+
+
 def spectral_grad(g_eff, w_bar, u, v, t_fwd, sigma_fwd, dw_bar, du=None, dv=None, slot='sn_bwd'):
     R, Cc, kh, kw = w_bar.shape
     ws = workspace(lib().gcc_spectral_workspace(R, Cc, kh * kw), w_bar.device, slot)
@@ -1319,6 +1341,26 @@ def attention_fwd(qkv, offs, x, gamma, Cc, C8, y, o, stats, A=None):
     op, _, _, _, _, ldo = geom(o)
     check(lib().gcc_attention_fwd(qp, ldq, offs[0], offs[1], offs[2], xp, ldx, gamma.data_ptr(), B, H * W, Cc, C8, yp, ldy,
                                   op, ldo, stats.data_ptr(), _p(A), stream()), 'gcc_attention_fwd')
+
+
+def attention_infer(qkv, offs, x, gamma, Cc, C8, y, split=True, slot='eval_attn', route_only=False):
+    """eval-only y = gamma * softmax(q^T k) v + x (gcc_attention_infer): one pass over the keys, nothing else written.
+    split: let a small grid split its keys (two launches) through the grow-only workspace `slot`; False: never split.
+    route_only: return the launches the call would make (1 or 2) without launching."""
+    qp, B, _, H, W, ldq = geom(qkv)
+    need = lib().gcc_attention_infer_workspace(B, H * W, Cc, C8) if split else 0
+    ws = workspace(need, qkv.device, slot) if need else None
+    if route_only:
+        rc = lib().gcc_attention_infer_route(B, H * W, Cc, C8, ws.numel() if ws is not None else 0)
+        if rc < 0:
+            check(rc, 'gcc_attention_infer_route')
+        return rc
+    xp, _, _, _, _, ldx = geom(x)
+    yp, _, _, _, _, ldy = geom(y)
+    check(lib().gcc_attention_infer(qp, ldq, offs[0], offs[1], offs[2], xp, ldx, gamma.data_ptr(), B, H * W, Cc, C8, yp, ldy,
+                                    ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream()),
+          'gcc_attention_infer')
+    return y
 
 
 def attention_bwd(qkv, offs, o, stats, gamma, dy, Cc, C8, dqkv, rowdot, dgamma=None):

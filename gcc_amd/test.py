@@ -5,7 +5,7 @@ Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
   pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path)
   srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer
   cyclegan  phase test, visual_forward, visuals real_A / fake_B
-  sagan     the first 1000 batches
+  sagan     the first 1000 batches; the generator through SAGANModel.infer_nhwc (fused eval path)
 Generated images are converted to bytes on the device (gcc_image_to_u8: the reference's tensor2im) and copied to the host once
 per batch; input images (fp32) go through the same arithmetic on the host.  PNGs are encoded by PIL on host threads."""
 import copy
@@ -156,6 +156,8 @@ def run(opt, model):
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A)}
         elif opt.model == 'cyclegan':
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A, 'A')}
+        elif opt.model == 'sagan':
+            visuals = {'fake_img': model.infer_nhwc(data), 'real_img': model.real_img}
         else:
             with torch.no_grad():
                 model.forward()

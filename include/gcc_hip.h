@@ -643,6 +643,29 @@ int gcc_spectral_power_iteration_pack_group(const gcc_sn_item_t* items, int n, v
 int gcc_spectral_grad(const float* g_eff, const float* w_bar, const float* u, const float* v, const float* t_fwd,
                       const float* sigma_fwd, int R, int C, int T, float* dw_bar, float* du, float* dv, void* ws,
                       size_t ws_bytes, gcc_stream_t stream);
+/* Eval-mode coefficients of the generator's spectrally normalised ConvTranspose2d + BatchNorm2d layers (SaganGeneratorEngine.infer):
+ * the grouped power iteration of gcc_spectral_power_iteration_pack_group -- u, v, t_out and sigma_out the same bits -- in THREE
+ * launches, the third of which (every workgroup of a layer forms the same sigma) also writes, for the C output channels,
+ *     scale[c] = gamma[c] / (sigma sqrt(running_var[c] + eps))
+ *     shift[c] = beta[c] + (bias[c] - running_mean[c]) gamma[c] / sqrt(running_var[c] + eps)
+ * so that scale * conv(x, bf16(W_bar)) + shift is the eval-mode BatchNorm of the conv with W_bar / sigma and its bias (sigma does
+ * not divide the bias).  No weight is written.  gamma / beta / bias / running_mean NULL: 1 / 0 / 0 / 0; running_var NULL: no
+ * division by sqrt(running_var + eps).  Added without a GCC_HIP_ABI bump (additions only).  n <= GCC_SPECTRAL_GROUP_MAX;
+ * ws: gcc_spectral_eval_coeffs_workspace(items, n) bytes (every layer its own scratch), 16-byte aligned. */
+typedef struct {
+    const float* w_bar;
+    float* u;
+    float* v;
+    int R, C, T;
+    float* t_out;
+    float* sigma_out;
+    const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+    const float* bias;
+    float eps; int pad_;
+    float* scale; float* shift;     /* [C] each */
+} gcc_sn_eval_item_t;
+size_t gcc_spectral_eval_coeffs_workspace(const gcc_sn_eval_item_t* items, int n);
+int gcc_spectral_eval_coeffs_group(const gcc_sn_eval_item_t* items, int n, void* ws, size_t ws_bytes, gcc_stream_t stream);
 /* Self attention, Self_Attn.forward (:72-104), per image over N = H*W <= 1024 positions: q, k (C8 channels) and v
  * (C <= 512 channels) are channel slices (qoff / koff / voff) of one NHWC bf16 buffer; y = gamma * softmax(q^T k) v + x.
  * The N x N score / attention matrices are never stored: the kernels recompute score tiles on the matrix cores (their
@@ -657,6 +680,20 @@ int gcc_attention_fwd(const void* qkv, int ldq, int qoff, int koff, int voff, co
 int gcc_attention_bwd(const void* qkv, int ldq, int qoff, int koff, int voff, const void* o, int ldo,
                       const float* stats, const float* gamma, const void* dy, int lddy, int B, int N, int C, int C8,
                       void* dqkv, int lddq, float* rowdot, float* dgamma, gcc_stream_t stream);
+/* Eval-only self attention (SaganGeneratorEngine.infer): y = gamma * softmax(q^T k) v + x as gcc_attention_fwd, with ONE pass
+ * over the keys (online softmax: running row maximum and sum, O rescaled in fp32) and nothing written but y -- no o, statistics
+ * or map.  y = gamma * O / l + x is formed in fp32 and rounded to bf16 once; channels C .. ceil8(C) - 1 of y are written as
+ * zeros.  K and V rows go through LDS once per workgroup.  Small grids (B = 1) split the keys over workgroups when `ws` holds
+ * gcc_attention_infer_workspace() bytes (16-byte aligned): fp32 (m, l, O) partials, then a second launch folds them and applies
+ * the epilogue; with ws NULL nothing is split.  Limits as gcc_attention_fwd (N <= 1024, C <= 512, 0 < C8 <= min(64, C)): any
+ * other geometry returns GCC_ERR_UNSUPPORTED, a missing pointer or an ld / offset that is not a multiple of 8 (or ldq below
+ * voff + ceil8(C), ldy below ceil8(C)) GCC_ERR_BAD_ARG, before anything is launched.  Added without a GCC_HIP_ABI bump.
+ * gcc_attention_infer_route answers without launching: the launches the call makes with `ws_bytes` of workspace (1, or 2 when
+ * the keys are split), or GCC_ERR_UNSUPPORTED.  gcc_attention_infer_workspace: 0 when the geometry is never split. */
+int gcc_attention_infer(const void* qkv, int ldq, int qoff, int koff, int voff, const void* x, int ldx, const float* gamma,
+                        int B, int N, int C, int C8, void* y, int ldy, void* ws, size_t ws_bytes, gcc_stream_t stream);
+size_t gcc_attention_infer_workspace(int B, int N, int C, int C8);
+int gcc_attention_infer_route(int B, int N, int C, int C8, size_t ws_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * SRGAN (models/SRGAN.py, models/GANLoss.py:95-145).
