@@ -519,3 +519,165 @@ extern "C" int gcc_crop_flip_normalize(const void* src, int H, int W, size_t pit
     const float half[3] = {0.5f, 0.5f, 0.5f};
     return gcc_crop_convert(src, H, W, pitch, x0, y0, crop_h, crop_w, flip, 0, half, half, nchw, nhwc_bf16, ld, stream);
 }
+
+// =============================================================================================
+// Cityscapes mIoU around the segmenter (metric/test_metric.py:47-87, metric/mIoU_score.py:70-105, 169-218).
+//   gcc_seg_input    util.tensor2im's byte of the generated image, then SegList's ToTensor + Normalize in fp32
+//   gcc_miou_score   resize_4d_tensor (PIL's 32-bit float BILINEAR resample, horizontal pass then vertical pass, f64 accumulation
+//                    in tap order, fp32 after each pass; a pass PIL skips runs with the table {1.0}, which keeps every value
+//                    but turns -0.0 into +0.0: equal under the argmax) + argmax over classes + fast_hist in ONE launch: the resized score tensor
+//                    ([N][19][1024][2048] fp32 in the reference) never exists.  Pillow multiplies and adds separately in f64:
+//                    the kernel is compiled with `fp contract(off)` and spells the products and sums as plain operators (the
+//                    __dmul_rn / __dadd_rn header functions carry the translation unit's contraction flag and were fused).
+// A workgroup owns MS_TH output rows x 256 output columns, one column per thread.  The rows of a tile share at most MS_TH + 2
+// source rows (supported sizes never shrink, so consecutive output rows advance by at most one source row): per class the thread
+// resamples those source rows horizontally once into its own LDS column, applies each output row's vertical taps (read from the
+// table once, before the class loop) and carries best / best index per row in registers across the class loop.  Labels feed a
+// per-workgroup uint32 histogram in LDS that is folded into the int64 table with 64-bit atomics (integers: the result does not
+// depend on arrival order).  Measured at 19 x 256 x 256 -> 1024 x 2048 (profiles/r8_miou_ab.txt): MS_TH 8 beats 4 and 16; staging
+// the source window of several class planes in LDS first, or issuing a class plane's loads ahead of their use, was slower.
+namespace {
+
+constexpr int MS_TW = 256, MS_TH = 8, MS_SRC = MS_TH + 2, MS_TAPS = 3, MS_MAX_CLASSES = 64;
+
+struct SegInArgs { float mean[3], stdv[3]; };
+
+__global__ __launch_bounds__(256) void seg_input_kernel(const bf16_t* __restrict__ xb, const unsigned char* __restrict__ xu, int ld,
+                                                        int off, size_t plane, size_t total, const SegInArgs a,
+                                                        float* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t n = i / plane, p = i - n * plane;
+        float* o = out + n * 3 * plane + p;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float b;
+            if (xu) {
+                b = (float)xu[i * 3 + c];
+            } else {
+                // util.tensor2im exactly as gcc_image_to_u8 computes it
+                float t = __fmul_rn(__fmul_rn(__fadd_rn(bf2f(xb[i * ld + off + c]), 1.f), 0.5f), 255.f);
+                t = t > 0.f ? (t < 255.f ? t : 255.f) : 0.f;
+                b = (float)(unsigned char)t;
+            }
+            // ToTensor's img.float() / 255, then Normalize's t.sub_(m).div_(s): two IEEE divisions, no reciprocal
+            o[(size_t)c * plane] = __fsub_rn(b / 255.f, a.mean[c]) / a.stdv[c];
+        }
+    }
+}
+
+struct MiouArgs {
+    const float* scores; const unsigned char* labels;
+    const int* hb; const double* hc; const int* vb; const double* vc;
+    unsigned long long* hist; unsigned char* pred;
+    int C, h, w, H, W, hk, vk;
+};
+
+__global__ __launch_bounds__(256) void miou_score_kernel(const MiouArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ unsigned int sh[];                 // [C][C]
+    __shared__ float hv[MS_SRC][MS_TW];                  // column tid belongs to thread tid alone: no barrier around it
+    const int tid = threadIdx.x, x = blockIdx.x * MS_TW + tid, y0 = blockIdx.y * MS_TH, n = blockIdx.z;
+    const int C = a.C, nn = C * C;
+    for (int i = tid; i < nn; i += 256) sh[i] = 0u;
+    __syncthreads();
+    const int rows = min(MS_TH, a.H - y0);
+    if (x < a.W) {
+        // the tables come from the caller: every index derived from them is clamped into the source plane
+        int xcnt = min(min(a.hb[2 * x + 1], a.hk), MS_TAPS);
+        xcnt = max(min(xcnt, a.w), 0);
+        const int xmin = max(min(a.hb[2 * x], a.w - xcnt), 0);
+        double kx[MS_TAPS];
+#pragma unroll
+        for (int k = 0; k < MS_TAPS; k++) kx[k] = k < xcnt ? a.hc[(size_t)x * a.hk + k] : 0.0;
+        const int ybase = max(min(a.vb[2 * y0], a.h - 1), 0);
+        const int ylast = y0 + rows - 1;
+        const int nsrc = max(min(min(a.vb[2 * ylast] + a.vb[2 * ylast + 1], a.h) - ybase, MS_SRC), 1);
+        // the tile's vertical taps, read once (wave-uniform): the class loop below touches no table
+        int vj[MS_TH], vcnt[MS_TH];
+        double kv[MS_TH][MS_TAPS];
+        float best[MS_TH];
+        int bi[MS_TH];
+#pragma unroll
+        for (int r = 0; r < MS_TH; r++) {
+            const int y = min(y0 + r, ylast);
+            vcnt[r] = min(min(a.vb[2 * y + 1], a.vk), MS_TAPS);
+            vj[r] = a.vb[2 * y] - ybase;
+#pragma unroll
+            for (int k = 0; k < MS_TAPS; k++) kv[r][k] = k < vcnt[r] ? a.vc[(size_t)y * a.vk + k] : 0.0;
+            best[r] = 0.f; bi[r] = 0;
+        }
+        for (int c = 0; c < C; c++) {
+            const float* plane = a.scores + ((size_t)n * C + c) * a.h * a.w;
+            for (int j = 0; j < nsrc; j++) {
+                const float* row = plane + (size_t)(ybase + j) * a.w + xmin;
+                double ss = 0.0;
+#pragma unroll
+                for (int k = 0; k < MS_TAPS; k++)
+                    if (k < xcnt) ss += (double)row[k] * kx[k];
+                hv[j][tid] = (float)ss;
+            }
+#pragma unroll
+            for (int r = 0; r < MS_TH; r++) {
+                if (r < rows) {
+                    double ss = 0.0;
+#pragma unroll
+                    for (int k = 0; k < MS_TAPS; k++)
+                        if (k < vcnt[r]) {
+                            const int j = max(min(vj[r] + k, nsrc - 1), 0);
+                            ss += (double)hv[j][tid] * kv[r][k];
+                        }
+                    const float v = (float)ss;
+                    // numpy.argmax: first maximum; a NaN counts as the maximum (first NaN wins)
+                    if (c == 0) { best[r] = v; }
+                    else if (best[r] == best[r] && (v > best[r] || v != v)) { best[r] = v; bi[r] = c; }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < MS_TH; r++) {
+            if (r < rows) {
+                const size_t o = ((size_t)n * a.H + (y0 + r)) * a.W + x;
+                if (a.pred) a.pred[o] = (unsigned char)bi[r];
+                const int l = a.labels[o];
+                if (l < C) atomicAdd(&sh[C * l + bi[r]], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < nn; i += 256)
+        if (sh[i]) atomicAdd(&a.hist[i], (unsigned long long)sh[i]);
+}
+
+}  // namespace
+
+extern "C" int gcc_seg_input(const void* x, int is_u8, int ld, int off, int N, int H, int W, const float* mean3, const float* std3,
+                             float* out, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!x || !out || !mean3 || !std3 || N <= 0 || H <= 0 || W <= 0) return GCC_ERR_BAD_ARG;
+    if (!is_u8 && (ld <= 0 || off < 0 || (ld & 7) || (off & 7) || ld < off + 8)) return GCC_ERR_BAD_ARG;
+    SegInArgs a;
+    for (int c = 0; c < 3; c++) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+    const size_t plane = (size_t)H * W, total = plane * N;
+    hipLaunchKernelGGL(seg_input_kernel, dim3(nblk(total, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)(is_u8 ? nullptr : x), (const unsigned char*)(is_u8 ? x : nullptr), ld, off, plane, total, a, out);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_miou_score(const float* scores, int N, int C, int h, int w, const unsigned char* labels, int H, int W,
+                              const int* hbounds, const double* hcoef, int hk, const int* vbounds, const double* vcoef, int vk,
+                              long long* hist, unsigned char* pred, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!scores || !labels || !hbounds || !hcoef || !vbounds || !vcoef || !hist || N <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 ||
+        W <= 0 || hk <= 0 || vk <= 0)
+        return GCC_ERR_BAD_ARG;
+    // an enlarging (or size-keeping) BILINEAR table has at most 3 taps per row; a reducing one widens with the scale
+    if (h > H || w > W || C > MS_MAX_CLASSES || hk > MS_TAPS || vk > MS_TAPS || N > 65535 || (H + MS_TH - 1) / MS_TH > 65535)
+        return GCC_ERR_UNSUPPORTED;
+    MiouArgs a = {scores, labels, hbounds, hcoef, vbounds, vcoef, (unsigned long long*)hist, pred, C, h, w, H, W, hk, vk};
+    hipLaunchKernelGGL(miou_score_kernel, dim3((W + MS_TW - 1) / MS_TW, (H + MS_TH - 1) / MS_TH, N), dim3(256),
+                       (size_t)C * C * sizeof(unsigned int), (hipStream_t)stream, a);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}

@@ -76,19 +76,15 @@ _FILTERS = {'bicubic': (_bicubic, 2.0), 'bilinear': (_bilinear, 1.0)}
 _coeff_cache = {}
 
 
-def resample_coeffs(in_size, out_size, filter='bicubic'):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c) for the BICUBIC (or BILINEAR) filter over the whole
-    axis: (bounds int32 [out, 2], coefficients int32 [out, ksize], ksize).  Double arithmetic in Pillow's operation order."""
-    key = (in_size, out_size, filter)
-    if key in _coeff_cache:
-        return _coeff_cache[key]
-    _bicubic, base_support = _FILTERS[filter]
+def precompute_coeffs(in_size, out_size, filter='bicubic'):
+    """Pillow's precompute_coeffs (Resample.c) over the whole axis, in double arithmetic in Pillow's operation order:
+    (bounds [(xmin, count)] per output index, normalised double coefficients [count] per output index, ksize)"""
+    kernel, base_support = _FILTERS[filter]
     scale = float(np.float32(in_size) - np.float32(0.0)) / out_size
     filterscale = scale if scale >= 1.0 else 1.0
     support = base_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
-    bounds = np.zeros((out_size, 2), dtype=np.int32)
-    coef = np.zeros((out_size, ksize), dtype=np.int32)
+    bounds, coefs = [], []
     ss = 1.0 / filterscale
     for xx in range(out_size):
         center = 0.0 + (xx + 0.5) * scale
@@ -99,14 +95,28 @@ def resample_coeffs(in_size, out_size, filter='bicubic'):
         if xmax > in_size:
             xmax = in_size
         xmax -= xmin
-        k = [_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        k = [kernel((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for w in k:
             ww += w
-        for x in range(xmax):
-            v = k[x] / ww if ww != 0.0 else k[x]
+        coefs.append([k[x] / ww if ww != 0.0 else k[x] for x in range(xmax)])
+        bounds.append((xmin, xmax))
+    return bounds, coefs, ksize
+
+
+def resample_coeffs(in_size, out_size, filter='bicubic'):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c) for the BICUBIC (or BILINEAR) filter over the whole
+    axis: (bounds int32 [out, 2], coefficients int32 [out, ksize], ksize).  Double arithmetic in Pillow's operation order."""
+    key = (in_size, out_size, filter)
+    if key in _coeff_cache:
+        return _coeff_cache[key]
+    b, k, ksize = precompute_coeffs(in_size, out_size, filter)
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    coef = np.zeros((out_size, ksize), dtype=np.int32)
+    for xx in range(out_size):
+        for x, v in enumerate(k[xx]):
             coef[xx, x] = int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS))
-        bounds[xx] = (xmin, xmax)
+        bounds[xx] = b[xx]
     _coeff_cache[key] = (bounds, coef, ksize)
     return _coeff_cache[key]
 

@@ -44,11 +44,13 @@ def per_class_iu(hist):
 
 def test(fakes, names, model, device, table_path='datasets/table.txt', data_dir='database/cityscapes', batch_size=1,
          num_workers=8, num_classes=19, use_tqdm=True, dataset=None):
-    """metric/mIoU_score.py:196-218.  The reference's SegList reads label images from disk and resizes the score maps to
-    2048x1024 with PIL; ``dataset`` yields (image batch, label batch [N, H, W] int) directly and the labels' size is the
-    evaluation size."""
+    """metric/mIoU_score.py:196-218.  Without ``dataset``: the reference's call -- ``fakes`` (uint8 [h, w, 3] images, what get_mIoU
+    passes), ``names``, the label files ``table_path`` names under ``data_dir`` -- through gcc_amd.metric.cityscapes (the fused
+    scorer: PIL's float BILINEAR resize to 2048 x 1024, argmax and fast_hist in one launch).  ``dataset`` instead yields (image
+    batch, label batch [N, H, W] int) directly and the labels' size is the evaluation size."""
     if dataset is None:
-        raise NotImplementedError('pass dataset=: the label files of the reference\'s SegList are host I/O (out of scope)')
+        from .cityscapes import miou_of_fakes
+        return miou_of_fakes(fakes, names, model, device, table_path, data_dir, batch_size=batch_size, num_classes=num_classes)
     if hasattr(model, 'eval'):
         model.eval()
     hist = None

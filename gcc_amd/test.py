@@ -2,7 +2,8 @@
 over the test split, write PNGs under <checkpoints_dir>/<name>/test_results with the names of the reference's util.save_images.
 
 Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
-  pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path)
+  pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path);
+            on a Cityscapes root with table.txt and a TorchScript segmenter at --drn_path: prints the mIoU afterwards
   srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer
   cyclegan  phase test, visual_forward, visuals real_A / fake_B
   sagan     the first 1000 batches; the generator through SAGANModel.infer_nhwc (fused eval path)
@@ -148,12 +149,25 @@ def run(opt, model):
             w.close()
         return result_dir
     w = _Writer(result_dir, opt.direction, opt.aspect_ratio)
-    for i, data in enumerate(create_dataset(topt, model.device)):
+    scorer = None
+    if opt.model == 'pix2pix' and 'cityscapes' in str(opt.dataroot):      # metric/test_metric.py:78-87 on the images written here
+        from .metric.cityscapes import builtin_segmenter, cityscapes_evaluator
+        segmenter, why = builtin_segmenter(opt)
+        if segmenter is None:
+            print('no Cityscapes evaluation: %s' % why)
+        else:
+            scorer = cityscapes_evaluator(segmenter).scorer(model, topt)
+    dataset = create_dataset(topt, model.device)
+    if scorer is not None and getattr(dataset, 'paths', None) is not None:
+        scorer.prefetch(dataset.paths)
+    for i, data in enumerate(dataset):
         if opt.model == 'sagan' and i == 1000:
             break
         model.set_input(data)
         if opt.model == 'pix2pix':
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A)}
+            if scorer is not None:
+                scorer.add(data['A_paths'][0], visuals['fake_B'])
         elif opt.model == 'cyclegan':
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A, 'A')}
         elif opt.model == 'sagan':
@@ -165,6 +179,8 @@ def run(opt, model):
             visuals = {k: (_nhwc(t) if k in RESULT_LABELS_FAKE else t) for k, t in v.items()}
         w.write(visuals, model.image_paths)
     w.close()
+    if scorer is not None:
+        print('mIoU: %.2f' % scorer.result())
     return result_dir
 
 

@@ -9,7 +9,8 @@ Batches come from gcc_amd.data (host decode + the GPU transform chain of SURVEY.
 batch dicts ({'A','B','A_paths','B_paths'} ...) can be passed to main(datasets=...) instead.
 The per-epoch evaluation of the reference's loop (train.py:14-73, 160-165) needs third-party evaluator networks
 (Inception / DRN weights): main(evaluate=fn) takes the callable that produces the metric(s) -- gcc_amd.metric supplies
-the arithmetic downstream of those networks -- and keeps the reference's best-checkpoint bookkeeping around it.
+the arithmetic downstream of those networks -- and keeps the reference's best-checkpoint bookkeeping around it.  Without
+evaluate=, builtin_evaluator picks SRGAN's PSNR / SSIM or, given a TorchScript segmenter at --drn_path, the Cityscapes mIoU.
 """
 import copy
 import os
@@ -112,7 +113,16 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
 
 def builtin_evaluator(opt, logger):
     """the evaluation a run gets without an explicit evaluate=: SRGAN's PSNR / SSIM on the reference's test sets found under
-    <dataroot>/test (train.py:37-56); None otherwise -- FID and mIoU need evaluator networks the caller provides"""
+    <dataroot>/test (train.py:37-56); Pix2Pix's mIoU on a Cityscapes root that holds table.txt when --drn_path is a TorchScript
+    segmenter (train.py:16-25; gcc_amd.metric.cityscapes); None otherwise -- FID needs an evaluator network the caller provides"""
+    if opt.model == 'pix2pix' and 'cityscapes' in str(opt.dataroot):
+        from .metric.cityscapes import builtin_segmenter, cityscapes_evaluator
+        segmenter, why = builtin_segmenter(opt)
+        if segmenter is None:
+            logger.info('no Cityscapes mIoU evaluation: %s' % why)
+            return None
+        logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s' % (opt.save_epoch_freq, opt.drn_path))
+        return cityscapes_evaluator(segmenter, logger)
     if opt.model != 'srgan' or str(opt.dataroot).startswith('synthetic'):
         return None
     from .metric.sr_eval import available_sets, srgan_evaluator

@@ -800,6 +800,31 @@ int gcc_crop_flip_normalize(const void* src, int H, int W, size_t pitch, int x0,
 int gcc_crop_convert(const void* src, int H, int W, size_t pitch, int x0, int y0, int crop_h, int crop_w, int flip, int form,
                      const float* mean3, const float* std3, float* nchw, void* nhwc_bf16, int ld, gcc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cityscapes mIoU around the segmenter (metric/test_metric.py:47-87, metric/mIoU_score.py:70-105, 169-218).  Added without a
+ * GCC_HIP_ABI bump (additions only).
+ * gcc_seg_input: the segmenter's input from the generator's output in one launch: NCHW fp32 out[N][3][H][W] =
+ *   (float(byte) / 255.f - mean3[c]) / std3[c] in fp32 with two IEEE divisions (SegList's ToTensor + Normalize), where byte is
+ *   util.tensor2im's byte exactly as gcc_image_to_u8 computes it from an NHWC bf16 image [N][H][W] (ld, off: multiples of 8), or,
+ *   with is_u8 != 0, the byte itself of a DEVICE uint8 [N][H][W][3] image (ld, off unused).  mean3 / std3: host arrays.
+ * gcc_miou_score: resize_4d_tensor(final, W, H).argmax(axis=1) followed by fast_hist, per output pixel, without the resized
+ *   tensor.  scores NCHW fp32 [N][C][h][w]; labels uint8 [N][H][W]; the tables are Pillow's precompute_coeffs for BILINEAR in
+ *   double precision (not normalised to fixed point): hbounds int32 [W][2] = first source column and tap count, hcoef f64
+ *   [W][hk]; vbounds [H][2], vcoef [H][vk].  Resample.c for 32-bit float images: horizontal pass first, ss = 0.0;
+ *   ss += (double)src * coef per tap in tap order (an f64 multiply, then an f64 add: never fused), every tap inside the bounds
+ *   multiplied whatever its coefficient, the sum rounded to fp32; then the vertical pass over those fp32 values likewise.  A
+ *   pass PIL skips (equal sizes) has the one-coefficient table {1.0}: 0.0 + v * 1.0 is v for the argmax (-0.0 becomes +0.0,
+ *   which compares equal; the resized value itself is never output).  argmax as gcc_argmax_channels.  hist[C * label + pred]
+ *   += 1 where label < C (int64 [C][C], accumulated); pred: optional uint8 [N][H][W] (NULL: not written).  Supported: h <= H,
+ *   w <= W, hk <= 3, vk <= 3, C <= 64; GCC_ERR_UNSUPPORTED otherwise, before anything is launched.  Indices read from the
+ *   tables are clamped into the source plane: a malformed table gives wrong numbers, never an access outside `scores`.
+ * --------------------------------------------------------------------------------------------- */
+int gcc_seg_input(const void* x, int is_u8, int ld, int off, int N, int H, int W, const float* mean3, const float* std3,
+                  float* out, gcc_stream_t stream);
+int gcc_miou_score(const float* scores, int N, int C, int h, int w, const unsigned char* labels, int H, int W, const int* hbounds,
+                   const double* hcoef, int hk, const int* vbounds, const double* vcoef, int vk, long long* hist,
+                   unsigned char* pred, gcc_stream_t stream);
+
 /* ---- gradient exchange ---------------------------------------------------------------------------------
  * The reference trains on one device (models/Pix2Pix.py:356); the data-parallel path sums the five optimizers' flat fp32
  * gradient buffers over ranks before each `optimizer.step()` (train.py has no counterpart: this is the exchange a
