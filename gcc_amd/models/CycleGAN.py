@@ -14,7 +14,6 @@ is the same arithmetic and autograd would add the same gradients.
 Naming: netG_A maps domain A -> B and is judged by netD_A (on domain B); side 'A' below means that pair.
 """
 import copy
-import os
 import random
 from collections import OrderedDict
 
@@ -26,35 +25,20 @@ from .. import engine, ops
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from .Pix2Pix import HipAdam, MobileResnetGenerator, _patchgan_tree, _portable
-from ._resume import TrainingStateMixin
-from ._streams import TeacherStreamMixin
+from .Pix2Pix import MobileResnetGenerator, _patchgan_tree
+from ._base import ARCH_SLOTS, GANModelBase, _ChainWgrad
+from ._optim import HipAdam
 
 HEAVY_SPARSITY = ('model.1', 'model.4', 'model.19', 'model.22')      # models/CycleGAN.py:243, 548-569
 # CYCLE_FORK: the two sides of the model (generator A -> B with its discriminator, generator B -> A with its) are independent
 # chains of small kernels inside forward, backward_G, backward_D and the architecture step: side B runs on the auxiliary stream
-# beside side A, for the student and the online teacher alike, and the weight gradients stay on their chain's stream instead of
-# a side stream each: four chains on four HIP streams = the device's four hardware queues (with side streams the same forks
+# beside side A, for the student and the online teacher alike, and the weight gradients stay on their chain's stream
+# (_ChainWgrad) instead of a side stream each: four chains on four HIP streams = the device's four hardware queues (with side streams the same forks
 # make eight streams and lose: profiles/r4ag_cyclegan_streams.txt -- eager 32.2 -> 23.3 ms, replayed 30.0 -> 24.7).  The host
 # enqueues A then B as before, so everything that accumulates in launch order keeps the reference's order: same bits.
 # False: both sides in line, weight gradients on side streams (the serialized reference of
 # tests/test_replay_gpu.py::test_cyclegan_two_sides_fork_changes_nothing).
 CYCLE_FORK = True
-
-
-class _ChainWgrad:
-    """with CYCLE_FORK: weight-gradient launches stay on the stream of the chain that needs them (engine.OVERLAP_WGRAD off for
-    the duration of the step; restored afterwards: other model families of the process keep their side streams)"""
-
-    def __enter__(self):
-        self.prev = engine.OVERLAP_WGRAD
-        if CYCLE_FORK:
-            engine.OVERLAP_WGRAD = False
-        return self
-
-    def __exit__(self, *exc):
-        engine.OVERLAP_WGRAD = self.prev
-        return False
 
 
 class NLayerDiscriminator(nn.Module):
@@ -177,15 +161,16 @@ class _Half:
         self.out, self.g_out = full.out[lo:hi], full.g_out[lo:hi]
 
 
-class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
+class MobileCycleGANModel(GANModelBase):
+    NETS = ('G_A', 'G_B', 'D_A', 'D_B')
+    CFGS = ('cfg_AtoB', 'cfg_BtoA')
+    DISTILL_LOSSES = (('lambda_content', ['content_A', 'content_B']), ('lambda_gram', ['gram_A', 'gram_B']),
+                      ('lambda_L1', ['L1_A', 'L1_B']))
+    DISTILL_VISUALS = ('Tfake_A', 'Tfake_B')
 
     def __init__(self, opt, cfg_AtoB=None, cfg_BtoA=None):
         super().__init__()
-        self.opt = opt
-        if len(opt.gpu_ids) == 0 or not torch.cuda.is_available():
-            raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU and gpu_ids >= 0')
-        self.device = gdist.local_device(opt)
-        ops.lib()
+        self._init_device(opt)
         self.cfg_AtoB, self.cfg_BtoA = cfg_AtoB, cfg_BtoA
         self.loss_names = ['D_A', 'G_A', 'cycle_A', 'idt_A', 'D_B', 'G_B', 'cycle_B', 'idt_B']
         self.visual_names = ['real_A', 'fake_B', 'rec_A', 'idt_B', 'real_B', 'fake_A', 'rec_B', 'idt_A']
@@ -260,30 +245,17 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             self.schedulers.append(self.arch_scheduler)
         names = []
         for w in 'AB':
-            names += [n + w for n in ('G_', 'cycle_', 'idt_', 'D_real_', 'D_fake_', 'L1_', 'arch_fake_', 'arch_fake_real_',
-                                      'arch_real_', 'D_arch_diff_', 'D_arch_', 'teacher_diff_', 'arch_c_fr_', 'arch_c_f_',
-                                      's0_', 's1_', 's2_')]
-        self._slot = {n: i for i, n in enumerate(names)}
-        self._lossvec = torch.zeros(len(names) + 4, dtype=torch.float32, device=dev)
+            names += [n + '_' + w for n in ('G', 'cycle', 'idt', 'D_real', 'D_fake', 'L1') + tuple(ARCH_SLOTS.values())]
+        self._init_losses(names, size=len(names) + 4)
+        self._arch_slots = {w: {k: v + '_' + w for k, v in ARCH_SLOTS.items()} for w in 'AB'}      # a set per side
         self._dist_out = {w: torch.zeros((6, 2), dtype=torch.float32, device=dev) for w in 'AB'}
-        self._bufs = {}
-        self._ema_started = False
-        self._world = gdist.world_size()
         self._ctx = None
         self._nchw = {}
         self._dctx_last = {}
 
     # ---------------------------------------------------------------------------------------
-    def _l(self, name):
-        i = self._slot[name]
-        return self._lossvec[i:i + 1]
-
-    def refresh_weights(self):
-        for w in 'AB':
-            self.G[w].repack()
-            self.D[w].repack()
-            for t in self.T[w]:
-                t.repack()
+    def _engines(self):
+        return [e for w in 'AB' for e in [self.G[w], self.D[w]] + self.T[w]]
 
     def init_net(self):
         for net in (self.netG_A, self.netG_B, self.netD_A, self.netD_B):
@@ -419,23 +391,6 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self.D[w].forward(ctx, train=True)
         return ctx
 
-    def _buf(self, key, N, C, H, W):
-        key = (key, N, C, H, W)
-        if key not in self._bufs:
-            self._bufs[key] = ops.new_act(N, C, H, W, self.device)
-        return self._bufs[key]
-
-    def _dws(self, key, N, C, HW):
-        key = ('ws', key, N, C, HW)
-        need = ops.distill_workspace_bytes(N, C, HW)       # depends on the weight-gradient split plan (tuning options)
-        buf = self._bufs.get(key)
-        if buf is None or buf.numel() < need:
-            buf = self._bufs[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return buf
-
-    def _allreduce(self, optimizer):
-        gdist.all_reduce_grads(optimizer)
-
     # -- generators (:480-546) ------------------------------------------------------------------------
     def backward_G(self, ts=None):
         opt, mode, c = self.opt, self.opt.gan_mode, self._ctx
@@ -526,7 +481,7 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     # -- one iteration (:571-590) -------------------------------------------------------------------------
     def optimize_parameters(self):
-        with _ChainWgrad():
+        with _ChainWgrad(CYCLE_FORK):
             return self._optimize_parameters()
 
     def _optimize_parameters(self):
@@ -560,76 +515,36 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     # -- architecture step (:407-459, 592-600) ----------------------------------------------------------------
     def get_D_arch_diff(self, isTeacher=False):
-        mode = self.opt.gan_mode
         ctxs = {}
-        ema = isTeacher and self._ema_started          # one flag for both sides, as the reference tests side A only
 
         def side(w, fake, real):
             cf = self._d_forward(w, 'a_fake', self._ctx[fake].out)
             cr = self._d_forward(w, 'a_real', real)
-            ops.gan_loss(mode, cf.pred, False, True, self._l('arch_fake_' + w))
-            ops.gan_loss(mode, cf.pred, True, False, self._l('arch_fake_real_' + w))
-            ops.gan_loss(mode, cr.pred, True, True, self._l('arch_real_' + w))
-            out = self._l('teacher_diff_' + w if isTeacher else 'D_arch_diff_' + w)
-            if ema:
-                b = float(self.opt.ema_beta)
-                ops.scalar_op(1, self._l('arch_fake_real_' + w), self._l('arch_fake_' + w), out, c=out, k0=b, k1=1.0 - b)
-            else:
-                ops.scalar_op(0, self._l('arch_fake_real_' + w), self._l('arch_fake_' + w), out)
+            self._arch_diff(cf, cr, isTeacher, self._arch_slots[w])
             ctxs[w] = (cf, cr)
 
         self._two_sides(lambda: side('A', 'fake_B', self._B), lambda: side('B', 'fake_A', self._A))
-        self._ema_started = True
+        self._ema_started = True               # one flag for both sides, as the reference tests side A only
         return ctxs
 
     def backward_D_arch(self, ts=None):
-        T, mode = self.teacher_model, self.opt.gan_mode
+        T = self.teacher_model
         if not ts:
             T.get_D_arch_diff(isTeacher=True)
         ctxs = self.get_D_arch_diff(isTeacher=False)
         self._join(ts)
         for w in 'AB':
-            ops.scalar_op(2, T._l('teacher_diff_' + w), T._l('teacher_diff_' + w), self._l('teacher_diff_' + w), k0=0.0)
+            d = self._arch_slots[w]['teacher_diff']
+            ops.scalar_op(2, T._l(d), T._l(d), self._l(d), k0=0.0)
         self._mark_teacher_free()
         def side(w):
-            cf, cr = ctxs[w]
-            ops.arch_coeffs(self._l('arch_fake_real_' + w), self._l('arch_fake_' + w), self._l('arch_real_' + w),
-                            self._l('teacher_diff_' + w), self._l('D_arch_' + w), self._l('arch_c_fr_' + w),
-                            self._l('arch_c_f_' + w))
-            gp = self.D[w].grad_pred_buffer(cf)
-            ops.gan_loss(mode, cf.pred, True, False, self._l('s0_' + w), dpred=gp, weight_dev=self._l('arch_c_fr_' + w))
-            ops.gan_loss(mode, cf.pred, False, True, self._l('s1_' + w), dpred=gp, weight_dev=self._l('arch_c_f_' + w),
-                         dpred_accumulate=True)
-            self.D[w].backward(cf, wgrad=False, agrad=True, need_dx=False)
-            ops.gan_loss(mode, cr.pred, True, True, self._l('s2_' + w), dpred=gp, grad_weight=0.5)
-            self.D[w].backward(cr, wgrad=False, agrad=True, need_dx=False)
+            self._arch_backward(self.D[w], *ctxs[w], self._arch_slots[w], grad_weight=0.5)
 
         self._two_sides(lambda: side('A'), lambda: side('B'))
 
     def optimizer_netD_arch(self):
-        with _ChainWgrad():
+        with _ChainWgrad(CYCLE_FORK):
             return self._optimizer_netD_arch()
-
-    def _optimizer_netD_arch(self):
-        T = self.teacher_model
-
-        def teacher_part():
-            T.set_input(self.input)
-            T.forward()
-            if self._teacher_stream():
-                T.get_D_arch_diff(isTeacher=True)
-        ts = self._run_teacher(teacher_part)
-        self.forward()
-        self.optimizer_arch.zero_grad()
-        self.backward_D_arch(ts)
-        self._allreduce(self.optimizer_arch)
-        self.optimizer_arch.step()
-
-    def clipping_mask_alpha(self):
-        for net in (self.netD_A, self.netD_B):
-            for m in net.modules():
-                if isinstance(m, DifferentiableOP):
-                    m.clip_alpha()
 
     # -- bookkeeping surface ----------------------------------------------------------------------
     def print_sparse_info(self, logger):
@@ -640,54 +555,8 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
                     logger.info('%s %s sparsity ratio: %.2f' % (tag, name, float((mask == 0.0).sum()) / mask.numel()))
             logger.info('-----------------------------------')
 
-    def adaptive_ema_beta(self, epoch):
-        self.opt.ema_beta = 1.0 - epoch / (self.opt.n_epochs + self.opt.n_epochs_decay)
-
-    def update_learning_rate(self, epoch):
-        for s in self.schedulers:
-            s.step()
-        self.adaptive_ema_beta(epoch)
-        print('learning rate = %.7f' % self.optimizers[0].param_groups[0]['lr'])
-
-    def set_requires_grad(self, nets, requires_grad=False):
-        for net in (nets if isinstance(nets, list) else [nets]):
-            if net is not None:
-                for p in net.parameters():
-                    p.requires_grad = requires_grad
-
-    def save_models(self, epoch, save_dir, fid=None, isbest=False, direction='AtoB'):
-        if gdist.rank() != 0:
-            return
-        util.mkdirs(save_dir)
-        ckpt = {'G_A': _portable(self.netG_A.state_dict()), 'G_B': _portable(self.netG_B.state_dict()),
-                'D_A': _portable(self.netD_A.state_dict()), 'D_B': _portable(self.netD_B.state_dict()),
-                'epoch': epoch, 'cfg': (self.cfg_AtoB, self.cfg_BtoA), 'fid': fid}
-        name = 'model_best_%s.pth' % direction if isbest else 'model_%d.pth' % epoch
-        torch.save(ckpt, os.path.join(save_dir, name))
-
     def load_models(self, load_path, load_discriminator=True):
-        ckpt = torch.load(load_path, map_location='cpu')
-        self.netG_A.load_state_dict(ckpt['G_A'])
-        self.netG_B.load_state_dict(ckpt['G_B'])
-        if load_discriminator:
-            self.netD_A.load_state_dict(ckpt['D_A'])
-            self.netD_B.load_state_dict(ckpt['D_B'])
-        self.refresh_weights()
-        print('loading the model from %s' % load_path)
-
-    def model_train(self):
-        for net in (self.netG_A, self.netG_B, self.netD_A, self.netD_B):
-            net.train()
-
-    def model_eval(self):
-        for net in (self.netG_A, self.netG_B, self.netD_A, self.netD_B):
-            net.eval()
-
-    def get_current_visuals(self):
-        ret = OrderedDict()
-        for name in self.visual_names:
-            ret[name] = getattr(self, name)
-        return ret
+        self._load_checkpoint(load_path, load_discriminator)         # the 'fid' is not read back: returns nothing
 
     @property
     def Tfake_A(self):
@@ -712,7 +581,7 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             elif name.startswith('gram_'):
                 val = self.opt.lambda_gram * float(d[w][:, 0].sum())
             elif name.startswith('teacher_netD_'):
-                val = float(v[s['teacher_diff_' + name[len('teacher_netD_')]]])
+                val = float(v[s['teacher_D_arch_diff_' + name[len('teacher_netD_')]]])
             else:
                 val = float(v[s[name]])
             ret[name] = val
@@ -720,24 +589,11 @@ class MobileCycleGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             ret = gdist.mean_dict(ret, self.device)
         return ret
 
-    def init_distillation(self):
-        if self.distill:
-            if self.opt.lambda_content > 0.0:
-                self.loss_names += ['content_A', 'content_B']
-            if self.opt.lambda_gram > 0.0:
-                self.loss_names += ['gram_A', 'gram_B']
-            if self.opt.lambda_L1 > 0.0:
-                self.loss_names += ['L1_A', 'L1_B']
-            self.visual_names += ['Tfake_A', 'Tfake_B']
-
     def get_distillation_features(self, AorB='A'):
         """4 generator features of the G(real) pass + the 2 discriminator features of the last D call of the iteration
         (the pooled fake of the D step), as the reference's hooks end up holding them"""
         w = AorB
         return self._gfeatures(w, self._ctx['fake_B' if w == 'A' else 'fake_A']) + self.D[w].features(self._dctx_last[w])
-
-    def get_cfg(self):
-        return self.cfg_AtoB, self.cfg_BtoA
 
     # -- pruning (models/CycleGAN.py:794-900): integer logic on host copies of the weights -------------
     def max_min_conv_norm(self, netG):

@@ -25,8 +25,8 @@ from .. import _lib
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from ._resume import TrainingStateMixin
-from ._streams import TeacherStreamMixin
+from ._base import GANModelBase
+from ._optim import HipAdam             # stays importable as gcc_amd.models.Pix2Pix.HipAdam
 
 
 # ------------------------------------------------------------------------------------------------
@@ -213,97 +213,6 @@ class MaskNLayerDiscriminator(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-class HipAdam(torch.optim.Optimizer):
-    """torch.optim.Optimizer facade (so LambdaLR/StepLR schedulers work unchanged) whose step() is
-    one multi-tensor gcc_adam_step launch over a FlatParams group."""
-
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, l1=None, dup=(), layout=None):
-        """dup: parameters (members of params) the reference lists twice in this optimizer (SAGAN, SURVEY.md hazard
-        H5): torch's Adam then applies two sequential updates per step to them, with the same gradient and the step
-        counter advancing twice -- reproduced by a second plan over those tensors that is stepped twice."""
-        params = list(params)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
-        dev = params[0].device
-        self.flat = engine.FlatParams(params, dev, layout=layout)
-        self.reducer = None         # dist.GradReducer under data parallelism (Pix2PixModel sets it)
-        l1 = list(l1) if l1 is not None else [0.0] * len(params)
-        dup_ids = {id(p) for p in dup}
-        once = [i for i, p in enumerate(params) if id(p) not in dup_ids]
-        twice = [i for i, p in enumerate(params) if id(p) in dup_ids]
-        pick = lambda idx, seq: [seq[i] for i in idx]
-        self.plan = ops.AdamPlan(pick(once, params), pick(once, self.flat.grad_views), dev, l1=pick(once, l1)) if once else None
-        self.plan_dup = ops.AdamPlan(pick(twice, params), pick(twice, self.flat.grad_views), dev, l1=pick(twice, l1)) if twice else None
-        # optimizer order -> (plan, index in the plan): where parameter i's exp_avg / exp_avg_sq / step live
-        self._where = [None] * len(params)
-        for plan, idx in ((self.plan, once), (self.plan_dup, twice)):
-            for j, i in enumerate(idx):
-                self._where[i] = (plan, j)
-
-    def zero_grad(self, set_to_none=False):
-        self.flat.zero_grad()
-
-    def set_grad_scale(self, s):
-        for plan in (self.plan, self.plan_dup):
-            if plan is not None:
-                plan.set_grad_scale(s)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        g = self.param_groups[0]
-        if self.plan is not None:
-            self.plan.step(g['lr'], g['betas'], g['eps'])
-        if self.plan_dup is not None:
-            self.plan_dup.step(g['lr'], g['betas'], g['eps'])
-            self.plan_dup.step(g['lr'], g['betas'], g['eps'])
-
-    def state_dict(self):
-        """torch.optim.Adam's format: state[i] = {'step', 'exp_avg', 'exp_avg_sq'} per parameter in optimizer order (logical
-        NCHW-contiguous fp32 CPU tensors; none before the first step, as torch), param_groups packed as torch packs them.  A
-        parameter of plan_dup is one entry whose step advances twice per step(), as torch's Adam counts a twice-listed one.
-        Reads the device moments: the caller orders this behind the last step (a device synchronize)."""
-        packed = super().state_dict()
-        state = {}
-        for i, (plan, j) in enumerate(self._where):
-            if plan.step_count > 0:
-                state[i] = {'step': torch.tensor(float(plan.step_count)),
-                            'exp_avg': plan.m[j].detach().to('cpu').contiguous(),
-                            'exp_avg_sq': plan.v[j].detach().to('cpu').contiguous()}
-        return {'state': state, 'param_groups': packed['param_groups']}
-
-    def load_state_dict(self, state_dict):
-        """the inverse of state_dict(), in place: the moments are COPIED into the existing AdamPlan.m / v tensors (their device
-        pointers are baked into the plans' descriptor lists and into recorded replays) and step_count is restored"""
-        groups = state_dict['param_groups']
-        if len(groups) != 1 or len(groups[0]['params']) != len(self._where):
-            raise GccError('optimizer state holds %s parameters, this optimizer has %d'
-                           % ([len(g['params']) for g in groups], len(self._where)))
-        state = state_dict['state']
-        steps = {}
-        for i, (plan, j) in enumerate(self._where):
-            s = state.get(i, state.get(str(i)))
-            if s is None:
-                steps.setdefault(id(plan), set()).add(0)
-                continue
-            steps.setdefault(id(plan), set()).add(int(float(s['step'])))
-            for dst, key in ((plan.m[j], 'exp_avg'), (plan.v[j], 'exp_avg_sq')):
-                src = s[key]
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise GccError('optimizer state of parameter %d: %s is %s, the parameter is %s'
-                                   % (i, key, tuple(src.shape), tuple(dst.shape)))
-                dst.copy_(src.to(dst.dtype))
-        for plan in (self.plan, self.plan_dup):
-            if plan is None:
-                continue
-            got = steps.get(id(plan), {0})
-            if len(got) != 1:
-                raise GccError('optimizer state: the parameters of one group disagree on their step count (%s)' % sorted(got))
-            plan.step_count = got.pop()
-            if plan.step_count == 0:
-                for t in plan.m + plan.v:
-                    t.zero_()
-        self.param_groups[0].update({k: v for k, v in groups[0].items() if k != 'params'})
-
-
 # Stream forks of the schedule.  Each is the product's path; False is the serialized form that
 # tests/test_replay_gpu.py::test_pix2pix_stream_forks_change_nothing holds it to, bit for bit.
 # DISTILL_FORK: the distillation terms on the generator's features run on the auxiliary stream beside the teacher
@@ -334,7 +243,10 @@ def _drain(gen, stream):
 
 
 # ------------------------------------------------------------------------------------------------
-class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
+class Pix2PixModel(GANModelBase):
+    DISTILL_LOSSES = GANModelBase.DISTILL_LOSSES[:2]             # no 'L1' entry: G_L1 is always logged
+    DISTILL_VISUALS = ('Tfake_B',)
+    LR_REPORT = 'learning rate = %(lr).7f\tema beta = %(ema_beta).7f'
 
     @property
     def replay_supported(self):
@@ -349,11 +261,7 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def __init__(self, opt, filter_cfgs=None, channel_cfgs=None):
         super().__init__()
-        self.opt = opt
-        if len(opt.gpu_ids) == 0 or not torch.cuda.is_available():
-            raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU and gpu_ids >= 0')
-        self.device = gdist.local_device(opt)
-        ops.lib()                      # fail loudly here if libgcc_hip.so is not built
+        self._init_device(opt)
         self.filter_cfgs, self.channel_cfgs = filter_cfgs, channel_cfgs
         self.loss_names = ['G_GAN', 'G_L1', 'D_real', 'D_fake']
         self.visual_names = ['real_A', 'fake_B', 'real_B']
@@ -455,16 +363,10 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self.schedulers = [util.get_scheduler(o, opt) for o in self.optimizers]
         if opt.darts_discriminator and opt.arch_lr_step:
             self.schedulers.append(self.arch_scheduler)
-        # device scalars: every loss of the iteration lives in one fp32 vector (read on demand)
-        self._lossvec = torch.zeros(32, dtype=torch.float32, device=dev)
-        self._slot = {n: i for i, n in enumerate(
-            ['G_GAN', 'G_L1', 'D_real', 'D_fake', 'D_arch_fake', 'D_arch_fake_real', 'D_arch_real', 'D_arch_diff',
-             'D_arch', 'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0', 'scratch1', 'scratch2', 'ema_prev'])}
+        self._init_losses(['G_GAN', 'G_L1', 'D_real', 'D_fake', 'D_arch_fake', 'D_arch_fake_real', 'D_arch_real', 'D_arch_diff',
+                           'D_arch', 'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0', 'scratch1', 'scratch2', 'ema_prev'])
         self._dist_out = torch.zeros((6, 2), dtype=torch.float32, device=dev)
-        self._dist_ws = {}
         self._fake_nchw = None
-        self._ema_started = False
-        self._world = gdist.world_size()
         if self._world > 1:
             engine.OVERLAP_WGRAD = engine.overlap_wgrad_default(self._world)
         self._defer_G_update = False
@@ -472,18 +374,13 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self._comm_group = None        # gdist.chain_group('teacher') once this model runs as an online teacher on its own stream
 
     # ---------------------------------------------------------------------------------------
-    def _l(self, name):
-        i = self._slot[name]
-        return self._lossvec[i:i + 1]
+    def _engines(self):
+        return [self.G, self.D] + self.T
 
     def refresh_weights(self):
-        """re-derive the bf16 weight packings from the fp32 masters (after init / load / Adam)"""
         self._g_generation = getattr(self, '_g_generation', 0) + 1
-        self.G.repack()
-        self.D.repack()
+        super().refresh_weights()
         self.D.mask_dirty = True
-        for t in self.T:
-            t.repack()
 
     def init_net(self):
         self.netG.to(self.device)
@@ -759,17 +656,9 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     def _tbuf(self, i, N, C, H, W):
         key = ('t', i, N, C, H, W)
-        if key not in self._dist_ws:
-            self._dist_ws[key] = (ops.new_act(N, C, H, W, self.device), ops.new_act(N, C, H, W, self.device))
-        return self._dist_ws[key]
-
-    def _dws(self, i, N, C, HW):
-        key = ('w', i, N, C, HW)
-        need = ops.distill_workspace_bytes(N, C, HW)       # depends on the weight-gradient split plan (tuning options)
-        buf = self._dist_ws.get(key)
-        if buf is None or buf.numel() < need:
-            buf = self._dist_ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return buf
+        if key not in self._bufs:
+            self._bufs[key] = (ops.new_act(N, C, H, W, self.device), ops.new_act(N, C, H, W, self.device))
+        return self._bufs[key]
 
     # -- one iteration (models/Pix2Pix.py:565-583) ----------------------------------------------------
     def optimize_parameters(self):
@@ -1018,66 +907,13 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         if flat is not None:
             ops.clamp_(flat.values, 0.0, 1.0)          # every alpha lives in the arch optimizer's flat buffer: one launch
         else:
-            for m in self.netD.modules():
-                if isinstance(m, DifferentiableOP):
-                    m.clip_alpha()
+            super().clipping_mask_alpha()
         self.D.mask_dirty = True
 
     # -- bookkeeping surface ----------------------------------------------------------------------
-    def print_sparse_info(self, logger):
-        for name, m in self.named_modules():
-            if isinstance(m, DifferentiableOP):
-                mask = m.get_current_mask()
-                logger.info('%s sparsity ratio: %.2f' % (name, float((mask == 0.0).sum()) / mask.numel()))
-
-    def adaptive_ema_beta(self, epoch):
-        self.opt.ema_beta = 1.0 - epoch / (self.opt.n_epochs + self.opt.n_epochs_decay)
-
-    def update_learning_rate(self, epoch):
-        for s in self.schedulers:
-            s.step()
-        self.adaptive_ema_beta(epoch)
-        lr = self.optimizers[0].param_groups[0]['lr']
-        print('learning rate = %.7f\tema beta = %.7f' % (lr, self.opt.ema_beta))
-
-    def set_requires_grad(self, nets, requires_grad=False):
-        for net in (nets if isinstance(nets, list) else [nets]):
-            if net is not None:
-                for p in net.parameters():
-                    p.requires_grad = requires_grad
-
     def save_models(self, epoch, save_dir, fid=None, isbest=False, direction='AtoB'):
         self.finish_G_update()
-        if gdist.rank() != 0:
-            return
-        util.mkdirs(save_dir)
-        ckpt = {'G': _portable(self.netG.state_dict()), 'D': _portable(self.netD.state_dict()), 'epoch': epoch,
-                'cfg': (self.filter_cfgs, self.channel_cfgs), 'fid': fid}
-        name = 'model_best_%s.pth' % direction if isbest else 'model_%d.pth' % epoch
-        torch.save(ckpt, os.path.join(save_dir, name))
-
-    def load_models(self, load_path, load_discriminator=True):
-        ckpt = torch.load(load_path, map_location='cpu')
-        self.netG.load_state_dict(ckpt['G'])
-        if load_discriminator:
-            self.netD.load_state_dict(ckpt['D'])
-        self.refresh_weights()
-        print('loading the model from %s' % load_path)
-        return ckpt['fid'], float('inf')
-
-    def model_train(self):
-        self.netG.train()
-        self.netD.train()
-
-    def model_eval(self):
-        self.netG.eval()
-        self.netD.eval()
-
-    def get_current_visuals(self):
-        ret = OrderedDict()
-        for name in self.visual_names:
-            ret[name] = getattr(self, name)
-        return ret
+        super().save_models(epoch, save_dir, fid, isbest, direction)
 
     def get_current_losses(self):
         """host read of the device loss scalars (the only sync of the iteration; print_freq cadence)"""
@@ -1096,21 +932,10 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             ret = gdist.mean_dict(ret, self.device)
         return ret
 
-    def init_distillation(self):
-        if self.distill:
-            if self.opt.lambda_content > 0.0:
-                self.loss_names.append('content')
-            if self.opt.lambda_gram > 0.0:
-                self.loss_names.append('gram')
-            self.visual_names.append('Tfake_B')
-
     def get_distillation_features(self):
         """4 generator features (hooked modules of :366-369) + 2 discriminator features, as the
         tensors the reference's hooks end up holding (post in-place activation, hazard H1)"""
         return self.G.features(self._gctx) + self.D.features(self._dctx_g)
-
-    def get_cfg(self):
-        return self.filter_cfgs, self.channel_cfgs
 
     # -- pruning cfgs (integer logic on host copies of the weights; models/Pix2Pix.py:742-952) -----------
     def _bn_sd(self):
@@ -1155,8 +980,3 @@ class Pix2PixModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         if self.opt.backbone == 'resnet':
             return prune_util.max_min_conv_norm_resnet(self.netG, 'union')
         return prune_util.max_min_conv_norm_unet(self.netG)
-
-
-def _portable(sd):
-    """NCHW-contiguous fp32 CPU copies, as a reference checkpoint stores them"""
-    return OrderedDict((k, v.detach().to('cpu').contiguous()) for k, v in sd.items())

@@ -17,7 +17,6 @@ Reference behaviour that is reproduced on purpose (SURVEY.md section 8 hazards):
   * Adam betas (0, 0.9); the discriminator's learning rate is 4x; only the arch scheduler steps.
 """
 import copy
-import os
 from collections import OrderedDict
 
 import torch
@@ -29,28 +28,12 @@ from .. import engine, ops
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from .Pix2Pix import HipAdam, _portable
-from ._resume import TrainingStateMixin
-from ._streams import TeacherStreamMixin
+from ._base import GANModelBase, _ChainWgrad
+from ._optim import HipAdam
 
 
 def l2normalize(v, eps=1e-12):
     return v / (v.norm() + eps)
-
-
-class _ChainWgrad:
-    """the weight-gradient launches stay on the stream of the chain that needs them instead of a side stream: at 64 x 64 every
-    kernel is a few microseconds and the two event operations of a side-stream fork cost more than the overlap returns (eager
-    10.6 -> 8.8 ms, replayed 9.3 -> 8.4: profiles/r4ak_chain_wgrad.txt; SRGAN measured the other way round)"""
-
-    def __enter__(self):
-        self.prev = engine.OVERLAP_WGRAD
-        engine.OVERLAP_WGRAD = False
-        return self
-
-    def __exit__(self, *exc):
-        engine.OVERLAP_WGRAD = self.prev
-        return False
 
 
 class SpectralNorm(nn.Module):
@@ -155,15 +138,12 @@ def _is_dup(name):
     return ('.module.' in name) or ('_conv.' in name)
 
 
-class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
+class SAGANModel(GANModelBase):
+    DISTILL_VISUALS = ('Tfake_img',)
 
     def __init__(self, opt, filter_cfgs=None, channel_cfgs=None):
         super().__init__()
-        self.opt = opt
-        if len(opt.gpu_ids) == 0 or not torch.cuda.is_available():
-            raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU and gpu_ids >= 0')
-        self.device = gdist.local_device(opt)
-        ops.lib()
+        self._init_device(opt)
         self.filter_cfgs, self.channel_cfgs = filter_cfgs, channel_cfgs
         self.loss_names = ['G_GAN', 'D_real', 'D_fake']
         self.visual_names = ['fake_img', 'real_img']
@@ -216,32 +196,21 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
                 arch_opt.lr_policy = 'step'
                 arch_opt.lr_decay_iters = 40
                 self.arch_scheduler = util.get_scheduler(self.optimizer_arch, arch_opt)
+        self.schedulers = [self.arch_scheduler] if hasattr(self, 'arch_scheduler') else []      # only the arch scheduler steps
 
         # ---- engines
         self.G = engine.SaganGeneratorEngine(self.netG, dev)
         self.D = engine.SaganDiscriminatorEngine(self.netD, masked, 0.5, dev)
         self.T = [engine.ConvOp(t.weight, None, 1, 1, 0, False) for t in self.transform_convs]
         self.refresh_weights()
-        self._lossvec = torch.zeros(32, dtype=torch.float32, device=dev)
-        self._slot = {n: i for i, n in enumerate(
-            ['G_GAN', 'D_real', 'D_fake', 'L1', 'D_arch_fake', 'D_arch_fake_real', 'D_arch_real', 'D_arch_diff', 'D_arch',
-             'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0', 'scratch1', 'scratch2'])}
+        self._init_losses(['G_GAN', 'D_real', 'D_fake', 'L1', 'D_arch_fake', 'D_arch_fake_real', 'D_arch_real', 'D_arch_diff',
+                           'D_arch', 'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0', 'scratch1', 'scratch2'])
         self._dist_out = torch.zeros((4, 2), dtype=torch.float32, device=dev)
-        self._bufs = {}
         self._nchw = None
-        self._ema_started = False
-        self._world = gdist.world_size()
 
     # ---------------------------------------------------------------------------------------
-    def _l(self, name):
-        i = self._slot[name]
-        return self._lossvec[i:i + 1]
-
-    def refresh_weights(self):
-        self.G.repack()
-        self.D.repack()
-        for t in self.T:
-            t.repack()
+    def _engines(self):
+        return [self.G, self.D] + self.T
 
     def init_net(self):
         for net in (self.netG, self.netD):
@@ -304,23 +273,6 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self.D.forward(ctx)
         return ctx
 
-    def _buf(self, key, N, C, H, W):
-        key = (key, N, C, H, W)
-        if key not in self._bufs:
-            self._bufs[key] = ops.new_act(N, C, H, W, self.device)
-        return self._bufs[key]
-
-    def _dws(self, i, N, C, HW):
-        key = ('ws', i, N, C, HW)
-        need = ops.distill_workspace_bytes(N, C, HW)       # depends on the weight-gradient split plan (tuning options)
-        buf = self._bufs.get(key)
-        if buf is None or buf.numel() < need:
-            buf = self._bufs[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return buf
-
-    def _allreduce(self, optimizer):
-        gdist.all_reduce_grads(optimizer)
-
     # -- D step (:370-381): real first, then the detached fake; the two terms are summed without the 1/2 ----------
     def backward_D(self):
         mode = self.opt.gan_mode
@@ -345,32 +297,10 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
         def distill_terms():
             T = self.teacher_model
-            N = gc.N
             self._join(ts)                                       # first read of the teacher's state (on this chain's stream)
             ct = T._d_forward('on_student', self._fake)          # teacher D (frozen) on the student's fake: not detached
-            feats = self.G.features(gc) + T.D.features(ct)
-            tf, dtf = [], []
-            for i in range(2):
-                f = feats[i]
-                buf = self._buf(('tf', i), N, self.T[i].rows, f.shape[2], f.shape[3])
-                self.T[i].forward(f, buf)
-                tf.append(buf)
-            tf += feats[2:]
-            for i in range(4):
-                dtf.append(self._buf(('dtf', i), N, tf[i].shape[1], tf[i].shape[2], tf[i].shape[3]))
-                ws = self._dws(i, N, tf[i].shape[1], tf[i].shape[2] * tf[i].shape[3])
-                t = self.target_distillation_features[i]
-                ops.distill_fwd(tf[i], t, self._dist_out[i], ws)
-                ops.distill_bwd(tf[i], t, opt.lambda_gram, opt.lambda_content, dtf[i], ws)
-            gf = []
-            for i in range(2):
-                self.T[i].backward_weight(feats[i], dtf[i])
-                gbuf = self._buf(('gf', i), N, feats[i].shape[1], feats[i].shape[2], feats[i].shape[3])
-                self.T[i].backward_data(dtf[i], gbuf)
-                gf.append(gbuf)
-            ops.SideStream.get(self.device).join()
-            dx2 = T.D.backward(ct, has_pred_grad=False, g_feat=[dtf[2], dtf[3]], wgrad=False, need_dx=True)
-            tmp = self._buf('l1', N, 3, 64, 64)
+            gf, dx2 = self._distill_terms(gc, ct, 2)
+            tmp = self._buf('l1', gc.N, 3, 64, 64)
             ops.l1_loss(self._fake, T._fake, self._l('L1'), weight=opt.lambda_L1, da=tmp)
             return gf, dx2, tmp
 
@@ -387,6 +317,9 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self.G.backward(gc, g_feat=g_feat, wgrad=True)
 
     # -- one iteration (:508-528) -----------------------------------------------------------------------------
+    # the weight-gradient launches stay on the stream of the chain that needs them instead of a side stream (_ChainWgrad): at
+    # 64 x 64 every kernel is a few microseconds and the two event operations of a side-stream fork cost more than the overlap
+    # returns (eager 10.6 -> 8.8 ms, replayed 9.3 -> 8.4: profiles/r4ak_chain_wgrad.txt; SRGAN measured the other way round)
     def optimize_parameters(self):
         with _ChainWgrad():
             return self._optimize_parameters()
@@ -417,118 +350,17 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     # -- architecture step (:383-413, 530-538) -----------------------------------------------------------------
     def get_D_arch_diff(self, isTeacher=False):
-        mode = self.opt.gan_mode
         cf = self._d_forward('a_fake', self._fake)
         cr = self._d_forward('a_real', self._real)
-        ops.gan_loss(mode, cf.pred, False, True, self._l('D_arch_fake'))
-        ops.gan_loss(mode, cf.pred, True, False, self._l('D_arch_fake_real'))
-        ops.gan_loss(mode, cr.pred, True, True, self._l('D_arch_real'))
-        out = self._l('teacher_D_arch_diff' if isTeacher else 'D_arch_diff')
-        if isTeacher and self._ema_started:
-            b = float(self.opt.ema_beta)
-            ops.scalar_op(1, self._l('D_arch_fake_real'), self._l('D_arch_fake'), out, c=out, k0=b, k1=1.0 - b)
-        else:
-            ops.scalar_op(0, self._l('D_arch_fake_real'), self._l('D_arch_fake'), out)
+        self._arch_diff(cf, cr, isTeacher)
         self._ema_started = True
         return cf, cr
-
-    def backward_D_arch(self, ts=None):
-        T, mode = self.teacher_model, self.opt.gan_mode
-        if not ts:
-            T.get_D_arch_diff(isTeacher=True)
-        cf, cr = self.get_D_arch_diff(isTeacher=False)
-        self._join(ts)
-        ops.scalar_op(2, T._l('teacher_D_arch_diff'), T._l('teacher_D_arch_diff'), self._l('teacher_D_arch_diff'), k0=0.0)
-        self._mark_teacher_free()
-        # loss_D_arch = |d_S - d_T| + L_real + L_fake  (no 1/2 here, :388-389)
-        ops.arch_coeffs(self._l('D_arch_fake_real'), self._l('D_arch_fake'), self._l('D_arch_real'),
-                        self._l('teacher_D_arch_diff'), self._l('D_arch'), self._l('arch_c_fr'), self._l('arch_c_f'), weight=1.0)
-        gp = self.D.grad_pred_buffer(cf)
-        ops.gan_loss(mode, cf.pred, True, False, self._l('scratch0'), dpred=gp, weight_dev=self._l('arch_c_fr'))
-        ops.gan_loss(mode, cf.pred, False, True, self._l('scratch1'), dpred=gp, weight_dev=self._l('arch_c_f'),
-                     dpred_accumulate=True)
-        self.D.backward(cf, wgrad=False, agrad=True, need_dx=False)
-        ops.gan_loss(mode, cr.pred, True, True, self._l('scratch2'), dpred=gp)
-        self.D.backward(cr, wgrad=False, agrad=True, need_dx=False)
 
     def optimizer_netD_arch(self):
         with _ChainWgrad():
             return self._optimizer_netD_arch()
 
-    def _optimizer_netD_arch(self):
-        T = self.teacher_model
-
-        def teacher_part():
-            T.set_input(self.input)
-            T.forward()
-            if self._teacher_stream():
-                T.get_D_arch_diff(isTeacher=True)
-        ts = self._run_teacher(teacher_part)
-        self.forward()
-        self.optimizer_arch.zero_grad()
-        self.backward_D_arch(ts)
-        self._allreduce(self.optimizer_arch)
-        self.optimizer_arch.step()
-
-    def clipping_mask_alpha(self):
-        for m in self.netD.modules():
-            if isinstance(m, DifferentiableOP):
-                m.clip_alpha()
-
     # -- bookkeeping surface ----------------------------------------------------------------------
-    def print_sparse_info(self, logger):
-        for name, m in self.named_modules():
-            if isinstance(m, DifferentiableOP):
-                mask = m.get_current_mask()
-                logger.info('%s sparsity ratio: %.2f' % (name, float((mask == 0.0).sum()) / mask.numel()))
-
-    def adaptive_ema_beta(self, epoch):
-        self.opt.ema_beta = 1.0 - epoch / (self.opt.n_epochs + self.opt.n_epochs_decay)
-
-    def update_learning_rate(self, epoch):
-        if self.opt.arch_lr_step and hasattr(self, 'arch_scheduler'):
-            self.arch_scheduler.step()
-        self.adaptive_ema_beta(epoch)
-        print('learning rate = %.7f' % self.optimizer_G.param_groups[0]['lr'])
-
-    def set_requires_grad(self, nets, requires_grad=False):
-        for net in (nets if isinstance(nets, list) else [nets]):
-            if net is not None:
-                for p in net.parameters():
-                    p.requires_grad = requires_grad
-
-    def save_models(self, epoch, save_dir, fid=None, isbest=False, direction='AtoB'):
-        if gdist.rank() != 0:
-            return
-        util.mkdirs(save_dir)
-        ckpt = {'G': _portable(self.netG.state_dict()), 'D': _portable(self.netD.state_dict()), 'epoch': epoch,
-                'cfg': (self.filter_cfgs, self.channel_cfgs), 'fid': fid}
-        name = 'model_best_%s.pth' % direction if isbest else 'model_%d.pth' % epoch
-        torch.save(ckpt, os.path.join(save_dir, name))
-
-    def load_models(self, load_path, load_discriminator=True):
-        ckpt = torch.load(load_path, map_location='cpu')
-        self.netG.load_state_dict(ckpt['G'])
-        if load_discriminator:
-            self.netD.load_state_dict(ckpt['D'])
-        self.refresh_weights()
-        print('loading the model from %s' % load_path)
-        return ckpt['fid'], float('inf')
-
-    def model_train(self):
-        self.netG.train()
-        self.netD.train()
-
-    def model_eval(self):
-        self.netG.eval()
-        self.netD.eval()
-
-    def get_current_visuals(self):
-        ret = OrderedDict()
-        for name in self.visual_names:
-            ret[name] = getattr(self, name)
-        return ret
-
     def get_current_losses(self):
         v = self._lossvec.cpu()
         d = self._dist_out.cpu()
@@ -550,22 +382,9 @@ class SAGANModel(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             ret = gdist.mean_dict(ret, self.device)
         return ret
 
-    def init_distillation(self):
-        if self.distill:
-            if self.opt.lambda_content > 0.0:
-                self.loss_names.append('content')
-            if self.opt.lambda_gram > 0.0:
-                self.loss_names.append('gram')
-            if self.opt.lambda_L1 > 0.0:
-                self.loss_names.append('L1')
-            self.visual_names.append('Tfake_img')
-
     def get_distillation_features(self):
         """2 generator features ('l2', 'attn2') + the 2 discriminator features of the last D call of the iteration"""
         return self.G.features(self._gctx) + self.D.features(self._dctx_g)
-
-    def get_cfg(self):
-        return self.filter_cfgs, self.channel_cfgs
 
     # -- pruning (:661-740): BatchNorm-scale counts per generator layer ---------------------------------------------
     def max_min_bn_scale(self):

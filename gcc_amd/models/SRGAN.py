@@ -26,9 +26,8 @@ from .. import engine, ops
 from .._lib import GccError, check
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from .Pix2Pix import HipAdam, _portable
-from ._resume import TrainingStateMixin
-from ._streams import TeacherStreamMixin
+from ._base import GANModelBase
+from ._optim import HipAdam
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -155,15 +154,13 @@ class TruncatedVGG19(nn.Module):
         self.truncated_vgg19.load_state_dict({k: sd['features.' + k] for k in own})
 
 
-class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
+class SRGAN(GANModelBase):
+    METRIC = 'psnr'
+    DISTILL_VISUALS = ('Tfake_hr',)
 
     def __init__(self, opt, filter_cfgs=None, channel_cfgs=None, vgg_widths=None):
         super().__init__()
-        self.opt = opt
-        if len(opt.gpu_ids) == 0 or not torch.cuda.is_available():
-            raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU and gpu_ids >= 0')
-        self.device = gdist.local_device(opt)
-        ops.lib()
+        self._init_device(opt)
         self.filter_cfgs, self.channel_cfgs = filter_cfgs, channel_cfgs
         self.current_epoch = 0
         self.optimizers = []
@@ -252,26 +249,15 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         s = torch.tensor([1.0 / (2.0 * sd) for sd in IMAGENET_STD], dtype=torch.float32, device=dev)
         t = torch.tensor([(0.5 - m) / sd for m, sd in zip(IMAGENET_MEAN, IMAGENET_STD)], dtype=torch.float32, device=dev)
         self._norm_scale, self._norm_shift, self._zero3 = s, t, torch.zeros(3, dtype=torch.float32, device=dev)
-        self._lossvec = torch.zeros(32, dtype=torch.float32, device=dev)
-        self._slot = {n: i for i, n in enumerate(
-            ['G_GAN', 'D_real', 'D_fake', 'mse_content', 'perceptual', 'L1', 'D_arch_fake', 'D_arch_fake_real', 'D_arch_real',
-             'D_arch_diff', 'D_arch', 'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0', 'scratch1', 'scratch2'])}
+        self._init_losses(['G_GAN', 'D_real', 'D_fake', 'mse_content', 'perceptual', 'L1', 'D_arch_fake', 'D_arch_fake_real',
+                           'D_arch_real', 'D_arch_diff', 'D_arch', 'teacher_D_arch_diff', 'arch_c_fr', 'arch_c_f', 'scratch0',
+                           'scratch1', 'scratch2'])
         self._dist_out = torch.zeros((6, 2), dtype=torch.float32, device=dev)
-        self._bufs = {}
         self._nchw = {}
-        self._ema_started = False
-        self._world = gdist.world_size()
 
     # ---------------------------------------------------------------------------------------
-    def _l(self, name):
-        i = self._slot[name]
-        return self._lossvec[i:i + 1]
-
-    def refresh_weights(self):
-        self.G.repack()
-        self.D.repack()
-        for t in self.T:
-            t.repack()
+    def _engines(self):
+        return [self.G, self.D] + self.T
 
     def init_net(self):
         for net in (self.netG, self.netD, self.truncated_vgg19):
@@ -285,20 +271,6 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         gdist.broadcast_module(self.netD)
 
     # ---------------------------------------------------------------------------------------
-    def _buf(self, key, N, C, H, W):
-        key = (key, N, C, H, W)
-        if key not in self._bufs:
-            self._bufs[key] = ops.new_act(N, C, H, W, self.device)
-        return self._bufs[key]
-
-    def _dws(self, i, N, C, HW):
-        key = ('ws', i, N, C, HW)
-        need = ops.distill_workspace_bytes(N, C, HW)       # depends on the weight-gradient split plan (tuning options)
-        buf = self._bufs.get(key)
-        if buf is None or buf.numel() < need:
-            buf = self._bufs[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return buf
-
     def set_input(self, input):
         self.input = input
         self._note_input(input)
@@ -354,9 +326,6 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
         self.D.forward(ctx, train=True)
         return ctx
 
-    def _allreduce(self, optimizer):
-        gdist.all_reduce_grads(optimizer)
-
     # -- generator (:446-480) ---------------------------------------------------------------------------------------
     def backward_G(self, ts=None):
         opt, mode, gc = self.opt, self.opt.gan_mode, self._gctx
@@ -399,28 +368,7 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
             T = self.teacher_model
             self._join(ts)                                       # first read of the teacher's state
             ct = T._d_forward('on_student', self._fake_n)
-            feats = self.G.features(gc) + T.D.features(ct)
-            tf, dtf = [], []
-            for i in range(4):
-                f = feats[i]
-                buf = self._buf(('tf', i), N, self.T[i].rows, f.shape[2], f.shape[3])
-                self.T[i].forward(f, buf)
-                tf.append(buf)
-            tf += feats[4:]
-            for i in range(6):
-                dtf.append(self._buf(('dtf', i), N, tf[i].shape[1], tf[i].shape[2], tf[i].shape[3]))
-                ws = self._dws(i, N, tf[i].shape[1], tf[i].shape[2] * tf[i].shape[3])
-                t = self.target_distillation_features[i]
-                ops.distill_fwd(tf[i], t, self._dist_out[i], ws)
-                ops.distill_bwd(tf[i], t, opt.lambda_gram, opt.lambda_content, dtf[i], ws)
-            g_feat = []
-            for i in range(4):
-                self.T[i].backward_weight(feats[i], dtf[i])
-                gbuf = self._buf(('gf', i), N, feats[i].shape[1], feats[i].shape[2], feats[i].shape[3])
-                self.T[i].backward_data(dtf[i], gbuf)
-                g_feat.append(gbuf)
-            ops.SideStream.get(self.device).join()
-            dx2 = T.D.backward(ct, has_pred_grad=False, g_feat=[dtf[4], dtf[5]], wgrad=False, need_dx=True)
+            g_feat, dx2 = self._distill_terms(gc, ct, 4)
             ops.nhwc_add(dx2, 0, g_n, 0, 3)
             tmp = self._buf('l1', N, 3, H, W)
             ops.l1_loss(self._fake_n, T._fake_n, self._l('L1'), weight=opt.lambda_L1, da=tmp)
@@ -495,114 +443,17 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
 
     # -- architecture step (:390-424, 495-503) -------------------------------------------------------------------------
     def get_D_arch_diff(self, isTeacher=False):
-        mode = self.opt.gan_mode
         self._normalise()
         cf = self._d_forward('a_fake', self._fake_n)
         cr = self._d_forward('a_real', self._hr_n)
-        ops.gan_loss(mode, cf.pred, False, True, self._l('D_arch_fake'))
-        ops.gan_loss(mode, cf.pred, True, False, self._l('D_arch_fake_real'))
-        ops.gan_loss(mode, cr.pred, True, True, self._l('D_arch_real'))
-        out = self._l('teacher_D_arch_diff' if isTeacher else 'D_arch_diff')
-        if isTeacher and self._ema_started:
-            b = float(self.opt.ema_beta)
-            ops.scalar_op(1, self._l('D_arch_fake_real'), self._l('D_arch_fake'), out, c=out, k0=b, k1=1.0 - b)
-        else:
-            ops.scalar_op(0, self._l('D_arch_fake_real'), self._l('D_arch_fake'), out)
+        self._arch_diff(cf, cr, isTeacher)
         self._ema_started = True
         return cf, cr
 
-    def backward_D_arch(self, ts=None):
-        T, mode = self.teacher_model, self.opt.gan_mode
-        if not ts:
-            T.get_D_arch_diff(isTeacher=True)
-        cf, cr = self.get_D_arch_diff(isTeacher=False)
-        self._join(ts)
-        ops.scalar_op(2, T._l('teacher_D_arch_diff'), T._l('teacher_D_arch_diff'), self._l('teacher_D_arch_diff'), k0=0.0)
-        self._mark_teacher_free()
-        ops.arch_coeffs(self._l('D_arch_fake_real'), self._l('D_arch_fake'), self._l('D_arch_real'),
-                        self._l('teacher_D_arch_diff'), self._l('D_arch'), self._l('arch_c_fr'), self._l('arch_c_f'), weight=1.0)
-        gp = self.D.grad_pred_buffer(cf)
-        ops.gan_loss(mode, cf.pred, True, False, self._l('scratch0'), dpred=gp, weight_dev=self._l('arch_c_fr'))
-        ops.gan_loss(mode, cf.pred, False, True, self._l('scratch1'), dpred=gp, weight_dev=self._l('arch_c_f'),
-                     dpred_accumulate=True)
-        self.D.backward(cf, wgrad=False, agrad=True, need_dx=False)
-        ops.gan_loss(mode, cr.pred, True, True, self._l('scratch2'), dpred=gp)
-        self.D.backward(cr, wgrad=False, agrad=True, need_dx=False)
-
-    def optimizer_netD_arch(self):
-        T = self.teacher_model
-
-        def teacher_part():
-            T.set_input(self.input)
-            T.forward()
-            if self._teacher_stream():
-                T.get_D_arch_diff(isTeacher=True)
-        ts = self._run_teacher(teacher_part)
-        self.forward()
-        self.optimizer_arch.zero_grad()
-        self.backward_D_arch(ts)
-        self._allreduce(self.optimizer_arch)
-        self.optimizer_arch.step()
-
-    def clipping_mask_alpha(self):
-        for m in self.netD.modules():
-            if isinstance(m, DifferentiableOP):
-                m.clip_alpha()
-
     # -- bookkeeping surface ----------------------------------------------------------------------
-    def print_sparse_info(self, logger):
-        for name, m in self.named_modules():
-            if isinstance(m, DifferentiableOP):
-                mask = m.get_current_mask()
-                logger.info('%s sparsity ratio: %.2f' % (name, float((mask == 0.0).sum()) / mask.numel()))
-
-    def adaptive_ema_beta(self, epoch):
-        self.opt.ema_beta = 1.0 - epoch / (self.opt.n_epochs + self.opt.n_epochs_decay)
-
     def update_learning_rate(self, epoch):
-        for s in self.schedulers:
-            s.step()
-        self.adaptive_ema_beta(epoch)
+        super().update_learning_rate(epoch)
         self.current_epoch = epoch
-        print('learning rate = %.7f' % self.optimizers[0].param_groups[0]['lr'])
-
-    def set_requires_grad(self, nets, requires_grad=False):
-        for net in (nets if isinstance(nets, list) else [nets]):
-            if net is not None:
-                for p in net.parameters():
-                    p.requires_grad = requires_grad
-
-    def save_models(self, epoch, save_dir, fid=None, isbest=False, direction='AtoB'):
-        if gdist.rank() != 0:
-            return
-        util.mkdirs(save_dir)
-        ckpt = {'G': _portable(self.netG.state_dict()), 'D': _portable(self.netD.state_dict()), 'epoch': epoch,
-                'cfg': (self.filter_cfgs, self.channel_cfgs), 'psnr': fid}
-        name = 'model_best_%s.pth' % direction if isbest else 'model_%d.pth' % epoch
-        torch.save(ckpt, os.path.join(save_dir, name))
-
-    def load_models(self, load_path, load_discriminator=True):
-        ckpt = torch.load(load_path, map_location='cpu')
-        self.netG.load_state_dict(ckpt['G'])
-        if load_discriminator:
-            self.netD.load_state_dict(ckpt['D'])
-        self.refresh_weights()
-        print('loading the model from %s' % load_path)
-        return ckpt['psnr'], float('inf')
-
-    def model_train(self):
-        self.netG.train()
-        self.netD.train()
-
-    def model_eval(self):
-        self.netG.eval()
-        self.netD.eval()
-
-    def get_current_visuals(self):
-        ret = OrderedDict()
-        for name in self.visual_names:
-            ret[name] = getattr(self, name)
-        return ret
 
     def get_current_losses(self):
         v = self._lossvec.cpu()
@@ -649,22 +500,9 @@ class SRGAN(TrainingStateMixin, TeacherStreamMixin, nn.Module):
                                ops.stream()), 'gcc_ssim_y_sum')
         return float(acc.item()) / (N * (H - 14) * (W - 14))
 
-    def init_distillation(self):
-        if self.distill:
-            if self.opt.lambda_content > 0.0:
-                self.loss_names.append('content')
-            if self.opt.lambda_gram > 0.0:
-                self.loss_names.append('gram')
-            if self.opt.lambda_L1 > 0.0:
-                self.loss_names.append('L1')
-            self.visual_names.append('Tfake_hr')
-
     def get_distillation_features(self):
         """4 generator features (outputs of residual blocks 3/7/11/15) + the 2 discriminator features of the last D call"""
         return self.G.features(self._gctx) + self.D.features(self._dctx_last)
-
-    def get_cfg(self):
-        return self.filter_cfgs, self.channel_cfgs
 
     # -- pruning (models/SRGAN.py:703-830): per-block inner widths from BatchNorm scales or filter norms ----------------
     def max_min_bn_scale(self):

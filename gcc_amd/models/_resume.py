@@ -19,6 +19,7 @@ from collections import OrderedDict
 import torch
 
 from .._lib import GccError
+from ._optim import HipAdam
 
 _TRANSFORMS = ('transform_convs', 'transform_A_convs', 'transform_B_convs')
 _CFGS = ('filter_cfgs', 'channel_cfgs', 'cfg_AtoB', 'cfg_BtoA')
@@ -39,7 +40,6 @@ class TrainingStateMixin:
         return nets
 
     def _state_optimizers(self):
-        from .Pix2Pix import HipAdam
         return OrderedDict((n, o) for n, o in sorted(vars(self).items()) if isinstance(o, HipAdam))
 
     def _state_schedulers(self):
