@@ -915,7 +915,7 @@ extern "C" int gcc_clamp_f32(float* p, float lo, float hi, size_t n, gcc_stream_
 extern "C" int gcc_scalar_op(int op, const float* a, const float* b, const float* c, float k0, float k1, float* out,
                              gcc_stream_t stream) {
     GCC_ENTER();
-    if (!a || !b || !out || op < 0 || op > 2) return GCC_ERR_BAD_ARG;
+    if (!a || !b || !out || op < 0 || op > 2 || (op == 1 && !c)) return GCC_ERR_BAD_ARG;   // op 1 alone reads c
     hipLaunchKernelGGL(scalar_ops_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, op, a, b, c, k0, k1, out);
     GCC_CHECK_LAUNCH();
     return GCC_OK;

@@ -1,7 +1,14 @@
-"""Kernel-level parity: every libgcc_hip.so entry point against a plain PyTorch-CPU fp32 reference
-of the same op on the same (bf16-rounded) inputs.  Tolerance: outputs are bf16 (8 significant
-bits) accumulated in fp32 -> |err| <= 1.2e-2 * max|ref| (+ tiny absolute floor); integer/mask
-outputs exact."""
+"""Kernel-level parity: the convolution, norm, attention, spectral and layout entry points of
+libgcc_hip.so against a plain PyTorch-CPU fp32 reference of the same op on the same (bf16-rounded)
+inputs.  Tolerance: outputs are bf16 (8 significant bits) accumulated in fp32 ->
+|err| <= 1.2e-2 * max|ref| (+ tiny absolute floor); integer/mask outputs exact.
+
+Tested elsewhere: channel dimensions that are a concatenation of two 8-padded parts (ConvOp
+row_split / col_split, the two-kind packing path, gcc_conv_wgrad_seg and its slab reduce) in
+tests/test_segmented_conv_gpu.py; the loss, optimizer and elementwise kernels of misc.hip (GAN /
+L1 / MSE losses, Adam, the bf16 casts, fill / add / clamp, the arch-step scalars, the image pool)
+at their loop edges in tests/test_misc_kernels_gpu.py, which also says which tests reach the comm,
+replay and event entry points.  The one-shape tests of those kernels below stay as they are."""
 import math
 import os
 
@@ -42,6 +49,16 @@ def close(got, ref, tol=1.2e-2, floor=1e-6, what=''):
     err = (got - ref).abs().max().item()
     lim = tol * ref.abs().max().item() + floor
     assert err <= lim, '%s: err %.4g > %.4g (max|ref| %.4g)' % (what, err, lim, ref.abs().max().item())
+
+
+BAD_ARG, ERR_WORKSPACE = -1, -3        # include/gcc_hip.h GCC_ERR_BAD_ARG, GCC_ERR_WORKSPACE
+
+
+def full_view(t):
+    """all ld physical channels of an NHWC activation view, on the CPU as fp32 [N, ld, H, W]"""
+    N, _, H, W = t.shape
+    ld = t.stride(3)
+    return torch.as_strided(t, (N, ld, H, W), t.stride()).float().cpu()
 
 
 def master_cl(w):
