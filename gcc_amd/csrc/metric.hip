@@ -65,10 +65,13 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
 }
 
 __device__ __forceinline__ float luma(const float* img, size_t plane, size_t o) {
-    // convert_image('[-1, 1]' -> 'y-channel'), the reference's operation order in fp32
+    // convert_image('[-1, 1]' -> 'y-channel'), the reference's operation order in fp32.  The dot product is spelled as the fused
+    // chain a matmul row makes of it (r, then g, then b): left as `r * 65.481f + g * 128.553f + b * 24.966f` the compiler chose the
+    // contraction per call site, and the two images of one launch went through different roundings (fused g into r * c for one,
+    // r into g * c for the other: psnr(x, x) had a sum that was not zero)
     const float r = 255.f * ((img[o] + 1.f) / 2.f), g = 255.f * ((img[plane + o] + 1.f) / 2.f),
                 b = 255.f * ((img[2 * plane + o] + 1.f) / 2.f);
-    return (r * 65.481f + g * 128.553f + b * 24.966f) / 255.f + 16.f;
+    return __fmaf_rn(b, 24.966f, __fmaf_rn(g, 128.553f, r * 65.481f)) / 255.f + 16.f;
 }
 
 __global__ __launch_bounds__(256) void psnr_sse_kernel(const float* __restrict__ fake, const float* __restrict__ real, int N, int H,

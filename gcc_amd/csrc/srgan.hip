@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void pool_head_bwd_kernel(const bf16_t* __rest
 // dw[c] += sum_n dlogit[n] * pooled[n][c] ; db += sum_n dlogit[n]
 __global__ __launch_bounds__(256) void linear_head_wgrad_kernel(const bf16_t* __restrict__ dlogit, int ldl, const float* __restrict__ pooled, int N,
                                                                 int C, float* __restrict__ dw, float* __restrict__ db) {
-    for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
+    for (int c = blockIdx.x * 256 + threadIdx.x; dw && c < C; c += gridDim.x * 256) {
         float acc = 0.f;
         for (int n = 0; n < N; n++) acc += bf2f(dlogit[(size_t)n * ldl]) * pooled[(size_t)n * C + c];
         dw[c] += acc;
@@ -349,9 +349,9 @@ extern "C" int gcc_pool_linear_bwd(const void* dlogit, int ldl, const float* w, 
                            (const bf16_t*)dlogit, ldl, w, C, HW, N, (bf16_t*)dx, lddx);
         GCC_CHECK_LAUNCH();
     }
-    if (dw) {
-        hipLaunchKernelGGL(linear_head_wgrad_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const bf16_t*)dlogit, ldl, pooled, N,
-                           C, dw, db);
+    if (dw || db) {                                      // db alone: one block, the dw loop is skipped
+        hipLaunchKernelGGL(linear_head_wgrad_kernel, dim3(dw ? (C + 255) / 256 : 1), dim3(256), 0, st, (const bf16_t*)dlogit, ldl,
+                           pooled, N, C, dw, db);
         GCC_CHECK_LAUNCH();
     }
     return GCC_OK;

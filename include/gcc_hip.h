@@ -706,7 +706,8 @@ int gcc_attention_infer_route(int B, int N, int C, int C8, size_t ws_bytes);
  * gcc_maxpool2x2: nn.MaxPool2d(2, 2) of the VGG stack; backward (1) routes to the first maximum in scan order; backward == 2: x is
  * the output of a ReLU and the ReLU's backward is applied on the way (a gradient whose maximum is not positive is dropped).
  * gcc_pool_linear_*: AdaptiveAvgPool2d((1,1)) + Linear(C, 1) of the discriminators (:245-262): pooled [N][C] fp32 is
- * kept for the backward pass, logit is bf16 [N][ldl] (one pixel per image, as gcc_gan_loss reads it). */
+ * kept for the backward pass, logit is bf16 [N][ldl] (one pixel per image, as gcc_gan_loss reads it).  gcc_pool_linear_bwd: dx, dw
+ * (+=) and db (+=) may each be NULL; dw and db come out of one launch, whichever of them is asked for. */
 int gcc_prelu(int backward, const void* x, int ldx, const float* slope, int C, int N, int H, int W, int shuffle,
               void* y, int ldy, const void* dy, int lddy, void* dx, int lddx, float* dslope, void* workspace,
               size_t workspace_bytes, gcc_stream_t stream);
