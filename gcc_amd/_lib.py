@@ -81,6 +81,7 @@ class eval_ex_epilogue_t(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
+FID_IN_BF16, FID_IN_U8, FID_IN_F32 = 0, 1, 2               # include/gcc_hip.h GCC_FID_IN_*
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
 DW_INORM_WORKSPACE_BYTES = 4096 + (3 << 20)                # include/gcc_hip.h GCC_DW_INORM_WORKSPACE_BYTES
 
@@ -252,6 +253,10 @@ PROTOTYPES = {
     'gcc_ssim_y_sum': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _Z, _P]),
     'gcc_activation_stats_workspace': (_Z, [_I, _I]),
     'gcc_activation_stats': (_I, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'gcc_activation_stats_stream_workspace': (_Z, [_I, _I]),
+    'gcc_activation_stats_update': (_I, [_P, _I, _I, _I, _I, C.c_longlong, _P, _P, _P, _Z, _P]),
+    'gcc_activation_stats_finish': (_I, [_P, C.c_longlong, _I, _P, _P]),
+    'gcc_fid_input': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'gcc_frechet_workspace': (_Z, [_I]),
     'gcc_frechet_distance': (_I, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'gcc_attention_fwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),

@@ -154,6 +154,65 @@ __global__ __launch_bounds__(256) void center_kernel(const void* act, int is_f64
     }
 }
 
+// Streamed statistics (gcc_activation_stats_update): a batch [b][d] (row stride ld) merged into running centred moments
+// (Chan et al.).  One launch per batch for everything but the rank-b product: a workgroup owns 64 columns, its four waves sum
+// interleaved rows (combined in wave order: a fixed order), then write the batch centred on its OWN mean (xc: the GEMM's
+// operand), delta = batch mean - running mean (the GEMM's rank-1 term) and the merged mean.  first != 0 (nothing merged yet):
+// mean is written, never read, and delta is 0.
+__global__ __launch_bounds__(256) void stream_center_kernel(const void* act, int is_f64, int ld, int b, int d, int first,
+                                                            double w /* b / (n_before + b) */, double* mean, double* delta,
+                                                            double* xc) {
+    __shared__ double part[4][64];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, j = blockIdx.x * 64 + tx;
+    const bool live = j < d;
+    double acc = 0.0;
+    if (live) {
+        if (is_f64) { const double* a = (const double*)act; for (int i = ty; i < b; i += 4) acc += a[(size_t)i * ld + j]; }
+        else { const float* a = (const float*)act; for (int i = ty; i < b; i += 4) acc += (double)a[(size_t)i * ld + j]; }
+    }
+    part[ty][tx] = acc;
+    __syncthreads();
+    if (!live) return;
+    const double mb = (((part[0][tx] + part[1][tx]) + part[2][tx]) + part[3][tx]) / (double)b;
+    for (int i = ty; i < b; i += 4) {
+        const double v = is_f64 ? ((const double*)act)[(size_t)i * ld + j] : (double)((const float*)act)[(size_t)i * ld + j];
+        xc[(size_t)i * d + j] = v - mb;
+    }
+    if (ty == 0) {
+        if (first) { delta[j] = 0.0; mean[j] = mb; }
+        else {
+            const double m = mean[j], dl = mb - m;
+            delta[j] = dl;
+            mean[j] = m + dl * w;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void scale_kernel(const double* x, double s, size_t n, double* y) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = x[i] * s;
+}
+// generated / real images as the FID network's input, the fp32 form: util.tensor2imgs' byte of an NCHW fp32 image in [-1, 1]
+// ((x + 1) / 2 * 255 in fp32, clipped, truncated) over 255.  The layout does not change: plain elements, four per lane where the
+// pointers allow it.  float(b) / 255.f is the fp32 rounding of the reference's double quotient for every byte.
+__device__ __forceinline__ float fid_unit(float x) {
+#pragma clang fp contract(off)
+    float t = __fmul_rn(__fmul_rn(__fadd_rn(x, 1.f), 0.5f), 255.f);
+    t = t > 0.f ? (t < 255.f ? t : 255.f) : 0.f;
+    return (float)(unsigned char)t / 255.f;
+}
+__global__ __launch_bounds__(256) void fid_input_f32_kernel(const float* __restrict__ x, size_t nvec, size_t total,
+                                                            float* __restrict__ out) {
+    const size_t items = nvec + (total - 4 * nvec);             // float4 groups, then the scalar tail
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (size_t)gridDim.x * 256) {
+        if (i < nvec) {
+            const float4 v = ((const float4*)x)[i];
+            ((float4*)out)[i] = make_float4(fid_unit(v.x), fid_unit(v.y), fid_unit(v.z), fid_unit(v.w));
+        } else {
+            const size_t e = 4 * nvec + (i - nvec);
+            out[e] = fid_unit(x[e]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // C[M][N] = alpha * (*alpha_dev) * sum_k a(i,k) b(k,j) + diag * [i == j];  a(i,k) = A[i*sai + k*sak], b(k,j) = B[k*sbk + j*sbj]
 struct GemmArgs {
@@ -163,7 +222,11 @@ struct GemmArgs {
     double alpha, diag;
     const double* alpha_dev;     // optional device scalar; inv != 0: multiply by 1 / (*alpha_dev)
     int inv;
+    // MERGE only (the streamed statistics' update): C = beta * C + (the above) + r1c * r1[i] * r1[j]; beta == 0 never reads C
+    double beta, r1c;
+    const double* r1;
 };
+template <bool MERGE>
 __global__ __launch_bounds__(256) void dgemm_kernel(const GemmArgs g) {
     __shared__ double As[16][65], Bs[16][65];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -204,13 +267,20 @@ __global__ __launch_bounds__(256) void dgemm_kernel(const GemmArgs g) {
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             const int i = i0 + ty * 4 + r, j = j0 + tx * 4 + c;
-            if (i < g.M && j < g.N) g.C[(size_t)i * g.N + j] = al * acc[r][c] + (i == j ? g.diag : 0.0);
+            if (i < g.M && j < g.N) {
+                double v = al * acc[r][c] + (i == j ? g.diag : 0.0);
+                if constexpr (MERGE) {
+                    v += g.r1c * g.r1[i] * g.r1[j];
+                    if (g.beta != 0.0) v += g.beta * g.C[(size_t)i * g.N + j];
+                }
+                g.C[(size_t)i * g.N + j] = v;
+            }
         }
 }
 void dgemm(hipStream_t st, const double* A, long sai, long sak, const double* B, long sbk, long sbj, double* C, int M, int N, int K,
            double alpha, double diag, const double* alpha_dev = nullptr, int inv = 0) {
-    GemmArgs g = {A, sai, sak, B, sbk, sbj, C, M, N, K, alpha, diag, alpha_dev, inv};
-    hipLaunchKernelGGL(dgemm_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, g);
+    GemmArgs g = {A, sai, sak, B, sbk, sbj, C, M, N, K, alpha, diag, alpha_dev, inv, 0.0, 0.0, nullptr};
+    hipLaunchKernelGGL(dgemm_kernel<false>, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, g);
 }
 
 // single-workgroup reductions (fixed order): out[slot] = sqrt(sum x^2) | trace | |a - b|^2
@@ -329,6 +399,40 @@ extern "C" int gcc_activation_stats(const void* act, int is_f64, int n, int d, d
     GCC_CHECK_LAUNCH();
     // sigma = Xc^T Xc / (n - 1)
     dgemm(st, xc, 1, d, xc, d, 1, sigma, d, d, n, 1.0 / (double)(n - 1), 0.0);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" size_t gcc_activation_stats_stream_workspace(int max_batch, int d) {
+    if (max_batch <= 0 || d <= 0) return 0;
+    return ((size_t)d + (size_t)max_batch * d) * sizeof(double);    // delta | the batch centred on its own mean
+}
+
+extern "C" int gcc_activation_stats_update(const void* act, int is_f64, int ld, int b, int d, long long n_before, double* mean,
+                                           double* m2, void* ws, size_t ws_bytes, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!act || !mean || !m2 || !ws || b <= 0 || d <= 0 || ld < d || n_before < 0) return GCC_ERR_BAD_ARG;
+    if (ws_bytes < gcc_activation_stats_stream_workspace(b, d)) return GCC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    double* delta = (double*)ws;
+    double* xc = delta + d;
+    const double n = (double)n_before + (double)b;
+    hipLaunchKernelGGL(stream_center_kernel, dim3((d + 63) / 64), dim3(256), 0, st, act, is_f64, ld, b, d, n_before == 0 ? 1 : 0,
+                       (double)b / n, mean, delta, xc);
+    GCC_CHECK_LAUNCH();
+    // M2 <- M2 + Xc^T Xc + (n_before b / n) delta delta^T; the first batch writes M2 without reading it
+    GemmArgs g = {xc, 1, d, xc, d, 1, m2, d, d, b, 1.0, 0.0, nullptr, 0, n_before == 0 ? 0.0 : 1.0, (double)n_before * (double)b / n,
+                  delta};
+    hipLaunchKernelGGL(dgemm_kernel<true>, dim3((d + 63) / 64, (d + 63) / 64), dim3(256), 0, st, g);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_activation_stats_finish(const double* m2, long long n, int d, double* sigma, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!m2 || !sigma || n < 2 || d <= 0) return GCC_ERR_BAD_ARG;
+    const size_t n2 = (size_t)d * d;
+    hipLaunchKernelGGL(scale_kernel, dim3(nblk(n2)), dim3(256), 0, (hipStream_t)stream, m2, 1.0 / (double)(n - 1), n2, sigma);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
@@ -664,6 +768,23 @@ extern "C" int gcc_seg_input(const void* x, int is_u8, int ld, int off, int N, i
     const size_t plane = (size_t)H * W, total = plane * N;
     hipLaunchKernelGGL(seg_input_kernel, dim3(nblk(total, 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)(is_u8 ? nullptr : x), (const unsigned char*)(is_u8 ? x : nullptr), ld, off, plane, total, a, out);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_fid_input(const void* x, int form, int ld, int off, int N, int H, int W, float* out, gcc_stream_t stream) {
+    if (form == GCC_FID_IN_BF16 || form == GCC_FID_IN_U8) {
+        // the byte of gcc_seg_input over 255; (q - 0) / 1 keeps q's bits
+        const float zero[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
+        return gcc_seg_input(x, form == GCC_FID_IN_U8, ld, off, N, H, W, zero, one, out, stream);
+    }
+    GCC_ENTER();
+    if (form != GCC_FID_IN_F32 || !x || !out || N <= 0 || H <= 0 || W <= 0) return GCC_ERR_BAD_ARG;
+    const size_t total = (size_t)N * 3 * H * W;
+    const bool aligned = (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
+    const size_t nvec = aligned ? total / 4 : 0;
+    hipLaunchKernelGGL(fid_input_f32_kernel, dim3(nblk(nvec + (total - 4 * nvec), 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, nvec, total, out);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }

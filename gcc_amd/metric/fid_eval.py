@@ -1,0 +1,241 @@
+"""FID of a Pix2Pix (any root but Cityscapes), CycleGAN or SAGAN generator (metric/test_metric.py:15-45 test_pix2pix_fid, 129-161
+test_sagan_fid, 163-204 test_cyclegan_fid): everything around the Inception network.  The network stays an external input, as
+DRN does for the Cityscapes mIoU: ``GCC_FID_INCEPTION`` names a TorchScript archive of the reference's InceptionV3([3]) (exported
+once with torch.jit where its weights live), or any callable with its contract -- NCHW fp32 in [0, 1] at the generator's
+resolution in (resizing and normalisation are the network's own), element 0 of the result [N, d, h, w] fp32 out, averaged over
+(h, w) when not 1 x 1.
+
+    generator (model.infer_nhwc) -> gcc_fid_input (util.tensor2imgs' byte / 255) into slot k of a persistent batch buffer
+        -> inception(batch)[0] when the buffer is full (and once for the remainder) -> gcc_activation_stats_update
+        -> gcc_activation_stats_finish -> gcc_frechet_distance against real_stat*.npz -> one host read
+
+Nothing is read back before that last step, and the device holds d^2 doubles of statistics whatever the number of images.
+
+The one deliberate difference from the reference: it runs Inception at batch 1 (its evaluations set opt.batch_size = 1); this
+evaluator batches up to 50 images (get_activations' own default).  An eval-mode network's output for an image does not depend on
+its batch neighbours, so the activations are those of the batch-1 run up to the network's own batched arithmetic."""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from .._lib import FID_IN_BF16, FID_IN_F32, FID_IN_U8, GccError, check
+from .cityscapes import _prepare, adopt_batch
+from .fid_score import ActivationStream, calculate_frechet_distance
+
+ENV = 'GCC_FID_INCEPTION'
+SAGAN_FRACTION = 0.1              # metric/test_metric.py:144
+
+
+def wants_fid(opt):
+    """the reference's evaluation cases that need FID (train.py:14-73): Pix2Pix off Cityscapes, CycleGAN, SAGAN"""
+    if opt.model == 'pix2pix':
+        return 'cityscapes' not in str(opt.dataroot)
+    return 'cyclegan' in opt.model or opt.model == 'sagan'
+
+
+def real_stat_slots(opt):
+    """[(npz file under --dataroot, slot tag)] in the slot order of train.py:14-73"""
+    if 'cyclegan' in opt.model:
+        return [('real_stat_B.npz', 'AtoB'), ('real_stat_A.npz', 'BtoA')]
+    if opt.model == 'sagan':
+        return [('real_stat.npz', opt.direction)]
+    return [('real_stat_B.npz' if opt.direction == 'AtoB' else 'real_stat_A.npz', opt.direction)]
+
+
+def sagan_stops(i, length):
+    """metric/test_metric.py:144 as it stands (Python float arithmetic): batch i is not scored, nor any after it"""
+    return i > length * SAGAN_FRACTION
+
+
+def sagan_count(length):
+    """the number of batches test_sagan_fid scores out of ``length``"""
+    i = 0
+    while i < length and not sagan_stops(i, length):
+        i += 1
+    return i
+
+
+def fid_input(image, out=None):
+    """the network's input (NCHW fp32 [N, 3, H, W] in [0, 1]) through gcc_fid_input: of an NHWC bf16 activation view (a
+    generator's output), a uint8 [N, H, W, 3] device tensor, or an NCHW fp32 device tensor in [-1, 1] (a loader's image); the
+    byte of util.tensor2imgs over 255.  ``out``: a contiguous fp32 [N, 3, H, W] device tensor, e.g. a slot of a batch buffer."""
+    if image.dtype == torch.uint8:
+        if image.dim() == 3:
+            image = image[None]
+        image = image.contiguous()
+        N, H, W, c3 = image.shape
+        ptr, form, ld = image.data_ptr(), FID_IN_U8, 0
+    elif image.dtype == torch.bfloat16:
+        ptr, N, c3, H, W, ld = ops.geom(image)
+        form = FID_IN_BF16
+    elif image.dtype == torch.float32 and image.dim() == 4:
+        image = image.contiguous()
+        N, c3, H, W = image.shape
+        ptr, form, ld = image.data_ptr(), FID_IN_F32, 0
+    else:
+        raise GccError('fid_input: expected an NHWC bf16 view, uint8 [N, H, W, 3] or NCHW fp32, got %s %s'
+                       % (image.dtype, tuple(image.shape)))
+    if c3 != 3 or not image.is_cuda:
+        raise GccError('fid_input: expected 3-channel images on the device, got %s on %s' % (tuple(image.shape), image.device))
+    if out is None:
+        out = torch.empty((N, 3, H, W), dtype=torch.float32, device=image.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (N, 3, H, W) or not out.is_contiguous() or out.device != image.device:
+        raise GccError('fid_input: out must be a contiguous fp32 [%d, 3, %d, %d] tensor on the image\'s device' % (N, H, W))
+    check(ops.lib().gcc_fid_input(ptr, form, ld, 0, N, H, W, out.data_ptr(), ops.stream()), 'gcc_fid_input')
+    return out
+
+
+class ImageStatistics:
+    """images in (one at a time, keyed), the Inception statistics of the distinct keys out.  The images wait in a persistent
+    [batch_size, 3, H, W] buffer; a full buffer (and the remainder at the end) goes through the network and into the streamed
+    statistics, all on the current stream."""
+
+    def __init__(self, inception, batch_size=50):
+        self.inception, self.bs = inception, max(1, int(batch_size))
+        self.buf, self.k, self.seen, self.stream = None, 0, set(), None
+
+    @property
+    def count(self):
+        return len(self.seen)
+
+    def add(self, key, image):
+        """image: one image in any form fid_input takes (read before this returns control to the stream: a generator's view
+        may be reused by its next inference).  The reference keeps its images in a dict: a repeated key counts once."""
+        if key in self.seen:
+            return
+        self.seen.add(key)
+        if self.buf is None:
+            H, W = image.shape[-3:-1] if image.dtype == torch.uint8 else image.shape[-2:]       # [.., H, W, 3] | [N, 3, H, W]
+            self.buf = torch.empty((self.bs, 3, int(H), int(W)), dtype=torch.float32, device=image.device)
+        fid_input(image, self.buf[self.k:self.k + 1])
+        self.k += 1
+        if self.k == self.bs:
+            self.flush()
+
+    def flush(self):
+        if not self.k:
+            return
+        with torch.no_grad():
+            pred = self.inception(self.buf[:self.k])[0]
+        if not torch.is_tensor(pred) or pred.dim() != 4 or pred.dtype != torch.float32 or pred.shape[0] != self.k:
+            raise GccError('the Inception network must return [N, d, h, w] fp32 activations as element 0, got %s'
+                           % ('%s %s' % (pred.dtype, tuple(pred.shape)) if torch.is_tensor(pred) else type(pred).__name__))
+        if pred.shape[2] != 1 or pred.shape[3] != 1:
+            pred = pred.mean((2, 3), keepdim=True)                  # metric/fid_score.py:205-206
+        if self.stream is None:
+            self.stream = ActivationStream(pred.shape[1], self.bs, pred.device)
+        self.stream.update(pred)
+        self.k = 0
+
+    def result(self):
+        """(mu [d], sigma [d, d]) f64 device tensors"""
+        if self.count < 2:
+            raise GccError('FID statistics need at least 2 images, %d were scored' % self.count)
+        self.flush()
+        return self.stream.result()
+
+
+def load_real_stat(path, d, device):
+    """mu [d], sigma [d, d] of a real_stat*.npz as f64 device tensors"""
+    with np.load(path) as z:
+        mu, sigma = np.asarray(z['mu']), np.asarray(z['sigma'])
+    if mu.shape != (d,) or sigma.shape != (d, d):
+        raise GccError('%s holds mu %s and sigma %s; the network\'s activations have d = %d' % (path, mu.shape, sigma.shape, d))
+    f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
+    return f(mu), f(sigma)
+
+
+class FidScorer:
+    """one evaluation: generated images in (per slot), one FID per slot out"""
+
+    def __init__(self, inception, dataroot, slots, batch_size=50):
+        self.files = [os.path.join(str(dataroot), name) for name, _ in slots]
+        self.tags = [tag for _, tag in slots]
+        self.stats = [ImageStatistics(inception, batch_size) for _ in slots]
+
+    def add(self, key, fake, slot=0):
+        self.stats[slot].add(key, fake)
+
+    def result(self):
+        values = []
+        for path, st in zip(self.files, self.stats):
+            mu, sigma = st.result()
+            m1, s1 = load_real_stat(path, mu.numel(), mu.device)
+            values.append(float(calculate_frechet_distance(m1, s1, mu, sigma)))         # metric/__init__.py:8-14
+        return values
+
+
+def fid_line(values, tags, model):
+    if 'cyclegan' in model:
+        return ' | '.join('%s FID: %.2f' % (t, v) for v, t in zip(values, tags))
+    return 'FID: %.2f' % values[0]
+
+
+def fid_evaluator(inception, logger=None, batch_size=50):
+    """evaluate(model, opt) for gcc_amd.train.run_evaluation: test_pix2pix_fid / test_cyclegan_fid / test_sagan_fid.
+    ``evaluate.scorer(model, opt)`` gives python -m gcc_amd.test the scorer of the images it writes.  Inception runs on batches
+    of up to ``batch_size`` images where the reference runs it at batch 1: the one deliberate difference (see the module)."""
+    state = {'inception': None}
+
+    def scorer(model, opt):
+        if state['inception'] is None:
+            state['inception'] = _prepare(inception, model.device)
+        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size)
+
+    def evaluate(model, opt):
+        from ..data import create_dataset
+        from ..test import test_overrides
+        topt = test_overrides(opt)
+        dataset = create_dataset(topt, model.device)
+        dataset.shard = False                      # an evaluation walks the whole split on whichever rank runs it
+        sc = scorer(model, topt)
+        cur = torch.cuda.current_stream(model.device)
+        length = len(dataset) if opt.model == 'sagan' else 0
+        for i, data in enumerate(dataset):
+            if opt.model == 'sagan' and sagan_stops(i, length):
+                break
+            adopt_batch(data, cur)
+            if opt.model == 'sagan':
+                sc.add(data['img_path'][0], model.infer_nhwc(data))
+            elif 'cyclegan' in opt.model:
+                sc.add(data['A_paths'][0], model.infer_nhwc(data, 'A'), 0)
+                sc.add(data['B_paths'][0], model.infer_nhwc(data, 'B'), 1)
+            else:
+                sc.add(data['A_paths'][0], model.infer_nhwc(data))
+        values = sc.result()
+        if logger is not None:
+            logger.info(fid_line(values, sc.tags, opt.model))
+        return list(zip(values, sc.tags))
+
+    evaluate.state = state
+    evaluate.scorer = scorer
+    return evaluate
+
+
+def load_inception():
+    """(module, None) from the TorchScript archive GCC_FID_INCEPTION names, else (None, the condition that failed)"""
+    path = os.environ.get(ENV)
+    if not path:
+        return None, '%s is not set (the path of a TorchScript archive of the Inception network)' % ENV
+    if not os.path.isfile(path):
+        return None, '%s %s does not exist' % (ENV, path)
+    try:
+        return torch.jit.load(path, map_location='cpu'), None
+    except Exception as e:
+        first = (str(e).strip().splitlines() or [type(e).__name__])[0]
+        return None, 'torch.jit.load could not read %s %s as a TorchScript archive (%s: %s); a plain state_dict needs the ' \
+                     'network\'s code: export InceptionV3([3]) with torch.jit once' % (ENV, path, type(e).__name__, first)
+
+
+def builtin_inception(opt):
+    """for a run whose evaluation is FID (wants_fid): (network, None) when GCC_FID_INCEPTION names a TorchScript archive and
+    --dataroot holds the real statistics the model's slots need, else (None, the condition that failed)"""
+    module, why = load_inception()
+    if module is None:
+        return None, why
+    missing = [name for name, _ in real_stat_slots(opt) if not os.path.isfile(os.path.join(str(opt.dataroot), name))]
+    if missing:
+        return None, '%s holds no %s (python -m gcc_amd.metric.get_real_stat writes it)' % (opt.dataroot, ', '.join(missing))
+    return module, None

@@ -39,6 +39,54 @@ def activation_statistics(act):
     return mu, sigma
 
 
+class ActivationStream:
+    """activation_statistics from batches (gcc_activation_stats_update / _finish: Chan et al.'s merge of centred moments in
+    f64): ``update(act)`` queues two launches behind whatever produced ``act`` on the current stream and reads nothing back;
+    ``result()`` -> (mu [d], sigma [d, d]) f64 device tensors.  The device holds d + d^2 doubles of state and a workspace of
+    (max_batch + 1) d doubles, whatever the number of rows; the row count is a host integer."""
+
+    def __init__(self, d, max_batch, device=None):
+        self.d, self.max_batch, self.n = int(d), int(max_batch), 0
+        if self.d <= 0 or self.max_batch <= 0:
+            raise GccError('ActivationStream: d and max_batch must be positive, got %d and %d' % (self.d, self.max_batch))
+        self.device = torch.device(device) if device is not None else _dev()
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.mean = torch.empty(self.d, dtype=torch.float64, device=self.device)
+        self.m2 = torch.empty((self.d, self.d), dtype=torch.float64, device=self.device)
+        self.ws = torch.empty(ops.lib().gcc_activation_stats_stream_workspace(self.max_batch, self.d), dtype=torch.uint8,
+                              device=self.device)
+
+    def update(self, act):
+        """act: [b, d] or [b, d, 1, 1], fp32 or f64, on the stream's device, 1 <= b <= max_batch; rows may be strided (read
+        in place), elements of a row may not"""
+        if act.dim() == 4 and act.shape[2] == 1 and act.shape[3] == 1:
+            act = act[:, :, 0, 0]
+        if act.dim() != 2 or act.shape[1] != self.d or act.dtype not in (torch.float32, torch.float64) or \
+                act.device != self.device:
+            raise GccError('ActivationStream.update: expected fp32 / f64 activations [b, %d] on %s, got %s %s on %s'
+                           % (self.d, self.device, act.dtype, tuple(act.shape), act.device))
+        b = act.shape[0]
+        if not 1 <= b <= self.max_batch:
+            raise GccError('ActivationStream.update: %d rows, the stream was made for 1..%d' % (b, self.max_batch))
+        if (self.d > 1 and act.stride(1) != 1) or (b > 1 and act.stride(0) < self.d):
+            act = act.contiguous()
+        ld = act.stride(0) if b > 1 else self.d
+        check(ops.lib().gcc_activation_stats_update(act.data_ptr(), int(act.dtype == torch.float64), ld, b, self.d, self.n,
+                                                    self.mean.data_ptr(), self.m2.data_ptr(), self.ws.data_ptr(),
+                                                    self.ws.numel(), ops.stream()), 'gcc_activation_stats_update')
+        self.n += b
+        return self
+
+    def result(self):
+        if self.n < 2:
+            raise GccError('ActivationStream.result: a covariance needs at least 2 rows, %d were given' % self.n)
+        sigma = torch.empty_like(self.m2)
+        check(ops.lib().gcc_activation_stats_finish(self.m2.data_ptr(), self.n, self.d, sigma.data_ptr(), ops.stream()),
+              'gcc_activation_stats_finish')
+        return self.mean, sigma
+
+
 def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6, iterations=None, return_residual=False):
     """metric/fid_score.py:219-284: d^2 = |mu1 - mu2|^2 + Tr(C1 + C2 - 2 sqrt(C1 C2)).  The reference retries with
     eps * I added to both covariances when scipy's sqrtm returns non-finite entries; here that happens when the

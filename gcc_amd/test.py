@@ -4,6 +4,8 @@ over the test split, write PNGs under <checkpoints_dir>/<name>/test_results with
 Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
   pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path);
             on a Cityscapes root with table.txt and a TorchScript segmenter at --drn_path: prints the mIoU afterwards
+  pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
+            --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written)
   srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer
   cyclegan  phase test, visual_forward, visuals real_A / fake_B
   sagan     the first 1000 batches; the generator through SAGANModel.infer_nhwc (fused eval path)
@@ -157,6 +159,14 @@ def run(opt, model):
             print('no Cityscapes evaluation: %s' % why)
         else:
             scorer = cityscapes_evaluator(segmenter).scorer(model, topt)
+    fid = None
+    from .metric import fid_eval
+    if fid_eval.wants_fid(opt):                  # metric/test_metric.py:15-45, 129-204 on the images written here
+        inception, why = fid_eval.builtin_inception(opt)
+        if inception is None:
+            print('no FID evaluation: %s' % why)
+        else:
+            fid = fid_eval.fid_evaluator(inception).scorer(model, topt)
     dataset = create_dataset(topt, model.device)
     if scorer is not None and getattr(dataset, 'paths', None) is not None:
         scorer.prefetch(dataset.paths)
@@ -168,10 +178,17 @@ def run(opt, model):
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A)}
             if scorer is not None:
                 scorer.add(data['A_paths'][0], visuals['fake_B'])
+            if fid is not None:
+                fid.add(data['A_paths'][0], visuals['fake_B'])
         elif opt.model == 'cyclegan':
             visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A, 'A')}
+            if fid is not None:                  # the second generator runs for its score only
+                fid.add(data['A_paths'][0], visuals['fake_B'], 0)
+                fid.add(data['B_paths'][0], model.infer_nhwc(model.real_B, 'B'), 1)
         elif opt.model == 'sagan':
             visuals = {'fake_img': model.infer_nhwc(data), 'real_img': model.real_img}
+            if fid is not None:
+                fid.add(data['img_path'][0], visuals['fake_img'])
         else:
             with torch.no_grad():
                 model.forward()
@@ -181,6 +198,8 @@ def run(opt, model):
     w.close()
     if scorer is not None:
         print('mIoU: %.2f' % scorer.result())
+    if fid is not None:
+        print(fid_eval.fid_line(fid.result(), fid.tags, opt.model))
     return result_dir
 
 

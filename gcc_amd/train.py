@@ -10,7 +10,8 @@ batch dicts ({'A','B','A_paths','B_paths'} ...) can be passed to main(datasets=.
 The per-epoch evaluation of the reference's loop (train.py:14-73, 160-165) needs third-party evaluator networks
 (Inception / DRN weights): main(evaluate=fn) takes the callable that produces the metric(s) -- gcc_amd.metric supplies
 the arithmetic downstream of those networks -- and keeps the reference's best-checkpoint bookkeeping around it.  Without
-evaluate=, builtin_evaluator picks SRGAN's PSNR / SSIM or, given a TorchScript segmenter at --drn_path, the Cityscapes mIoU.
+evaluate=, builtin_evaluator picks SRGAN's PSNR / SSIM, given a TorchScript segmenter at --drn_path the Cityscapes mIoU, or, given
+a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under --dataroot, the FID of the other three cases.
 """
 import copy
 import os
@@ -114,7 +115,9 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
 def builtin_evaluator(opt, logger):
     """the evaluation a run gets without an explicit evaluate=: SRGAN's PSNR / SSIM on the reference's test sets found under
     <dataroot>/test (train.py:37-56); Pix2Pix's mIoU on a Cityscapes root that holds table.txt when --drn_path is a TorchScript
-    segmenter (train.py:16-25; gcc_amd.metric.cityscapes); None otherwise -- FID needs an evaluator network the caller provides"""
+    segmenter (train.py:16-25; gcc_amd.metric.cityscapes); the FID of Pix2Pix on any other root, CycleGAN and SAGAN (train.py:26-36,
+    57-73; gcc_amd.metric.fid_eval) when GCC_FID_INCEPTION names a TorchScript Inception network and the root holds the real
+    statistics; None otherwise"""
     if opt.model == 'pix2pix' and 'cityscapes' in str(opt.dataroot):
         from .metric.cityscapes import builtin_segmenter, cityscapes_evaluator
         segmenter, why = builtin_segmenter(opt)
@@ -123,7 +126,17 @@ def builtin_evaluator(opt, logger):
             return None
         logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s' % (opt.save_epoch_freq, opt.drn_path))
         return cityscapes_evaluator(segmenter, logger)
-    if opt.model != 'srgan' or str(opt.dataroot).startswith('synthetic'):
+    if str(opt.dataroot).startswith('synthetic'):
+        return None
+    from .metric.fid_eval import ENV, builtin_inception, fid_evaluator, wants_fid
+    if wants_fid(opt):
+        inception, why = builtin_inception(opt)
+        if inception is None:
+            logger.info('no FID evaluation: %s' % why)
+            return None
+        logger.info('FID evaluation every %d epochs with the Inception network %s' % (opt.save_epoch_freq, os.environ[ENV]))
+        return fid_evaluator(inception, logger)
+    if opt.model != 'srgan':
         return None
     from .metric.sr_eval import available_sets, srgan_evaluator
     sets = available_sets(opt)

@@ -826,6 +826,34 @@ int gcc_miou_score(const float* scores, int N, int C, int h, int w, const unsign
                    const double* hcoef, int hk, const int* vbounds, const double* vcoef, int vk, long long* hist,
                    unsigned char* pred, gcc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * FID around the Inception network (metric/test_metric.py:15-45, 129-204, metric/get_real_stat.py; the network itself is the
+ * caller's).  Added without a GCC_HIP_ABI bump (additions only).
+ * gcc_fid_input: the network's input, NCHW fp32 out[N][3][H][W] in [0, 1] = float(byte) / 255.f (equal to the reference's
+ *   float(double(byte) / 255.0) for all 256 bytes), written at `out` (a slot of a batch buffer works), from
+ *     GCC_FID_IN_BF16  an NHWC bf16 image [N][H][W] (ld, off: multiples of 8): byte as gcc_image_to_u8 / util.tensor2imgs
+ *     GCC_FID_IN_U8    a DEVICE uint8 [N][H][W][3] image: the byte itself (ld, off unused)
+ *     GCC_FID_IN_F32   an NCHW fp32 image in [-1, 1] (what the data loaders yield; ld, off unused): byte = trunc(clip((x + 1) / 2
+ *                      * 255, 0, 255)) in fp32 in exactly that order -- 63 of the 256 bytes b do not come back from the loaders'
+ *                      (b / 255 - 0.5) / 0.5 as b but as b - 1, and the real-image statistics are those of the reference only
+ *                      when that is reproduced.
+ * Streamed activation statistics: what gcc_activation_stats computes, from batches, with a workspace that does not grow with n.
+ *   The caller keeps mean [d] and m2 [d][d] (f64, device) and the count of rows merged so far (a host integer).
+ *   gcc_activation_stats_update merges b >= 1 rows act[b][d] (fp32 or f64, row stride ld >= d elements: a [b][d][1][1] network
+ *   output is read in place): m_b = batch mean, Xc = batch - m_b, delta = m_b - mean,
+ *       m2 += Xc^T Xc + (n_before b / (n_before + b)) delta delta^T ;  mean += delta b / (n_before + b)      (Chan et al.)
+ *   in f64, two launches, fixed summation order.  n_before == 0: mean and m2 are written without being read (no zero fill
+ *   needed).  ws: gcc_activation_stats_stream_workspace(max_batch, d) bytes serve every b <= max_batch; one stream at a time.
+ *   gcc_activation_stats_finish: sigma = m2 / (n - 1) (sigma may be m2); GCC_ERR_BAD_ARG for n < 2.
+ *   Both refuse (GCC_ERR_BAD_ARG / GCC_ERR_WORKSPACE) before anything is launched.
+ * --------------------------------------------------------------------------------------------- */
+enum { GCC_FID_IN_BF16 = 0, GCC_FID_IN_U8 = 1, GCC_FID_IN_F32 = 2 };
+int gcc_fid_input(const void* x, int form, int ld, int off, int N, int H, int W, float* out, gcc_stream_t stream);
+size_t gcc_activation_stats_stream_workspace(int max_batch, int d);
+int gcc_activation_stats_update(const void* act, int is_f64, int ld, int b, int d, long long n_before, double* mean, double* m2,
+                                void* ws, size_t ws_bytes, gcc_stream_t stream);
+int gcc_activation_stats_finish(const double* m2, long long n, int d, double* sigma, gcc_stream_t stream);
+
 /* ---- gradient exchange ---------------------------------------------------------------------------------
  * The reference trains on one device (models/Pix2Pix.py:356); the data-parallel path sums the five optimizers' flat fp32
  * gradient buffers over ranks before each `optimizer.step()` (train.py has no counterpart: this is the exchange a
