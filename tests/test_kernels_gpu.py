@@ -8,7 +8,10 @@ row_split / col_split, the two-kind packing path, gcc_conv_wgrad_seg and its sla
 tests/test_segmented_conv_gpu.py; the loss, optimizer and elementwise kernels of misc.hip (GAN /
 L1 / MSE losses, Adam, the bf16 casts, fill / add / clamp, the arch-step scalars, the image pool)
 at their loop edges in tests/test_misc_kernels_gpu.py, which also says which tests reach the comm,
-replay and event entry points.  The one-shape tests of those kernels below stay as they are."""
+replay and event entry points; the depthwise / reflection-pad kernels of dwconv.hip, and spectral.hip
+and the training kernels of attention.hip, at pruned channel counts, small planes, strides, slices and
+loop edges, per element against float64, in tests/test_dwconv_kernels_gpu.py and
+tests/test_sagan_kernels_gpu.py.  The one-shape tests of those kernels below stay as they are."""
 import math
 import os
 
