@@ -246,6 +246,9 @@ PROTOTYPES = {
     'gcc_crop_convert': (_I, [_P, _I, _I, _Z, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     'gcc_seg_input': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     'gcc_miou_score': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    'gcc_phase_regroup': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'gcc_relu_bf16': (_I, [_P, _I, _I, _I, _Z, _P]),
+    'gcc_seg_head': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     'gcc_argmax_channels': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_confusion_hist': (_I, [_P, _P, _Z, _I, _P, _P]),
     'gcc_psnr_workspace': (_Z, []),

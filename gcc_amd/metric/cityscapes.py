@@ -1,6 +1,7 @@
 """Cityscapes mIoU of a Pix2Pix generator (metric/test_metric.py:47-87 test_pix2pix_mIoU, metric/mIoU_score.py:70-105, 169-218):
-everything around the segmentation network.  The network itself (DRN-D-105 in the reference) stays an external input: any
-callable ``segmenter(x)`` whose result's element 0 is the [N, C, h, w] fp32 score map.
+everything around the segmentation network.  The network itself (DRN-D-105 in the reference) is any callable ``segmenter(x)``
+whose result's element 0 is the [N, C, h, w] fp32 score map: drn_seg.DrnSegEngine from the reference's own weights file, or a
+TorchScript archive.
 
     generator (model.infer_nhwc) -> gcc_seg_input (tensor2im's byte, ToTensor, Normalize) -> segmenter(x)[0]
         -> gcc_miou_score (PIL's float BILINEAR resize to the labels' size + argmax + fast_hist, one launch, exact)
@@ -311,8 +312,9 @@ def cityscapes_evaluator(segmenter, logger=None, batch_size=1):
 
 def builtin_segmenter(opt):
     """for a Pix2Pix run on a Cityscapes root (the callers' test, the reference's own: 'cityscapes' in --dataroot): (segmenter,
-    None) when <dataroot>/table.txt exists and --drn_path is a TorchScript archive (the reference's DRNSeg exported once with
-    torch.jit where its weights live), else (None, the condition that failed)"""
+    None) when <dataroot>/table.txt exists and --drn_path is a TorchScript archive (the reference's DRNSeg exported with
+    torch.jit) or the reference's own file, the plain state_dict of a DRNSeg over an arch-D DRN (drn_seg.DrnSegEngine, still on the
+    host: the scorer moves it to the device); else (None, the condition that failed)"""
     root = str(opt.dataroot)
     if not os.path.isfile(os.path.join(root, 'table.txt')):
         return None, '%s holds no table.txt' % root
@@ -323,5 +325,16 @@ def builtin_segmenter(opt):
         return torch.jit.load(path, map_location='cpu'), None
     except Exception as e:
         first = (str(e).strip().splitlines() or [type(e).__name__])[0]
-        return None, 'torch.jit.load could not read --drn_path %s as a TorchScript archive (%s: %s); a plain state_dict needs ' \
-                     'the network\'s code: export DRNSeg with torch.jit once' % (path, type(e).__name__, first)
+        reason = 'torch.jit.load could not read --drn_path %s as a TorchScript archive (%s: %s); a plain state_dict needs ' \
+                 'the network\'s code: export DRNSeg with torch.jit once' % (path, type(e).__name__, first)
+    from .drn_seg import DrnSegEngine, is_drn_seg_state_dict
+    try:
+        sd = torch.load(path, map_location='cpu', weights_only=True)
+    except Exception:
+        return None, reason
+    if not is_drn_seg_state_dict(sd):
+        return None, reason
+    try:
+        return DrnSegEngine(sd), None
+    except GccError as e:
+        return None, '--drn_path %s holds a DRNSeg state_dict this package does not run: %s' % (path, e)

@@ -881,6 +881,45 @@ def nhwc_add(src, soff, dst, doff, Cc):
     check(lib().gcc_nhwc_add(sp, lds, soff, dp, ldd, doff, Cc, N * H * W, stream()), 'gcc_nhwc_add')
 
 
+def phase_regroup(src, dst, d_src, d_dst):
+    """gcc_phase_regroup: src, the phase layout d_src ([N d_src^2, C, H / d_src, W / d_src]) of a logical NHWC bf16 image
+    [N, C, H, W], written as its phase layout d_dst into dst (metric/drn_seg.py: a dilated 3 x 3 conv is a plain one there)"""
+    sp, Ns, Cc, hs, ws, lds = geom(src)
+    dp, Nd, Cd, hd, wd, ldd = geom(dst)
+    N, H, W = Ns // (d_src * d_src), hs * d_src, ws * d_src
+    if Cd != Cc or Ns != N * d_src * d_src or (Nd, hd * d_dst, wd * d_dst) != (N * d_dst * d_dst, H, W):
+        raise _lib.GccError('phase_regroup: %s in layout %d against %s in layout %d' % (tuple(src.shape), d_src, tuple(dst.shape), d_dst))
+    check(lib().gcc_phase_regroup(sp, lds, 0, d_src, dp, ldd, 0, d_dst, N, H, W, Cc, stream()), 'gcc_phase_regroup')
+    return dst
+
+
+def relu_(x):
+    """gcc_relu_bf16: in-place ReLU of the channels of an NHWC bf16 view"""
+    xp, N, Cc, H, W, ld = geom(x)
+    check(lib().gcc_relu_bf16(xp, ld, 0, Cc, N * H * W, stream()), 'gcc_relu_bf16')
+    return x
+
+
+def seg_head(x, seg_w, seg_b, up_w, scores, logp=None):
+    """gcc_seg_head: scores (NCHW fp32 [N, C, h, w]) = the 1 x 1 conv seg_w [C, Cin] (+ seg_b) of the NHWC bf16 feature map x
+    (x None: scores are read as given); logp (NCHW fp32 [N, C, 8h, 8w], optional) = LogSoftmax of the depthwise 16 x 16,
+    stride-8, padding-4 ConvTranspose2d with weights up_w [C, 256] of the scores.  All fp32 tensors contiguous."""
+    N, Cc, h, w = scores.shape
+    xp, ld, Cin = None, 0, 0
+    if x is not None:
+        xp, Nx, Cin, hx, wx, ld = geom(x)
+        if (Nx, hx, wx) != (N, h, w) or tuple(seg_w.shape) != (Cc, Cin):
+            raise _lib.GccError('seg_head: features %s, weights %s, scores %s' % (tuple(x.shape), tuple(seg_w.shape), tuple(scores.shape)))
+    for t in (seg_w, seg_b, up_w, scores, logp):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != scores.device):
+            raise _lib.GccError('seg_head: fp32 contiguous tensors on one device expected')
+    if logp is not None and (tuple(logp.shape) != (N, Cc, 8 * h, 8 * w) or up_w is None or up_w.numel() != Cc * 256):
+        raise _lib.GccError('seg_head: log-probabilities %s / up weights against scores %s' % (tuple(logp.shape), tuple(scores.shape)))
+    check(lib().gcc_seg_head(xp, ld, 0, N, h, w, Cin, _p(seg_w), _p(seg_b), Cc, _p(up_w), scores.data_ptr(), _p(logp), stream()),
+          'gcc_seg_head')
+    return scores, logp
+
+
 class BNState:
     """Per-application saved statistics of one BatchNorm layer (fp32 [C] each)."""
 

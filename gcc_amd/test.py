@@ -3,7 +3,7 @@ over the test split, write PNGs under <checkpoints_dir>/<name>/test_results with
 
 Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
   pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path);
-            on a Cityscapes root with table.txt and a TorchScript segmenter at --drn_path: prints the mIoU afterwards
+            on a Cityscapes root with table.txt and a segmenter at --drn_path (the reference's .pth or TorchScript): prints the mIoU afterwards
   pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
             --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written)
   srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer

@@ -10,7 +10,7 @@ batch dicts ({'A','B','A_paths','B_paths'} ...) can be passed to main(datasets=.
 The per-epoch evaluation of the reference's loop (train.py:14-73, 160-165) needs third-party evaluator networks
 (Inception / DRN weights): main(evaluate=fn) takes the callable that produces the metric(s) -- gcc_amd.metric supplies
 the arithmetic downstream of those networks -- and keeps the reference's best-checkpoint bookkeeping around it.  Without
-evaluate=, builtin_evaluator picks SRGAN's PSNR / SSIM, given a TorchScript segmenter at --drn_path the Cityscapes mIoU, or, given
+evaluate=, builtin_evaluator picks SRGAN's PSNR / SSIM, given a segmenter at --drn_path (the reference's DRNSeg .pth or a TorchScript archive) the Cityscapes mIoU, or, given
 a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under --dataroot, the FID of the other three cases.
 """
 import copy
@@ -114,8 +114,8 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
 
 def builtin_evaluator(opt, logger):
     """the evaluation a run gets without an explicit evaluate=: SRGAN's PSNR / SSIM on the reference's test sets found under
-    <dataroot>/test (train.py:37-56); Pix2Pix's mIoU on a Cityscapes root that holds table.txt when --drn_path is a TorchScript
-    segmenter (train.py:16-25; gcc_amd.metric.cityscapes); the FID of Pix2Pix on any other root, CycleGAN and SAGAN (train.py:26-36,
+    <dataroot>/test (train.py:37-56); Pix2Pix's mIoU on a Cityscapes root that holds table.txt when --drn_path is the reference's
+    DRNSeg state_dict or a TorchScript segmenter (train.py:16-25; gcc_amd.metric.cityscapes, .drn_seg); the FID of Pix2Pix on any other root, CycleGAN and SAGAN (train.py:26-36,
     57-73; gcc_amd.metric.fid_eval) when GCC_FID_INCEPTION names a TorchScript Inception network and the root holds the real
     statistics; None otherwise"""
     if opt.model == 'pix2pix' and 'cityscapes' in str(opt.dataroot):

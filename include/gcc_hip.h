@@ -827,6 +827,36 @@ int gcc_miou_score(const float* scores, int N, int C, int h, int w, const unsign
                    unsigned char* pred, gcc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The segmenter itself (DRN-D of metric/drn.py under DRNSeg, metric/mIoU_score.py:124-157): its convolutions are
+ * gcc_conv_eval_ex / gcc_conv_fprop_eval calls; these are the three streaming pieces around them (gcc_amd/csrc/segnet.hip,
+ * gcc_amd/metric/drn_seg.py).  Added without a GCC_HIP_ABI bump (additions only).  One launch each unless stated; every refusal
+ * happens before anything is launched.
+ * gcc_phase_regroup: "phase layout" d of a logical NHWC bf16 image [N][H][W] is the image [N d^2][H / d][W / d] in which logical
+ *   pixel (n, h, w) sits at batch index n d^2 + (h mod d) d + (w mod d), row h div d, column w div d (d = 1: the image itself).
+ *   A 3 x 3, stride-1 convolution of dilation d and zero padding d of the logical image is the plain 3 x 3, padding-1
+ *   convolution of its phase layout d.  The call copies channels [soff, soff + C) of `src` (layout d_src) to channels
+ *   [doff, doff + C) of `dst` (layout d_dst) in 16-byte chunks; channels [C, ceil8(C)) of the destination window are written as
+ *   zeros, every other channel of dst is left alone.  GCC_ERR_BAD_ARG: a null pointer, a non-positive size, an ld / offset that
+ *   is no multiple of 8, a window that does not fit its ld, buffers that overlap (the permutation is not done in place);
+ *   GCC_ERR_UNSUPPORTED: a d other than 1, 2, 4, or H / W that are no multiples of both.
+ * gcc_relu_bf16: x[p][off + c] = x > 0 ? x : +0 in place for c < C, p < pixels (NaN stays NaN, -0 becomes +0): the ReLU of
+ *   relu(bn(conv) + residual) behind gcc_conv_fprop_eval.  Channels outside the window are untouched.
+ * gcc_seg_head: DRNSeg's output end in fp32, two launches.
+ *   (a) x != NULL: scores[n][c][p] = seg_b[c] + sum_k seg_w[c][k] x[n][p][off + k], the 1 x 1 `seg` conv of the NHWC bf16 feature
+ *       map x [N][h][w] (Cin channels, a multiple of 8; seg_w fp32 [C][Cin]; seg_b fp32 [C] or NULL), NCHW fp32 [N][C][h][w].
+ *       x == NULL: `scores` is read as given.
+ *   (b) logp != NULL: logp = LogSoftmax_c(ConvTranspose2d(C, C, 16, stride 8, padding 4, groups C, no bias)(scores)) with the
+ *       weights up_w fp32 [C][1][16][16] (read, never assumed bilinear), NCHW fp32 [N][C][8h][8w]; at most 2 x 2 taps reach an
+ *       output pixel, whose C values stay in one thread's registers.
+ *   C <= 64, GCC_ERR_UNSUPPORTED beyond.
+ * --------------------------------------------------------------------------------------------- */
+int gcc_phase_regroup(const void* src, int lds, int soff, int d_src, void* dst, int ldd, int doff, int d_dst, int N, int H, int W,
+                      int C, gcc_stream_t stream);
+int gcc_relu_bf16(void* x, int ld, int off, int C, size_t pixels, gcc_stream_t stream);
+int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b, int C,
+                 const float* up_w, float* scores, float* logp, gcc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FID around the Inception network (metric/test_metric.py:15-45, 129-204, metric/get_real_stat.py; the network itself is the
  * caller's).  Added without a GCC_HIP_ABI bump (additions only).
  * gcc_fid_input: the network's input, NCHW fp32 out[N][3][H][W] in [0, 1] = float(byte) / 255.f (equal to the reference's
