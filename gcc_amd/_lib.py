@@ -82,6 +82,7 @@ class eval_ex_epilogue_t(C.Structure):
 
 
 FID_IN_BF16, FID_IN_U8, FID_IN_F32 = 0, 1, 2               # include/gcc_hip.h GCC_FID_IN_*
+POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2     # include/gcc_hip.h GCC_POOL3_*
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
 DW_INORM_WORKSPACE_BYTES = 4096 + (3 << 20)                # include/gcc_hip.h GCC_DW_INORM_WORKSPACE_BYTES
 
@@ -249,6 +250,10 @@ PROTOTYPES = {
     'gcc_phase_regroup': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_relu_bf16': (_I, [_P, _I, _I, _I, _Z, _P]),
     'gcc_seg_head': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    'gcc_fid_resize': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    'gcc_pool3x3': (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'gcc_border_copy': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'gcc_global_avgpool': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'gcc_argmax_channels': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_confusion_hist': (_I, [_P, _P, _Z, _I, _P, _P]),
     'gcc_psnr_workspace': (_Z, []),

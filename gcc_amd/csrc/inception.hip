@@ -1,0 +1,247 @@
+// The streaming kernels around the convolutions of the FID Inception-v3 network (metric/inception.py:166-315;
+// gcc_amd/metric/inception_fid.py drives them):
+//   gcc_fid_resize       NCHW fp32 [N][3][H][W] in [0, 1] -> NHWC bf16 [N][Ho][Wo][8] = 2 bilinear(x) - 1 (align_corners = False,
+//                        no antialiasing: F.interpolate as the network's forward calls it), channels 3 .. 7 zero
+//   gcc_pool3x3          3 x 3 pooling of an NHWC bf16 channel window: max stride 2 padding 0, max stride 1 padding 1 (padding is
+//                        -inf), average stride 1 padding 1 over the taps inside the map (count_include_pad = False)
+//   gcc_border_copy      an NHWC bf16 channel window copied into the middle of a map with a zero border of (ph, pw) pixels, border
+//                        included: a (1, 7) / (7, 1) / (1, 3) / (3, 1) convolution with its own padding is then a padding-0 call
+//   gcc_global_avgpool   the mean over the pixels of an NHWC bf16 channel window in fp32
+// One thread per 16-byte chunk (8 channels) of the DESTINATION: consecutive threads write consecutive chunks of a pixel, then the
+// next pixel.  Every thread owns its outputs: no atomics, no inter-workgroup communication, no grid-wide state.
+#include <math.h>
+#include "common.hpp"
+
+namespace {
+
+constexpr int IN_THREADS = 256;
+
+inline unsigned in_blocks(size_t items, size_t cap = 1u << 20) {
+    const size_t b = (items + IN_THREADS - 1) / IN_THREADS;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+// an NHWC bf16 channel window of C channels at `off` inside pixels of `ld` elements, 16-byte chunks throughout
+inline bool in_window_ok(const void* p, int ld, int off, int C) {
+    return p && ld > 0 && off >= 0 && !(ld & 7) && !(off & 7) && ld >= off + C && !(((uintptr_t)p) & 15);
+}
+
+// torch's area_pixel_compute_source_index (align_corners = False, not cubic): index and the weight of the upper neighbour
+__device__ __forceinline__ void resize_tap(int d, float scale, int in, int& i0, int& i1, float& l1) {
+    float s = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
+    s = s < 0.f ? 0.f : s;
+    i0 = (int)s;
+    if (i0 > in - 1) i0 = in - 1;
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+}
+
+__global__ __launch_bounds__(IN_THREADS) void fid_resize_kernel(const float* __restrict__ x, int H, int W, bf16_t* __restrict__ y,
+                                                                 int ld, int off, int Ho, int Wo, float sh, float sw, size_t total) {
+    const size_t plane = (size_t)H * W, oplane = (size_t)Ho * Wo;
+    for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
+        const size_t n = i / oplane, r = i - n * oplane;
+        const int oy = (int)(r / Wo), ox = (int)(r - (size_t)oy * Wo);
+        int y0, y1, x0, x1;
+        float ly, lx;
+        resize_tap(oy, sh, H, y0, y1, ly);
+        resize_tap(ox, sw, W, x0, x1, lx);
+        const float ky = 1.f - ly, kx = 1.f - lx;
+        float f[8];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float* p = x + (n * 3 + c) * plane;
+            const float a = p[(size_t)y0 * W + x0], b = p[(size_t)y0 * W + x1];
+            const float cc = p[(size_t)y1 * W + x0], d = p[(size_t)y1 * W + x1];
+            const float v = ky * (kx * a + lx * b) + ly * (kx * cc + lx * d);
+            f[c] = 2.f * v - 1.f;
+        }
+#pragma unroll
+        for (int c = 3; c < 8; c++) f[c] = 0.f;
+        *(i32x4*)(y + i * ld + off) = pack8(f);
+    }
+}
+
+// MODE: GCC_POOL3_MAX_S2 / GCC_POOL3_MAX_S1P1 / GCC_POOL3_AVG_S1P1.  Taps are visited row by row, left to right (torch's order:
+// of equal maxima the first met stays, a NaN wins); the average sums in fp32 in that order and divides by the taps inside the map.
+template <int MODE>
+__global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const bf16_t* __restrict__ x, int ldx, int xoff, bf16_t* __restrict__ y,
+                                                              int ldy, int yoff, int H, int W, int Ho, int Wo, int chunks, size_t total) {
+    constexpr int S = MODE == GCC_POOL3_MAX_S2 ? 2 : 1, P = MODE == GCC_POOL3_MAX_S2 ? 0 : 1;
+    for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
+        const size_t dp = i / chunks;
+        const int ch = (int)(i - dp * chunks);
+        size_t t = dp;
+        const int ox = (int)(t % Wo); t /= Wo;
+        const int oy = (int)(t % Ho); t /= Ho;
+        const size_t n = t;
+        float acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc[j] = MODE == GCC_POOL3_AVG_S1P1 ? 0.f : -INFINITY;
+        int count = 0;
+#pragma unroll
+        for (int ky = 0; ky < 3; ky++) {
+            const int iy = oy * S - P + ky;
+            if ((unsigned)iy >= (unsigned)H) continue;
+#pragma unroll
+            for (int kx = 0; kx < 3; kx++) {
+                const int ix = ox * S - P + kx;
+                if ((unsigned)ix >= (unsigned)W) continue;
+                float f[8];
+                unpack8(*(const i32x4*)(x + ((n * H + iy) * W + ix) * ldx + xoff + ch * 8), f);
+                count++;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    if (MODE == GCC_POOL3_AVG_S1P1) acc[j] += f[j];
+                    else if (f[j] > acc[j] || f[j] != f[j]) acc[j] = f[j];
+                }
+            }
+        }
+        if (MODE == GCC_POOL3_AVG_S1P1) {
+            const float cnt = (float)count;       // >= 1: the centre tap is always inside
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc[j] = acc[j] / cnt;
+        }
+        *(i32x4*)(y + dp * ldy + yoff + ch * 8) = pack8(acc);
+    }
+}
+
+__global__ __launch_bounds__(IN_THREADS) void border_copy_kernel(const bf16_t* __restrict__ src, int lds, int soff,
+                                                                  bf16_t* __restrict__ dst, int ldd, int doff, int H, int W, int ph,
+                                                                  int pw, int chunks, size_t total) {
+    const int Hd = H + 2 * ph, Wd = W + 2 * pw;
+    for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
+        const size_t dp = i / chunks;
+        const int ch = (int)(i - dp * chunks);
+        size_t t = dp;
+        const int wd = (int)(t % Wd); t /= Wd;
+        const int hd = (int)(t % Hd); t /= Hd;
+        const size_t n = t;
+        const int h = hd - ph, w = wd - pw;
+        i32x4 v = {0, 0, 0, 0};
+        if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) v = *(const i32x4*)(src + ((n * H + h) * W + w) * lds + soff + ch * 8);
+        *(i32x4*)(dst + dp * ldd + doff + ch * 8) = v;
+    }
+}
+
+// out[n][c] = (sum over the pixels of x[n][.][c]) / pixels: eight fp32 partial sums (pixel p goes to partial p mod 8), added as
+// ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) -- the order is fixed by the shape alone, and a sum of 64 terms takes 10 roundings
+__global__ __launch_bounds__(IN_THREADS) void global_avgpool_kernel(const bf16_t* __restrict__ x, int ld, int off, int pixels, int C,
+                                                                     int chunks, float* __restrict__ out, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
+        const size_t n = i / chunks;
+        const int ch = (int)(i - n * chunks);
+        const bf16_t* p = x + n * pixels * ld + off + ch * 8;
+        float part[8][8];
+#pragma unroll
+        for (int a = 0; a < 8; a++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) part[a][j] = 0.f;
+        int q = 0;
+        for (; q + 8 <= pixels; q += 8) {
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                float f[8];
+                unpack8(*(const i32x4*)(p + (size_t)(q + a) * ld), f);
+#pragma unroll
+                for (int j = 0; j < 8; j++) part[a][j] += f[j];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 8; a++) {
+            if (q + a < pixels) {
+                float f[8];
+                unpack8(*(const i32x4*)(p + (size_t)(q + a) * ld), f);
+#pragma unroll
+                for (int j = 0; j < 8; j++) part[a][j] += f[j];
+            }
+        }
+        const float cnt = (float)pixels;
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++)
+            o[j] = (((part[0][j] + part[1][j]) + (part[2][j] + part[3][j])) + ((part[4][j] + part[5][j]) + (part[6][j] + part[7][j]))) / cnt;
+        float* op = out + n * C + ch * 8;
+        *(f32x4*)op = f32x4{o[0], o[1], o[2], o[3]};
+        *(f32x4*)(op + 4) = f32x4{o[4], o[5], o[6], o[7]};
+    }
+}
+
+}  // namespace
+
+extern "C" int gcc_fid_resize(const float* x, int N, int H, int W, void* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!x || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(y, ld, off, 8) || (((uintptr_t)x) & 3)) return GCC_ERR_BAD_ARG;
+    const size_t total = (size_t)N * Ho * Wo;
+    if ((size_t)N * 3 * H * W >= (size_t)1 << 40 || total >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    // torch's area_pixel_compute_scale<float>: the ratio of the sizes in fp32
+    const float sh = (float)H / (float)Ho, sw = (float)W / (float)Wo;
+    hipLaunchKernelGGL(fid_resize_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, x, H, W, (bf16_t*)y, ld,
+                       off, Ho, Wo, sh, sw, total);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_pool3x3(int mode, const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int N, int H, int W, int C,
+                           gcc_stream_t stream) {
+    GCC_ENTER();
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return GCC_ERR_BAD_ARG;
+    if (mode != GCC_POOL3_MAX_S2 && mode != GCC_POOL3_MAX_S1P1 && mode != GCC_POOL3_AVG_S1P1) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(x, ldx, xoff, ceil8(C)) || !in_window_ok(y, ldy, yoff, ceil8(C))) return GCC_ERR_BAD_ARG;
+    if (C & 7) return GCC_ERR_UNSUPPORTED;
+    int Ho = H, Wo = W;
+    if (mode == GCC_POOL3_MAX_S2) {
+        if (H < 3 || W < 3) return GCC_ERR_UNSUPPORTED;            // no output pixel
+        Ho = (H - 3) / 2 + 1; Wo = (W - 3) / 2 + 1;
+    }
+    const int chunks = C / 8;
+    const size_t total = (size_t)N * Ho * Wo * chunks;
+    if ((size_t)N * H * W * ldx >= (size_t)1 << 40 || (size_t)N * Ho * Wo * ldy >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(in_blocks(total)), block(IN_THREADS);
+    const bf16_t* xp = (const bf16_t*)x;
+    bf16_t* yp = (bf16_t*)y;
+    if (mode == GCC_POOL3_MAX_S2)
+        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_MAX_S2>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+    else if (mode == GCC_POOL3_MAX_S1P1)
+        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_MAX_S1P1>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+    else
+        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_AVG_S1P1>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_border_copy(const void* src, int lds, int soff, void* dst, int ldd, int doff, int N, int H, int W, int C, int ph,
+                               int pw, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || ph < 0 || pw < 0) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(src, lds, soff, ceil8(C)) || !in_window_ok(dst, ldd, doff, ceil8(C))) return GCC_ERR_BAD_ARG;
+    if (C & 7) return GCC_ERR_UNSUPPORTED;
+    if (ph > (1 << 15) || pw > (1 << 15)) return GCC_ERR_UNSUPPORTED;
+    const size_t spix = (size_t)N * H * W, dpix = (size_t)N * (H + 2 * ph) * (W + 2 * pw);
+    if (spix * lds >= (size_t)1 << 40 || dpix * ldd >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    {   // never in place: a destination pixel is another source pixel's address
+        const char* a = (const char*)src; const char* b = (const char*)dst;
+        if (a < b + dpix * ldd * 2 && b < a + spix * lds * 2) return GCC_ERR_BAD_ARG;
+    }
+    const int chunks = C / 8;
+    const size_t total = dpix * chunks;
+    hipLaunchKernelGGL(border_copy_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, (const bf16_t*)src, lds,
+                       soff, (bf16_t*)dst, ldd, doff, H, W, ph, pw, chunks, total);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_global_avgpool(const void* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!out || N <= 0 || h <= 0 || w <= 0 || C <= 0) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(x, ld, off, ceil8(C)) || (((uintptr_t)out) & 15)) return GCC_ERR_BAD_ARG;
+    if (C & 7) return GCC_ERR_UNSUPPORTED;
+    if ((size_t)h * w >= (size_t)1 << 24 || (size_t)N * h * w * ld >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    const int chunks = C / 8;
+    const size_t total = (size_t)N * chunks;
+    hipLaunchKernelGGL(global_avgpool_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, ld,
+                       off, h * w, C, chunks, out, total);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}

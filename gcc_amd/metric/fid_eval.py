@@ -1,7 +1,8 @@
 """FID of a Pix2Pix (any root but Cityscapes), CycleGAN or SAGAN generator (metric/test_metric.py:15-45 test_pix2pix_fid, 129-161
 test_sagan_fid, 163-204 test_cyclegan_fid): everything around the Inception network.  The network stays an external input, as
-DRN does for the Cityscapes mIoU: ``GCC_FID_INCEPTION`` names a TorchScript archive of the reference's InceptionV3([3]) (exported
-once with torch.jit where its weights live), or any callable with its contract -- NCHW fp32 in [0, 1] at the generator's
+DRN does for the Cityscapes mIoU: ``GCC_FID_INCEPTION`` names the reference's own weight file (the plain state_dict of
+fid_inception_v3(), run natively by inception_fid.InceptionFidEngine) or a TorchScript archive of the reference's InceptionV3([3])
+(exported once with torch.jit where its weights live); fid_evaluator takes any callable with its contract -- NCHW fp32 in [0, 1] at the generator's
 resolution in (resizing and normalisation are the network's own), element 0 of the result [N, d, h, w] fp32 out, averaged over
 (h, w) when not 1 x 1.
 
@@ -214,8 +215,25 @@ def fid_evaluator(inception, logger=None, batch_size=50):
     return evaluate
 
 
+def _native_inception(path):
+    """(InceptionFidEngine on the host, None) when `path` is the reference's own weight file -- the plain state_dict of
+    fid_inception_v3() --, (None, why) when it is one this package does not run, (None, None) for any other file"""
+    from .inception_fid import InceptionFidEngine, is_fid_inception_state_dict
+    try:
+        sd = torch.load(path, map_location='cpu', weights_only=True)
+    except Exception:
+        return None, None
+    if not is_fid_inception_state_dict(sd):
+        return None, None
+    try:
+        return InceptionFidEngine(sd), None
+    except GccError as e:
+        return None, '%s %s holds an Inception state_dict this package does not run: %s' % (ENV, path, e)
+
+
 def load_inception():
-    """(module, None) from the TorchScript archive GCC_FID_INCEPTION names, else (None, the condition that failed)"""
+    """(network, None) from the file GCC_FID_INCEPTION names -- a TorchScript archive of InceptionV3([3]), or the reference's own
+    pt_inception weight file (a plain state_dict: InceptionFidEngine runs it natively) --, else (None, the condition that failed)"""
     path = os.environ.get(ENV)
     if not path:
         return None, '%s is not set (the path of a TorchScript archive of the Inception network)' % ENV
@@ -225,12 +243,15 @@ def load_inception():
         return torch.jit.load(path, map_location='cpu'), None
     except Exception as e:
         first = (str(e).strip().splitlines() or [type(e).__name__])[0]
+        engine, refusal = _native_inception(path)
+        if engine is not None or refusal is not None:
+            return engine, refusal
         return None, 'torch.jit.load could not read %s %s as a TorchScript archive (%s: %s); a plain state_dict needs the ' \
                      'network\'s code: export InceptionV3([3]) with torch.jit once' % (ENV, path, type(e).__name__, first)
 
 
 def builtin_inception(opt):
-    """for a run whose evaluation is FID (wants_fid): (network, None) when GCC_FID_INCEPTION names a TorchScript archive and
+    """for a run whose evaluation is FID (wants_fid): (network, None) when GCC_FID_INCEPTION names a network file (load_inception) and
     --dataroot holds the real statistics the model's slots need, else (None, the condition that failed)"""
     module, why = load_inception()
     if module is None:

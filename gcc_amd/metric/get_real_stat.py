@@ -7,7 +7,7 @@ dataset's real images, the real_stat*.npz a FID evaluation compares against.
         --output_path ./database/celeb/real_stat.npz
 
 The reference's arguments and defaults; ``--dataset_mode unaligned`` is accepted as well (domain B for AtoB, A for BtoA), so
-that CycleGAN roots get theirs.  The network is the TorchScript archive GCC_FID_INCEPTION names (gcc_amd.metric.fid_eval).
+that CycleGAN roots get theirs.  The network is the file GCC_FID_INCEPTION names: the reference's weight file or a TorchScript archive (gcc_amd.metric.fid_eval).
 Images are read through gcc_amd.data, keyed by path (a repeated path counts once), turned into the network's input by
 gcc_fid_input -- util.tensor2imgs' byte of the loader's [-1, 1] tensor over 255, exactly: 63 of the 256 byte values come back
 one lower from that round trip, and the reference's statistics are statistics of those bytes -- and go through the network at

@@ -1,0 +1,411 @@
+"""The FID Inception-v3 network (metric/inception.py:166-315 fid_inception_v3 under InceptionV3([3]): torchvision's
+Inception3(num_classes=1008, aux_logits=False) with the FID patches) from the reference's own weight file, a plain state_dict
+(pt_inception-2015-12-05-6726825d.pth), on the library's inference convolutions.
+
+    x NCHW fp32 in [0, 1] -> gcc_fid_resize (bilinear to resize x resize, 2 x - 1, NHWC bf16)
+        -> stem, Mixed_5b .. Mixed_7c: gcc_conv_eval_ex (conv + folded BatchNorm (eps 1e-3) + ReLU), gcc_pool3x3; every branch's
+           last conv writes its channel slice of the block's output, so no concatenation is ever copied
+        -> gcc_global_avgpool -> [N, d, 1, 1] fp32
+
+gcc_conv_t has one padding for both directions, so the (1, 7) / (7, 1) / (1, 3) / (3, 1) convolutions run as gcc_border_copy (the
+input inside its own zero border) and a padding-0 call with KH != KW.  Mixed_7c's pooling branch is a MAX pool: the FID network's
+known quirk (metric/inception.py:301-304), kept.
+
+Every width is read from the shapes: the only constraints are that concatenations match and that widths are multiples of 8, so a
+thin seeded network runs through the same code as the real one.  Construction parses the state_dict on the host (no device, no
+library); .to(device) packs the weights and folds the BatchNorms once -- the weights of an evaluator never change."""
+from types import SimpleNamespace
+
+import torch
+
+from .._lib import GccError
+
+BN_FIELDS = ('weight', 'bias', 'running_mean', 'running_var')
+BN_EPS = 1e-3                                        # BasicConv2d's BatchNorm2d(eps=0.001): a state_dict does not carry it
+UNUSED_KEYS = ('fc.weight', 'fc.bias')
+MAX_S2, MAX_S1P1, AVG_S1P1 = 0, 1, 2                 # _lib.POOL3_*
+WHAT = 'FID Inception state_dict'
+
+
+def _c(name, k=1, stride=1, pad=0):
+    """a BasicConv2d: name, (kh, kw), stride, (ph, pw)"""
+    k = (k, k) if isinstance(k, int) else k
+    pad = (pad, pad) if isinstance(pad, int) else pad
+    return SimpleNamespace(name=name, k=k, stride=stride, pad=pad, key=name + '.conv.weight', bn=name + '.bn', co=0, ci=0)
+
+
+def _branch(pre=None, chain=(), tails=()):
+    """one branch of a block: an optional pool of the block's input, convs into temporaries, then `tails`, each a conv of the
+    chain's result into the next channel slice of the block's output (no tails: the pool itself is the slice)"""
+    return SimpleNamespace(pre=pre, chain=list(chain), tails=list(tails))
+
+
+def _block_a(p):
+    return [_branch(tails=[_c(p + 'branch1x1')]),
+            _branch(chain=[_c(p + 'branch5x5_1')], tails=[_c(p + 'branch5x5_2', 5, pad=2)]),
+            _branch(chain=[_c(p + 'branch3x3dbl_1'), _c(p + 'branch3x3dbl_2', 3, pad=1)], tails=[_c(p + 'branch3x3dbl_3', 3, pad=1)]),
+            _branch(pre=AVG_S1P1, tails=[_c(p + 'branch_pool')])]
+
+
+def _block_b(p):
+    return [_branch(tails=[_c(p + 'branch3x3', 3, 2)]),
+            _branch(chain=[_c(p + 'branch3x3dbl_1'), _c(p + 'branch3x3dbl_2', 3, pad=1)], tails=[_c(p + 'branch3x3dbl_3', 3, 2)]),
+            _branch(pre=MAX_S2)]
+
+
+def _block_c(p):
+    r, c = dict(k=(1, 7), pad=(0, 3)), dict(k=(7, 1), pad=(3, 0))
+    return [_branch(tails=[_c(p + 'branch1x1')]),
+            _branch(chain=[_c(p + 'branch7x7_1'), _c(p + 'branch7x7_2', **r)], tails=[_c(p + 'branch7x7_3', **c)]),
+            _branch(chain=[_c(p + 'branch7x7dbl_1'), _c(p + 'branch7x7dbl_2', **c), _c(p + 'branch7x7dbl_3', **r),
+                           _c(p + 'branch7x7dbl_4', **c)], tails=[_c(p + 'branch7x7dbl_5', **r)]),
+            _branch(pre=AVG_S1P1, tails=[_c(p + 'branch_pool')])]
+
+
+def _block_d(p):
+    return [_branch(chain=[_c(p + 'branch3x3_1')], tails=[_c(p + 'branch3x3_2', 3, 2)]),
+            _branch(chain=[_c(p + 'branch7x7x3_1'), _c(p + 'branch7x7x3_2', (1, 7), pad=(0, 3)),
+                           _c(p + 'branch7x7x3_3', (7, 1), pad=(3, 0))], tails=[_c(p + 'branch7x7x3_4', 3, 2)]),
+            _branch(pre=MAX_S2)]
+
+
+def _block_e(p, pool):
+    r, c = dict(k=(1, 3), pad=(0, 1)), dict(k=(3, 1), pad=(1, 0))
+    return [_branch(tails=[_c(p + 'branch1x1')]),
+            _branch(chain=[_c(p + 'branch3x3_1')], tails=[_c(p + 'branch3x3_2a', **r), _c(p + 'branch3x3_2b', **c)]),
+            _branch(chain=[_c(p + 'branch3x3dbl_1'), _c(p + 'branch3x3dbl_2', 3, pad=1)],
+                    tails=[_c(p + 'branch3x3dbl_3a', **r), _c(p + 'branch3x3dbl_3b', **c)]),
+            _branch(pre=pool, tails=[_c(p + 'branch_pool')])]
+
+
+def _network():
+    """the module tree: a list of ('conv', _c) / ('pool', mode) / ('block', name, branches)"""
+    net = [('conv', _c('Conv2d_1a_3x3', 3, 2)), ('conv', _c('Conv2d_2a_3x3', 3)), ('conv', _c('Conv2d_2b_3x3', 3, pad=1)),
+           ('pool', MAX_S2), ('conv', _c('Conv2d_3b_1x1')), ('conv', _c('Conv2d_4a_3x3', 3)), ('pool', MAX_S2)]
+    for n in ('Mixed_5b', 'Mixed_5c', 'Mixed_5d'):
+        net.append(('block', n, _block_a(n + '.')))
+    net.append(('block', 'Mixed_6a', _block_b('Mixed_6a.')))
+    for n in ('Mixed_6b', 'Mixed_6c', 'Mixed_6d', 'Mixed_6e'):
+        net.append(('block', n, _block_c(n + '.')))
+    net.append(('block', 'Mixed_7a', _block_d('Mixed_7a.')))
+    net.append(('block', 'Mixed_7b', _block_e('Mixed_7b.', AVG_S1P1)))
+    net.append(('block', 'Mixed_7c', _block_e('Mixed_7c.', MAX_S1P1)))          # the FID network's max pool
+    return net
+
+
+def _net_convs(net):
+    out = []
+    for item in net:
+        if item[0] == 'conv':
+            out.append(item[1])
+        elif item[0] == 'block':
+            for b in item[2]:
+                out.extend(b.chain)
+                out.extend(b.tails)
+    return out
+
+
+def _shape(v):
+    return tuple(v.shape) if hasattr(v, 'shape') else tuple(v)
+
+
+def is_fid_inception_state_dict(sd):
+    """an Inception3 state_dict by its keys (the first and the last convolution of the FID network)"""
+    return isinstance(sd, dict) and 'Conv2d_1a_3x3.conv.weight' in sd and 'Mixed_7c.branch_pool.conv.weight' in sd
+
+
+def parse_fid_inception(sd):
+    """the architecture of a fid_inception_v3 state_dict (values: tensors, or bare shapes) from its keys and shapes:
+    SimpleNamespace(net (the module tree with every conv's ci / co filled in), convs (in launch order), widths {block: output
+    channels}, d (the feature width)).  Raises GccError naming the first key that does not belong or does not fit."""
+    if not isinstance(sd, dict):
+        raise GccError('%s: expected a dict, got %s' % (WHAT, type(sd).__name__))
+    net = _network()
+    convs = _net_convs(net)
+    known = set(UNUSED_KEYS)
+    for c in convs:
+        known.add(c.key)
+        known.update('%s.%s' % (c.bn, f) for f in BN_FIELDS + ('num_batches_tracked',))
+    for key in sd:
+        if key not in known:
+            raise GccError('%s: unknown key %s' % (WHAT, key))
+
+    def read(c, cin):
+        if c.key not in sd:
+            raise GccError('%s: %s is missing' % (WHAT, c.key))
+        s = _shape(sd[c.key])
+        if len(s) != 4 or s[2:] != c.k:
+            raise GccError('%s: %s has shape %s, expected a %d x %d convolution' % (WHAT, c.key, s, c.k[0], c.k[1]))
+        c.co, c.ci = s[0], s[1]
+        if c.ci != cin:
+            raise GccError('%s: %s takes %d channels, the layer before it gives %d' % (WHAT, c.key, c.ci, cin))
+        if c.co % 8 or c.co <= 0:
+            raise GccError('%s: %s has %d output channels; widths must be multiples of 8' % (WHAT, c.key, c.co))
+        for f in BN_FIELDS:
+            k = '%s.%s' % (c.bn, f)
+            if k not in sd:
+                raise GccError('%s: %s is missing (BatchNorm behind %s)' % (WHAT, k, c.key))
+            if _shape(sd[k]) != (c.co,):
+                raise GccError('%s: %s has shape %s, expected (%d,)' % (WHAT, k, _shape(sd[k]), c.co))
+        return c.co
+
+    cin, widths = 3, {}
+    for item in net:
+        if item[0] == 'conv':
+            cin = read(item[1], cin)
+        elif item[0] == 'block':
+            total = 0
+            for b in item[2]:
+                cur = cin
+                for c in b.chain:
+                    cur = read(c, cur)
+                total += sum(read(c, cur) for c in b.tails) if b.tails else cur
+            widths[item[1]] = cin = total                 # every slice offset is a sum of multiples of 8 (cin of a pool: checked above)
+    return SimpleNamespace(net=net, convs=convs, widths=widths, d=cin)
+
+
+def _out(size, k, stride, pad):
+    return (size + 2 * pad - k) // stride + 1
+
+
+class InceptionFidEngine:
+    """inception(x)[0] for fid_eval.ImageStatistics: x NCHW fp32 [N, 3, H, W] in [0, 1] on the device, any H, W -> [features],
+    features fp32 [N, d, 1, 1] (d = 2048 for the real network), InceptionV3([3]).forward's list.  Activations are NHWC bf16 with
+    one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic."""
+
+    def __init__(self, state_dict, resize=299):
+        self.arch = parse_fid_inception(state_dict)
+        self.convs = self.arch.convs
+        self.d = self.arch.d
+        self.resize = int(resize)
+        if self.resize <= 0:
+            raise GccError('InceptionFidEngine: resize must be positive, got %r' % (resize,))
+        keys = set(c.key for c in self.convs) | set('%s.%s' % (c.bn, f) for c in self.convs for f in BN_FIELDS)
+        self.host = {k: state_dict[k].detach().to('cpu', torch.float32).contiguous() for k in keys}
+        self._plan(1)                                  # a resize too small for the network is refused here, on the host
+        self.device = None
+        self._slab, self._programs = None, {}
+
+    # ---- host -> device: once -------------------------------------------------------------------------------------------
+    def to(self, device):
+        from .. import ops
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise GccError('InceptionFidEngine runs on the GPU only (asked for %s)' % device)
+        if device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if self.device == device:
+            return self
+        self.device = device
+        self._slab, self._programs = None, {}
+        with torch.cuda.device(device):
+            n = sum(c.co for c in self.convs)
+            bn = torch.empty((4, n), dtype=torch.float32)
+            off = 0
+            for c in self.convs:
+                for i, f in enumerate(BN_FIELDS):
+                    bn[i, off:off + c.co] = self.host['%s.%s' % (c.bn, f)]
+                off += c.co
+            self._bn = bn.to(device)
+            entries, off = [], 0
+            for c in self.convs:
+                g, b, rm, rv = (self._bn[i, off:off + c.co] for i in range(4))
+                entries.append((SimpleNamespace(weight=g, bias=b, running_mean=rm, running_var=rv, eps=BN_EPS), None, c.co))
+                off += c.co
+                master = self.host[c.key].to(device).contiguous(memory_format=torch.channels_last)
+                c.w, _ = ops.pack_weights(master, want_w=True, want_wt=False)
+            self._table = ops.BNEvalTable(entries, device)
+            self._table.run()                          # scale = gamma / sqrt(var + 1e-3), shift = beta - mean scale, fp32
+            for i, c in enumerate(self.convs):
+                c.scale, c.shift = self._table.scale[i], self._table.shift[i]
+        return self
+
+    def eval(self):
+        return self
+
+    # ---- the launch program ---------------------------------------------------------------------------------------------
+    def _plan(self, N):
+        """the launches of a batch of N as tuples over symbolic activations of the slab: behind the 8-channel resized input, four
+        regions -- a block's input and output, which swap from layer to layer, and two temporaries the branches alternate between.
+        The input's own H and W appear in no launch but gcc_fid_resize, so a program depends on N alone."""
+        steps, sizes, where = [], [], ['the input']
+        R = self.resize
+        reg = SimpleNamespace(x=0, y=1, t1=2, t2=3)
+
+        def act(Cc, h, w, region, ld=None, off=0):
+            if h <= 0 or w <= 0:
+                raise GccError('InceptionFidEngine: resize = %d leaves no pixel at %s' % (R, where[0]))
+            ld = ld or Cc
+            if off == 0:
+                sizes.append(N * h * w * ld)
+            return SimpleNamespace(C=Cc, h=h, w=w, region=region, ld=ld, off=off, view=None)
+
+        def free(a):
+            """the temporary `a` is not in"""
+            return reg.t2 if a.region == reg.t1 else reg.t1
+
+        def apply(c, cur, dst=None):
+            """conv c of `cur` into the slice `dst`, or into a fresh activation of the temporary that is free.  A rectangular
+            kernel's padding is a zero border first (in the temporary `cur` is not in: `cur` may have other readers)."""
+            where[0] = c.key
+            ph, pw = c.pad
+            if c.k[0] != c.k[1]:
+                b = act(cur.C, cur.h + 2 * ph, cur.w + 2 * pw, free(cur))
+                steps.append(('border', cur, b, ph, pw))
+                cur, ph, pw = b, 0, 0
+            ho, wo = _out(cur.h, c.k[0], c.stride, ph), _out(cur.w, c.k[1], c.stride, pw)
+            if dst is None:
+                dst = act(c.co, ho, wo, free(cur))
+            elif (dst.h, dst.w) != (ho, wo):
+                raise GccError('InceptionFidEngine: %s gives %d x %d, its block %d x %d' % (c.key, ho, wo, dst.h, dst.w))
+            steps.append(('conv', c, cur, dst))
+            return dst
+
+        def pool(mode, cur, dst):
+            steps.append(('pool', mode, cur, dst))
+            return dst
+
+        x = SimpleNamespace(C=3, h=R, w=R, region=-1, ld=8, off=0, view=None)
+        for item in self.arch.net:
+            if item[0] == 'conv':
+                c = item[1]
+                where[0] = c.key
+                y = apply(c, x, act(c.co, _out(x.h, c.k[0], c.stride, c.pad[0]), _out(x.w, c.k[1], c.stride, c.pad[1]), reg.y))
+            elif item[0] == 'pool':
+                where[0] = 'the stem\'s max pool'
+                y = pool(item[1], x, act(x.C, _out(x.h, 3, 2, 0), _out(x.w, 3, 2, 0), reg.y))
+            else:
+                name, branches = item[1], item[2]
+                where[0] = name
+                s2 = any(b.pre == MAX_S2 for b in branches)
+                ho, wo = (_out(x.h, 3, 2, 0), _out(x.w, 3, 2, 0)) if s2 else (x.h, x.w)
+                width = self.arch.widths[name]
+                y = act(width, ho, wo, reg.y)
+                off = 0
+                for b in branches:
+                    cur = x
+                    if b.pre is not None and not b.tails:                      # the pool is the slice
+                        pool(b.pre, x, act(x.C, ho, wo, reg.y, width, off))
+                        off += x.C
+                        continue
+                    if b.pre is not None:
+                        cur = pool(b.pre, x, act(x.C, x.h, x.w, reg.t1))
+                    for c in b.chain:
+                        cur = apply(c, cur)
+                    for c in b.tails:
+                        if off % 8:
+                            raise GccError('InceptionFidEngine: %s would be written at channel %d of %s' % (c.key, off, name))
+                        apply(c, cur, act(c.co, ho, wo, reg.y, width, off))
+                        off += c.co
+                if off != width:
+                    raise GccError('InceptionFidEngine: %s concatenates %d channels, expected %d' % (name, off, width))
+            x, reg.x, reg.y = y, reg.y, reg.x
+        return SimpleNamespace(steps=steps, size_in=N * R * R * 8, size_r=max(sizes), last=x, slab=None, x_in=None,
+                               total=N * R * R * 8 + 4 * max(sizes))
+
+    def _program(self, N):
+        prog = self._programs.get(N)
+        if prog is None:
+            prog = self._programs[N] = self._plan(N)
+        return prog
+
+    def _bind(self, N):
+        """the program of a batch size with its views of the slab.  The slab only grows; when it is replaced, the programs bound
+        to the old one are dropped with it (their views would keep it alive) and made again on their next use."""
+        prog = self._program(N)
+        if self._slab is None or self._slab.numel() < prog.total:
+            self._slab, self._programs = None, {}
+            self._slab = torch.zeros(prog.total, dtype=torch.bfloat16, device=self.device)
+            prog = self._program(N)
+        if prog.slab is self._slab:
+            return prog
+        slab = self._slab
+
+        def view(a):
+            if a.view is None:
+                base = 0 if a.region < 0 else prog.size_in + a.region * prog.size_r
+                if a.off % 8 or a.ld % 8:
+                    raise GccError('InceptionFidEngine: a channel slice at %d of %d is off the 8-channel grid' % (a.off, a.ld))
+                a.view = slab[base:base + N * a.h * a.w * a.ld].view(N, a.h, a.w, a.ld).permute(0, 3, 1, 2)[:, a.off:a.off + a.C]
+            return a.view
+        for st in prog.steps:
+            for a in st[1:]:
+                if isinstance(a, SimpleNamespace) and hasattr(a, 'region'):
+                    view(a)
+        view(prog.last)
+        prog.x_in = prog.steps[0][2].view               # the first conv's source: 3 channels in an ld of 8, ahead of the regions
+        prog.slab = slab
+        self._check_routes(prog)
+        return prog
+
+    def _conv(self, c, src, dst, route_only=False):
+        from .. import _lib, ops
+        kw = dict(slot='inception_eval', route_only=route_only)
+        if not route_only:
+            kw.update(scale=c.scale, shift=c.shift, act=_lib.EVAL_ACT_RELU)
+        if c.k[0] != c.k[1]:
+            return ops.conv_eval_rect(src.view, c.w, c.co, c.k, c.stride, dst.view, **kw)
+        return ops.conv_eval_ex(src.view, c.w, c.co, c.k[0], c.stride, c.pad[0], dst.view, **kw)
+
+    def _check_routes(self, prog):
+        """every conv geometry asked of the library before anything runs: a declined one names its layer; there is no other route"""
+        import ctypes as C
+        from .. import ops
+        for st in prog.steps:
+            if st[0] != 'conv':
+                continue
+            _, c, src, dst = st
+            _, Nb, Ci, h, w, ldx = ops.geom(src.view)
+            square = c.k[0] == c.k[1]
+            d = ops.conv_desc(Nb, h, w, Ci, c.co, c.k[0], c.stride, c.pad[0] if square else 0, ldx, ops.geom(dst.view)[5])
+            d.KW = c.k[1]
+            if ops.lib().gcc_conv_eval_ex_route(C.byref(d), 0, 0) < 0:
+                raise GccError('InceptionFidEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, '
+                               'on %d x %d x %d): there is no other route' % (c.key, c.ci, c.co, c.k[0], c.k[1], c.stride, Nb, h, w))
+
+    def _run(self, x, N, count_only=False):
+        from .. import ops
+        if self.device is None:
+            raise GccError('InceptionFidEngine: .to(device) first')
+        prog = self._bind(N)
+        if count_only:
+            return 2 + sum(self._conv(*st[1:], route_only=True) if st[0] == 'conv' else 1 for st in prog.steps)
+        ops.fid_resize(x, prog.x_in)
+        for st in prog.steps:
+            kind = st[0]
+            if kind == 'conv':
+                try:
+                    self._conv(*st[1:])
+                except GccError as e:
+                    raise GccError('InceptionFidEngine: %s: %s' % (st[1].key, e))
+            elif kind == 'pool':
+                ops.pool3x3(st[1], st[2].view, st[3].view)
+            else:
+                ops.border_copy(st[1].view, st[2].view, st[3], st[4])
+        out = torch.empty((N, self.d, 1, 1), dtype=torch.float32, device=self.device)
+        ops.global_avgpool(prog.last.view, out)
+        return [out]
+
+    def __call__(self, x):
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or 0 in x.shape:
+            raise GccError('InceptionFidEngine: expected an NCHW fp32 [N, 3, H, W] tensor, got %s %s'
+                           % (getattr(x, 'dtype', type(x).__name__), tuple(getattr(x, 'shape', ()))))
+        if self.device is None:
+            raise GccError('InceptionFidEngine: .to(device) first')
+        if x.device != self.device:
+            raise GccError('InceptionFidEngine: the input is on %s, the engine on %s' % (x.device, self.device))
+        return self._run(x.contiguous(), x.shape[0])
+
+    def infer_launches(self, N, H=None, W=None):
+        """kernel launches of one call on an [N, 3, H, W] input, from the library's route introspection (launches nothing); the
+        input's size changes the resize kernel's work, not the count"""
+        return self._run(None, N, count_only=True)
+
+    def flops(self):
+        """multiply-adds x 2 of one image from the shapes (convolutions only; the streaming kernels not counted)"""
+        total = 0
+        for st in self._program(1).steps:
+            if st[0] == 'conv':
+                _, c, _, dst = st
+                total += 2 * dst.h * dst.w * c.co * c.ci * c.k[0] * c.k[1]
+        return total

@@ -900,6 +900,75 @@ def relu_(x):
     return x
 
 
+def fid_resize(x, out):
+    """gcc_fid_resize: NCHW fp32 [N, 3, H, W] in [0, 1] -> 2 bilinear(x) - 1 at the size of `out`, an NHWC bf16 view of 3
+    channels in an ld of at least 8 (channels 3 .. 7 of each pixel are written as zeros)"""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise _lib.GccError('fid_resize: expected a contiguous NCHW fp32 [N, 3, H, W] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+    N, _, H, W = x.shape
+    yp, Ny, Cy, Ho, Wo, ld = geom(out)
+    if Ny != N or Cy != 3:
+        raise _lib.GccError('fid_resize: %s into %s' % (tuple(x.shape), tuple(out.shape)))
+    check(lib().gcc_fid_resize(x.data_ptr(), N, H, W, yp, ld, 0, Ho, Wo, stream()), 'gcc_fid_resize')
+    return out
+
+
+def pool3x3(mode, x, out):
+    """gcc_pool3x3 (mode: _lib.POOL3_*) of an NHWC bf16 view into another of the same channels (a channel slice works)"""
+    xp, N, Cc, H, W, ldx = geom(x)
+    yp, Ny, Cy, Ho, Wo, ldy = geom(out)
+    want = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == _lib.POOL3_MAX_S2 else (H, W)
+    if (Ny, Cy, Ho, Wo) != (N, Cc) + want:
+        raise _lib.GccError('pool3x3 mode %d: %s into %s' % (mode, tuple(x.shape), tuple(out.shape)))
+    check(lib().gcc_pool3x3(mode, xp, ldx, 0, yp, ldy, 0, N, H, W, Cc, stream()), 'gcc_pool3x3')
+    return out
+
+
+def border_copy(src, dst, ph, pw):
+    """gcc_border_copy: dst [N, C, H + 2 ph, W + 2 pw] = src [N, C, H, W] inside a border of zeros (written too)"""
+    sp, N, Cc, H, W, lds = geom(src)
+    dp, Nd, Cd, Hd, Wd, ldd = geom(dst)
+    if (Nd, Cd, Hd, Wd) != (N, Cc, H + 2 * ph, W + 2 * pw):
+        raise _lib.GccError('border_copy (%d, %d): %s into %s' % (ph, pw, tuple(src.shape), tuple(dst.shape)))
+    check(lib().gcc_border_copy(sp, lds, 0, dp, ldd, 0, N, H, W, Cc, ph, pw, stream()), 'gcc_border_copy')
+    return dst
+
+
+def global_avgpool(x, out=None):
+    """gcc_global_avgpool: fp32 [N, C] mean over the pixels of an NHWC bf16 view"""
+    xp, N, Cc, h, w, ld = geom(x)
+    if out is None:
+        out = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.numel() != N * Cc or not out.is_contiguous():
+        raise _lib.GccError('global_avgpool: out must be a contiguous fp32 tensor of %d x %d elements' % (N, Cc))
+    check(lib().gcc_global_avgpool(xp, ld, 0, N, h, w, Cc, out.data_ptr(), stream()), 'gcc_global_avgpool')
+    return out
+
+
+def conv_eval_rect(x, w, Co, kernel, stride, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slot='eval', route_only=False):
+    """inference conv with a (kh, kw) kernel and NO padding (gcc_conv_eval_ex with KH != KW allowed): out = act(scale[c] conv(x, w)
+    + shift[c]).  gcc_conv_t has one `pad` for both directions, so a rectangular kernel's own padding (ph, pw) is border_copy's
+    work: conv_eval_rect(border_copy(x, xb, ph, pw), ...).  w: pack_weights of the [Co, Ci, kh, kw] master.
+    route_only: -1 when the library declines the geometry, else the launches the call would make (nothing is launched)."""
+    kh, kw = kernel
+    xp, N, Ci, H, W, ldx = geom(x)
+    yp, _, _, _, _, ldy = geom(out)
+    d = conv_desc(N, H, W, Ci, Co, kh, stride, 0, ldx, ldy)
+    d.KW = kw
+    if route_only:
+        if lib().gcc_conv_eval_ex_route(C.byref(d), 0, 0) < 0:
+            return -1
+    need = lib().gcc_conv_eval_ex_workspace(C.byref(d), 0)
+    ws = workspace(need, x.device, slot) if need else None
+    if route_only:
+        return 2 if lib().gcc_conv_eval_ex_route(C.byref(d), 0, ws.numel() if ws is not None else 0) == 5 else 1
+    ep = _lib.eval_ex_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, _lib.EVAL_ACT_NONE, 0.0, 0, None, 0)
+    if ws is not None:
+        ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib().gcc_conv_eval_ex(C.byref(d), 0, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_ex')
+    return out
+
+
 def seg_head(x, seg_w, seg_b, up_w, scores, logp=None):
     """gcc_seg_head: scores (NCHW fp32 [N, C, h, w]) = the 1 x 1 conv seg_w [C, Cin] (+ seg_b) of the NHWC bf16 feature map x
     (x None: scores are read as given); logp (NCHW fp32 [N, C, 8h, 8w], optional) = LogSoftmax of the depthwise 16 x 16,

@@ -857,6 +857,37 @@ int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w, int Cin, c
                  const float* up_w, float* scores, float* logp, gcc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The FID Inception-v3 network (metric/inception.py:166-315 fid_inception_v3 under InceptionV3([3])): its convolutions are
+ * gcc_conv_eval_ex calls; these are the streaming pieces around them (gcc_amd/csrc/inception.hip,
+ * gcc_amd/metric/inception_fid.py).  Added without a GCC_HIP_ABI bump (additions only).  One launch each, 16-byte accesses over
+ * 8-channel chunks, no atomics; every refusal happens before anything is launched: GCC_ERR_BAD_ARG for a null pointer, a
+ * non-positive size, an ld / offset that is no multiple of 8, a window that does not fit its ld, a pointer off its alignment;
+ * GCC_ERR_UNSUPPORTED for a channel count that is no multiple of 8.
+ * gcc_fid_resize: y[n][oy][ox][off + c] = bf16(2 v - 1), v = F.interpolate(x, (Ho, Wo), mode = 'bilinear', align_corners =
+ *   False) of the NCHW fp32 image x [N][3][H][W], in fp32 with torch's source index max(0, (o + 0.5) (in / out) - 0.5), the
+ *   upper neighbour clamped to in - 1 (it enlarges and shrinks; no antialiasing); channels off + 3 .. off + 7 are written as
+ *   zeros.  y: NHWC bf16 [N][Ho][Wo], ld elements per pixel.
+ * gcc_pool3x3: 3 x 3 pooling of channels [xoff, xoff + C) of the NHWC bf16 map x [N][H][W] into channels [yoff, yoff + C) of y;
+ *   every other channel of y is left alone.  GCC_POOL3_MAX_S2: max, stride 2, no padding, y [N][(H - 3) / 2 + 1][(W - 3) / 2 +
+ *   1] (H, W >= 3); GCC_POOL3_MAX_S1P1: max, stride 1, padding 1 of -inf, y [N][H][W]; GCC_POOL3_AVG_S1P1: mean over the taps
+ *   inside the map (count_include_pad = False), fp32 sum, one division, one rounding.  x and y must not overlap.
+ * gcc_border_copy: dst [N][H + 2 ph][W + 2 pw] = src [N][H][W] with a border of ph rows and pw columns of zeros around it, for
+ *   channels [soff, soff + C) -> [doff, doff + C); the border is written in the same launch whatever dst held.  A convolution with
+ *   a (KH, KW) kernel and padding (ph, pw) of src is the padding-0 convolution of dst.  Never in place (GCC_ERR_BAD_ARG).
+ * gcc_global_avgpool: out[n][c] = mean over the h w pixels of x[n][.][off + c], fp32 [N][C] (16-byte aligned), summed in fp32
+ *   in an order the shape alone fixes (eight interleaved partial sums, then a tree).
+ * --------------------------------------------------------------------------------------------- */
+#define GCC_POOL3_MAX_S2 0
+#define GCC_POOL3_MAX_S1P1 1
+#define GCC_POOL3_AVG_S1P1 2
+int gcc_fid_resize(const float* x, int N, int H, int W, void* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream);
+int gcc_pool3x3(int mode, const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int N, int H, int W, int C,
+                gcc_stream_t stream);
+int gcc_border_copy(const void* src, int lds, int soff, void* dst, int ldd, int doff, int N, int H, int W, int C, int ph, int pw,
+                    gcc_stream_t stream);
+int gcc_global_avgpool(const void* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FID around the Inception network (metric/test_metric.py:15-45, 129-204, metric/get_real_stat.py; the network itself is the
  * caller's).  Added without a GCC_HIP_ABI bump (additions only).
  * gcc_fid_input: the network's input, NCHW fp32 out[N][3][H][W] in [0, 1] = float(byte) / 255.f (equal to the reference's
