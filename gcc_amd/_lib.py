@@ -81,6 +81,12 @@ class eval_ex_epilogue_t(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
 
 
+class eval_f32_epilogue_t(C.Structure):
+    """include/gcc_hip.h gcc_eval_f32_epilogue_t: the epilogue of gcc_conv_eval_f32 (fp32 in, fp32 out; residual before the act)"""
+    _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('residual', C.c_void_p), ('ld_residual', C.c_int),
+                ('residual_off', C.c_int), ('act', C.c_int), ('dilation', C.c_int)]
+
+
 FID_IN_BF16, FID_IN_U8, FID_IN_F32 = 0, 1, 2               # include/gcc_hip.h GCC_FID_IN_*
 POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2     # include/gcc_hip.h GCC_POOL3_*
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
@@ -218,6 +224,10 @@ PROTOTYPES = {
     'gcc_conv_eval_ex': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(eval_ex_epilogue_t), _P]),
     'gcc_conv_eval_ex_workspace': (_Z, [C.POINTER(conv_t), _I]),
     'gcc_conv_eval_ex_route': (_I, [C.POINTER(conv_t), _I, _Z]),
+    'gcc_conv_eval_f32': (_I, [C.POINTER(conv_t), _P, _P, _P, C.POINTER(eval_f32_epilogue_t), _P]),
+    'gcc_conv_eval_f32_route': (_I, [C.POINTER(conv_t), _I]),
+    'gcc_conv_eval_f32_kp': (_I, [_I, _I, _I]),
+    'gcc_nchw_f32_to_nhwc_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_dw_inorm_fwd': (_I, [C.POINTER(dw_inorm_t), _P]),
     'gcc_dw_inorm_route': (_I, [C.POINTER(dw_inorm_t)]),
@@ -250,6 +260,7 @@ PROTOTYPES = {
     'gcc_phase_regroup': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_relu_bf16': (_I, [_P, _I, _I, _I, _Z, _P]),
     'gcc_seg_head': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    'gcc_seg_head_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     'gcc_fid_resize': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     'gcc_pool3x3': (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_border_copy': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

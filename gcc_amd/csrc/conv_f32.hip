@@ -1,0 +1,254 @@
+// Inference convolution in fp32 on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain,
+// at 1/16 of the bf16 MFMA rate): gcc_conv_eval_f32, the evaluator networks at the reference's own precision
+// (gcc_amd/metric/drn_seg.py, precision 'fp32').
+//
+// Implicit GEMM: M = N Ho Wo output pixels, N = Co, K = KH KW Cip (Cip = Ci, or 4 for the 3-channel stem).  A workgroup of four
+// waves owns one BM x BN output tile and walks ALL of K in steps of 16: no split-K, no atomics, no inter-workgroup state.
+//   A tile  gathered from NHWC fp32, 16 bytes (4 channels of one tap) per load; taps outside the image, rows beyond M and k
+//           beyond KH KW Cip are zeros; stride and dilation are index arithmetic
+//   B tile  rows of the packed weights [Co][Kp] (k contiguous, zero-filled to Kp = ceil16(K)); rows beyond Co are zeros
+//   LDS     As[row][16 + 4], Bs[col][16 + 4] floats, two stages (40 KB for the largest tile).  A lane reads its row's k-half
+//           (4 floats at 8 g + 4 (lane >> 5)) with one ds_read_b128; the row stride of 20 dwords puts the 16 lanes of every
+//           ds_read_b128 lane group on 16 distinct 4-bank spans of the 64 banks
+//   MFMA    32x32x2: lane l supplies A[row l & 31][k half l >> 5] and B[k half l >> 5][col l & 31], so instruction e of half-step
+//           g multiplies k = 8 g + e and 8 g + 4 + e.  The order of K is the same for every tile shape, every pixel, every batch.
+//   C       col = lane & 31 (a channel: 32 lanes store 128 contiguous bytes), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+// The next step's global loads are issued into registers before the current step's MFMAs and stored to the other LDS stage behind
+// them: one barrier per step.
+#include "common.hpp"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+constexpr int CF_BK = 16, CF_LDK = CF_BK + 4, CF_THREADS = 256;
+
+struct ConvF32Args {
+    const float* x; const float* w; float* y;
+    const float* scale; const float* shift; const float* res;
+    int M, H, W, Ho, Wo, Ci, Cip, Co, KW, stride, pad, dil;
+    int ldx, xoff, ldy, yoff, ldr, roff, Kreal, Kp, relu;
+    FastDiv dWo, dHo, dCip, dKW;
+};
+
+template <int MI, int NI, int WM, int WN>
+__global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
+    static_assert(WM * WN == 4, "four waves");
+    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
+    constexpr int A_PER = BM * 4 / CF_THREADS, B_PER = (BN * 4 + CF_THREADS - 1) / CF_THREADS;
+    __shared__ __attribute__((aligned(16))) float As[2][BM * CF_LDK];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BN * CF_LDK];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int chunk = t & 3;                        // the thread's 4 floats of a 16-float k step, for its A rows and its B rows
+
+    // the thread's A rows: output pixel -> (image base, first tap's input row / column); a row beyond M never passes the range test
+    int ih0[A_PER], iw0[A_PER], nb[A_PER];
+#pragma unroll
+    for (int i = 0; i < A_PER; i++) {
+        const int m = m0 + ((t + i * CF_THREADS) >> 2);
+        if (m < a.M) {
+            const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;
+            const int n = fdiv(q, a.dHo), oh = q - n * a.Ho;
+            ih0[i] = oh * a.stride - a.pad; iw0[i] = ow * a.stride - a.pad; nb[i] = n * a.H * a.W;
+        } else {
+            ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
+        }
+    }
+    const float* wrow[B_PER];
+#pragma unroll
+    for (int i = 0; i < B_PER; i++) {
+        const int idx = t + i * CF_THREADS, co = n0 + (idx >> 2);
+        wrow[i] = (idx < BN * 4 && co < a.Co) ? a.w + (size_t)co * a.Kp + chunk * 4 : nullptr;
+    }
+
+    f32x4 ra[A_PER], rb[B_PER];
+    auto load = [&](int kt) {
+        const int k4 = kt * CF_BK + chunk * 4;
+        const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;
+        const int kh = fdiv(tap, a.dKW), kw = tap - kh * a.KW;
+        const bool kok = k4 < a.Kreal;
+        const int dh = kh * a.dil, dw = kw * a.dil;
+#pragma unroll
+        for (int i = 0; i < A_PER; i++) {
+            const int ih = ih0[i] + dh, iw = iw0[i] + dw;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (kok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
+                v = *(const f32x4*)(a.x + (size_t)(nb[i] + ih * a.W + iw) * a.ldx + a.xoff + ci);
+                if (a.Ci == 3) v[3] = 0.f;           // the stem's pad channel: whatever it holds, it is not an input
+            }
+            ra[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < B_PER; i++) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (wrow[i]) v = *(const f32x4*)(wrow[i] + kt * CF_BK);
+            rb[i] = v;
+        }
+    };
+    auto stage = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < A_PER; i++) *(f32x4*)&As[s][((t + i * CF_THREADS) >> 2) * CF_LDK + chunk * 4] = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_PER; i++) {
+            const int idx = t + i * CF_THREADS;
+            if (idx < BN * 4) *(f32x4*)&Bs[s][(idx >> 2) * CF_LDK + chunk * 4] = rb[i];
+        }
+    };
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+        for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[mi][ni][r] = 0.f;
+
+    const int nk = a.Kp / CF_BK;
+    const int arow = (wm * MI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
+    const int brow = (wn * NI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
+    load(0);
+    stage(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; kt++) {
+        const int cur = kt & 1;
+        if (kt + 1 < nk) load(kt + 1);
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            f32x4 af[MI], bf[NI];
+#pragma unroll
+            for (int mi = 0; mi < MI; mi++) af[mi] = *(const f32x4*)&As[cur][arow + mi * 32 * CF_LDK + g * 8];
+#pragma unroll
+            for (int ni = 0; ni < NI; ni++) bf[ni] = *(const f32x4*)&Bs[cur][brow + ni * 32 * CF_LDK + g * 8];
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+                    for (int ni = 0; ni < NI; ni++)
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi][e], bf[ni][e], acc[mi][ni], 0, 0, 0);
+        }
+        if (kt + 1 < nk) stage(cur ^ 1);
+        __syncthreads();
+    }
+
+    // epilogue: act(scale acc + shift + residual); only pixels < M and channels < Co are touched
+#pragma unroll
+    for (int ni = 0; ni < NI; ni++) {
+        const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
+        if (co >= a.Co) continue;
+        const float sc = a.scale ? a.scale[co] : 1.f, sh = a.shift ? a.shift[co] : 0.f;
+#pragma unroll
+        for (int mi = 0; mi < MI; mi++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int m = m0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m >= a.M) continue;
+                float v = fmaf(acc[mi][ni][r], sc, sh);
+                if (a.res) v += a.res[(size_t)m * a.ldr + a.roff + co];
+                if (a.relu) v = v < 0.f ? 0.f : v;
+                a.y[(size_t)m * a.ldy + a.yoff + co] = v;
+            }
+        }
+    }
+}
+
+// one thread per pixel: C strided reads (consecutive threads read consecutive floats of a plane), cfill / 4 16-byte stores
+__global__ __launch_bounds__(CF_THREADS) void nchw_to_nhwc_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
+                                                                       size_t plane, size_t pixels, int ld, int off, int cfill) {
+    for (size_t p = (size_t)blockIdx.x * CF_THREADS + threadIdx.x; p < pixels; p += (size_t)gridDim.x * CF_THREADS) {
+        const size_t n = p / plane, q = p - n * plane;
+        const float* s = src + n * C * plane + q;
+        float* d = dst + p * ld + off;
+        for (int c4 = 0; c4 < cfill; c4 += 4) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = (c4 + j < C) ? s[(size_t)(c4 + j) * plane] : 0.f;
+            *(f32x4*)(d + c4) = v;
+        }
+    }
+}
+
+inline int cf_cip(int Ci) { return Ci == 3 ? 4 : Ci; }
+inline int cf_kp(int Ci, int KH, int KW) { return (KH * KW * cf_cip(Ci) + CF_BK - 1) / CF_BK * CF_BK; }
+
+// the tile of a geometry (0: 128 x 128, 1: 64 x 64, 2: 128 x 32), or the error the call returns for it
+int cf_route(const gcc_conv_t* c, int dilation) {
+    if (!c || c->N <= 0 || c->H <= 0 || c->W <= 0 || c->Ci <= 0 || c->Co <= 0 || c->KH <= 0 || c->KW <= 0 || c->stride <= 0 ||
+        c->pad < 0 || dilation < 1)
+        return GCC_ERR_BAD_ARG;
+    if (c->ldx <= 0 || c->ldy <= 0 || c->xoff < 0 || c->yoff < 0 || (c->ldx & 3) || (c->xoff & 3) || (c->ldy & 3) || (c->yoff & 3))
+        return GCC_ERR_BAD_ARG;
+    if (c->KH != c->KW || (c->KH != 1 && c->KH != 3 && c->KH != 7) || (c->stride != 1 && c->stride != 2)) return GCC_ERR_UNSUPPORTED;
+    if ((dilation != 1 && dilation != 2 && dilation != 4) || c->pad != dilation * (c->KH / 2)) return GCC_ERR_UNSUPPORTED;
+    if ((c->Ci != 3 && (c->Ci & 7)) || (c->Co & 7)) return GCC_ERR_UNSUPPORTED;
+    if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
+    const int span = dilation * (c->KH - 1) + 1;
+    if (c->H + 2 * c->pad < span || c->W + 2 * c->pad < span) return GCC_ERR_BAD_ARG;
+    const long long Ho = (c->H + 2 * c->pad - span) / c->stride + 1, Wo = (c->W + 2 * c->pad - span) / c->stride + 1;
+    const long long M = (long long)c->N * Ho * Wo, Min = (long long)c->N * c->H * c->W;
+    if (M >= (1ll << 31) - 256 || Min >= (1ll << 31) || (long long)c->KH * c->KW * cf_cip(c->Ci) >= (1ll << 30))
+        return GCC_ERR_UNSUPPORTED;
+    if (c->Co <= 32) return 2;
+    const long long big = ((M + 127) / 128) * ((c->Co + 127) / 128);
+    return (c->Co >= 128 && big >= 256) ? 0 : 1;           // 128 x 128 tiles once they fill the chip, else 64 x 64
+}
+
+}  // namespace
+
+extern "C" int gcc_conv_eval_f32_kp(int Ci, int KH, int KW) {
+    if (Ci <= 0 || KH <= 0 || KW <= 0 || (long long)KH * KW * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
+    return cf_kp(Ci, KH, KW);
+}
+
+extern "C" int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation) { return cf_route(c, dilation); }
+
+extern "C" int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const float* w, float* y, const gcc_eval_f32_epilogue_t* ep,
+                                 gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
+    const int route = cf_route(c, ep->dilation);
+    if (route < 0) return route;
+    if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)ep->residual)) & 15) return GCC_ERR_BAD_ARG;
+    if (ep->residual && (ep->ld_residual <= 0 || ep->residual_off < 0 || (ep->ld_residual & 3) || (ep->residual_off & 3) ||
+                         ep->ld_residual < ep->residual_off + c->Co))
+        return GCC_ERR_BAD_ARG;
+    ConvF32Args a;
+    const int span = ep->dilation * (c->KH - 1) + 1;
+    a.x = x; a.w = w; a.y = y; a.scale = ep->scale; a.shift = ep->shift; a.res = ep->residual;
+    a.H = c->H; a.W = c->W;
+    a.Ho = (c->H + 2 * c->pad - span) / c->stride + 1;
+    a.Wo = (c->W + 2 * c->pad - span) / c->stride + 1;
+    a.M = c->N * a.Ho * a.Wo;
+    a.Ci = c->Ci; a.Cip = cf_cip(c->Ci); a.Co = c->Co; a.KW = c->KW; a.stride = c->stride; a.pad = c->pad; a.dil = ep->dilation;
+    a.ldx = c->ldx; a.xoff = c->xoff; a.ldy = c->ldy; a.yoff = c->yoff;
+    a.ldr = ep->residual ? ep->ld_residual : 0; a.roff = ep->residual ? ep->residual_off : 0;
+    a.Kreal = c->KH * c->KW * a.Cip; a.Kp = cf_kp(c->Ci, c->KH, c->KW);
+    a.relu = ep->act == GCC_EVAL_ACT_RELU;
+    a.dWo = make_fastdiv(a.Wo); a.dHo = make_fastdiv(a.Ho); a.dCip = make_fastdiv(a.Cip); a.dKW = make_fastdiv(a.KW);
+    const hipStream_t st = (hipStream_t)stream;
+    if (route == 0)
+        hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128)), dim3(CF_THREADS), 0, st, a);
+    else if (route == 1)
+        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 2, 2>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64)), dim3(CF_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 4, 1>), dim3(cdiv(a.M, 128), 1), dim3(CF_THREADS), 0, st, a);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,
+                                        gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!src || !dst || N <= 0 || C <= 0 || H <= 0 || W <= 0) return GCC_ERR_BAD_ARG;
+    if (ld <= 0 || off < 0 || cfill < C || (ld & 3) || (off & 3) || (cfill & 3) || ld < off + cfill || (((uintptr_t)dst) & 15))
+        return GCC_ERR_BAD_ARG;
+    const size_t plane = (size_t)H * W, pixels = plane * N;
+    size_t blocks = (pixels + CF_THREADS - 1) / CF_THREADS;
+    if (blocks > (1u << 20)) blocks = 1u << 20;
+    hipLaunchKernelGGL(nchw_to_nhwc_f32_kernel, dim3((unsigned)blocks), dim3(CF_THREADS), 0, (hipStream_t)stream, src, dst, C, plane,
+                       pixels, ld, off, cfill);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}

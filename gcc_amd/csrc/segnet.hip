@@ -4,7 +4,7 @@
 //                       n d^2 + (h mod d) d + (w mod d), row h div d, column w div d of an [N d^2, H / d, W / d] image, so that a
 //                       3 x 3 convolution of dilation d and padding d is an ordinary 3 x 3, padding-1 convolution of that image
 //   gcc_relu_bf16       in-place ReLU of a channel window: relu(bn(conv) + residual) behind gcc_conv_fprop_eval
-//   gcc_seg_head        the fp32 output end: the 1 x 1 `seg` conv with bias (NCHW fp32 scores), then the depthwise 16 x 16,
+//   gcc_seg_head        (and gcc_seg_head_f32: fp32 features) the fp32 output end: the 1 x 1 `seg` conv with bias (NCHW fp32 scores), then the depthwise 16 x 16,
 //                       stride-8, padding-4 ConvTranspose2d `up` and LogSoftmax over the classes, per output pixel in registers
 // Every thread owns its outputs: no atomics, no inter-workgroup communication, no grid-wide state.
 #include "common.hpp"
@@ -70,8 +70,16 @@ __global__ __launch_bounds__(SG_THREADS) void relu_bf16_kernel(bf16_t* __restric
 
 // seg: scores[n][c][p] = bias[c] + sum_k w[c][k] x[n][p][k] in fp32, k ascending.  A workgroup is 64 pixels x 4 waves; wave v
 // owns classes v, v + 4, ... (so the weights of a wave's FMAs are wave-uniform) and reads each 16-byte chunk of its pixel once.
+// The feature map is bf16 (gcc_seg_head) or fp32 (gcc_seg_head_f32: two 16-byte loads per 8 channels); the sums are the same.
 constexpr int SEG_WAVES = 4, SEG_PER_WAVE = SG_MAX_CLASSES / SEG_WAVES;
-__global__ __launch_bounds__(SG_THREADS) void seg_scores_kernel(const bf16_t* __restrict__ x, int ld, int off, int Cin,
+__device__ __forceinline__ void seg_load8(const bf16_t* p, float* f) { unpack8(*(const i32x4*)p, f); }
+__device__ __forceinline__ void seg_load8(const float* p, float* f) {
+    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+#pragma unroll
+    for (int j = 0; j < 4; j++) { f[j] = a[j]; f[4 + j] = b[j]; }
+}
+template <typename T>
+__global__ __launch_bounds__(SG_THREADS) void seg_scores_kernel(const T* __restrict__ x, int ld, int off, int Cin,
                                                                  const float* __restrict__ w, const float* __restrict__ bias, int C,
                                                                  size_t plane, size_t pixels, float* __restrict__ scores) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -83,10 +91,10 @@ __global__ __launch_bounds__(SG_THREADS) void seg_scores_kernel(const bf16_t* __
         const int c = wave + SEG_WAVES * j;
         acc[j] = (c < C && bias) ? bias[c] : 0.f;
     }
-    const bf16_t* xp = x + p * ld + off;
+    const T* xp = x + p * ld + off;
     for (int k = 0; k < Cin; k += 8) {           // Cin is a multiple of 8 (checked on the host)
         float f[8];
-        unpack8(*(const i32x4*)(xp + k), f);
+        seg_load8(xp + k, f);
 #pragma unroll
         for (int j = 0; j < SEG_PER_WAVE; j++) {
             const int c = wave + SEG_WAVES * j;
@@ -189,11 +197,14 @@ extern "C" int gcc_relu_bf16(void* x, int ld, int off, int C, size_t pixels, gcc
     return GCC_OK;
 }
 
-extern "C" int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b,
-                            int C, const float* up_w, float* scores, float* logp, gcc_stream_t stream) {
+// T: the feature map's element type; ALIGN: what its ld / offset must be multiples of (16 bytes)
+template <typename T, int ALIGN>
+static int seg_head_impl(const T* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b, int C,
+                         const float* up_w, float* scores, float* logp, gcc_stream_t stream) {
     GCC_ENTER();
     if (!scores || N <= 0 || h <= 0 || w <= 0 || C <= 0 || (!x && !logp)) return GCC_ERR_BAD_ARG;
-    if (x && (!seg_w || Cin <= 0 || ld <= 0 || off < 0 || (ld & 7) || (off & 7) || ld < off + ceil8(Cin) || (((uintptr_t)x) & 15)))
+    if (x && (!seg_w || Cin <= 0 || ld <= 0 || off < 0 || (ld & (ALIGN - 1)) || (off & (ALIGN - 1)) || ld < off + ceil8(Cin) ||
+              (((uintptr_t)x) & 15)))
         return GCC_ERR_BAD_ARG;
     if (logp && !up_w) return GCC_ERR_BAD_ARG;
     if (C > SG_MAX_CLASSES || (x && (Cin & 7))) return GCC_ERR_UNSUPPORTED;
@@ -201,8 +212,8 @@ extern "C" int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w,
     if (pixels * 64 >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
     const hipStream_t st = (hipStream_t)stream;
     if (x) {
-        hipLaunchKernelGGL(seg_scores_kernel, dim3((unsigned)((pixels + 63) / 64)), dim3(SG_THREADS), 0, st, (const bf16_t*)x, ld, off,
-                           Cin, seg_w, seg_b, C, plane, pixels, scores);
+        hipLaunchKernelGGL(seg_scores_kernel<T>, dim3((unsigned)((pixels + 63) / 64)), dim3(SG_THREADS), 0, st, x, ld, off, Cin, seg_w,
+                           seg_b, C, plane, pixels, scores);
         GCC_CHECK_LAUNCH();
     }
     if (logp) {
@@ -216,4 +227,14 @@ extern "C" int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w,
         GCC_CHECK_LAUNCH();
     }
     return GCC_OK;
+}
+
+extern "C" int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b,
+                            int C, const float* up_w, float* scores, float* logp, gcc_stream_t stream) {
+    return seg_head_impl<bf16_t, 8>((const bf16_t*)x, ld, off, N, h, w, Cin, seg_w, seg_b, C, up_w, scores, logp, stream);
+}
+
+extern "C" int gcc_seg_head_f32(const float* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w,
+                                const float* seg_b, int C, const float* up_w, float* scores, float* logp, gcc_stream_t stream) {
+    return seg_head_impl<float, 4>(x, ld, off, N, h, w, Cin, seg_w, seg_b, C, up_w, scores, logp, stream);
 }

@@ -310,11 +310,17 @@ def cityscapes_evaluator(segmenter, logger=None, batch_size=1):
     return evaluate
 
 
+PRECISION_ENV = 'GCC_DRN_PRECISION'
+
+
 def builtin_segmenter(opt):
     """for a Pix2Pix run on a Cityscapes root (the callers' test, the reference's own: 'cityscapes' in --dataroot): (segmenter,
     None) when <dataroot>/table.txt exists and --drn_path is a TorchScript archive (the reference's DRNSeg exported with
     torch.jit) or the reference's own file, the plain state_dict of a DRNSeg over an arch-D DRN (drn_seg.DrnSegEngine, still on the
-    host: the scorer moves it to the device); else (None, the condition that failed)"""
+    host: the scorer moves it to the device); else (None, the condition that failed).  The environment variable
+    GCC_DRN_PRECISION ('bf16', the default, or 'fp32': the reference's own arithmetic on the f32-input matrix instructions) chooses
+    the precision of the engine built from a plain state_dict; any other value raises GccError.  A TorchScript archive runs as it
+    was exported and ignores the variable."""
     root = str(opt.dataroot)
     if not os.path.isfile(os.path.join(root, 'table.txt')):
         return None, '%s holds no table.txt' % root
@@ -327,14 +333,17 @@ def builtin_segmenter(opt):
         first = (str(e).strip().splitlines() or [type(e).__name__])[0]
         reason = 'torch.jit.load could not read --drn_path %s as a TorchScript archive (%s: %s); a plain state_dict needs ' \
                  'the network\'s code: export DRNSeg with torch.jit once' % (path, type(e).__name__, first)
-    from .drn_seg import DrnSegEngine, is_drn_seg_state_dict
+    from .drn_seg import PRECISIONS, DrnSegEngine, is_drn_seg_state_dict
     try:
         sd = torch.load(path, map_location='cpu', weights_only=True)
     except Exception:
         return None, reason
     if not is_drn_seg_state_dict(sd):
         return None, reason
+    precision = os.environ.get(PRECISION_ENV) or 'bf16'
+    if precision not in PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (PRECISION_ENV, precision, ', '.join(PRECISIONS)))
     try:
-        return DrnSegEngine(sd), None
+        return DrnSegEngine(sd, precision=precision), None
     except GccError as e:
         return None, '--drn_path %s holds a DRNSeg state_dict this package does not run: %s' % (path, e)

@@ -12,6 +12,12 @@ the ordinary one with batch N d^2.  1 x 1 convs, BatchNorm, ReLU and residual su
 arch D every 3 x 3 conv of a level has the level's dilation (level 5: 2, 6: 4, 7: 2, 8: 1), so the whole network needs four
 gcc_phase_regroup launches: 1 -> 2, 2 -> 4, 4 -> 2, 2 -> 1.
 
+precision='fp32' is the same network at the reference's own precision: NHWC fp32 activations and fp32 weights through
+gcc_conv_eval_f32 (f32-input MFMA), where dilation is index arithmetic and the residual sum and the ReLU behind it are part of
+the conv's epilogue -- no regroup and no separate ReLU launches:
+
+    x NCHW fp32 -> gcc_nchw_f32_to_nhwc_f32 -> one gcc_conv_eval_f32 per convolution -> gcc_seg_head_f32
+
 Construction parses the state_dict on the host (no device, no library); .to(device) packs the weights and folds the BatchNorms
 once -- the weights of an evaluator never change."""
 import ctypes as C
@@ -27,6 +33,7 @@ LEVEL_DILATION = (1, 1, 1, 1, 1, 2, 4, 2, 1)
 CONV_LEVELS = (1, 2, 7, 8)                           # Sequential(conv, BatchNorm, ReLU, ...); 3 .. 6 are residual blocks
 HEAD_KEYS = ('base.0.0.weight', 'seg.weight', 'seg.bias', 'up.weight')
 BN_FIELDS = ('weight', 'bias', 'running_mean', 'running_var')
+PRECISIONS = ('bf16', 'fp32')
 BN_EPS = 1e-5                                        # nn.BatchNorm2d's default: a state_dict does not carry it
 MAX_CLASSES = 64
 SIZE_MULTIPLE = 32                                   # 8x downsampling, then sub-grids of dilation 4
@@ -204,9 +211,13 @@ def _all_convs(arch):
 class DrnSegEngine:
     """segmenter(x) for cityscapes._Batcher / mIoU_score.test: x NCHW fp32 [N, 3, H, W] (H, W multiples of 32) ->
     (log-softmax [N, C, H, W] fp32, scores [N, C, H / 8, W / 8] fp32), DRNSeg.forward's tuple.  Activations are bf16 with one
-    rounding per conv + BatchNorm (+ ReLU) and per residual sum; the head is fp32."""
+    rounding per conv + BatchNorm (+ ReLU) and per residual sum; the head is fp32.  precision='fp32': activations, weights and
+    every sum are fp32 (the reference's own arithmetic), one launch per convolution."""
 
-    def __init__(self, state_dict):
+    def __init__(self, state_dict, precision='bf16'):
+        if precision not in PRECISIONS:
+            raise GccError('DrnSegEngine: precision %r; expected one of %s' % (precision, ', '.join(PRECISIONS)))
+        self.precision = precision
         self.arch = parse_drn_seg(state_dict)
         self.convs = _all_convs(self.arch)
         keys = set(c.key for c in self.convs) | set('%s.%s' % (c.bn, f) for c in self.convs for f in BN_FIELDS) | set(HEAD_KEYS)
@@ -241,6 +252,9 @@ class DrnSegEngine:
                 g, b, rm, rv = (self._bn[i, off:off + c.co] for i in range(4))
                 entries.append((SimpleNamespace(weight=g, bias=b, running_mean=rm, running_var=rv, eps=BN_EPS), None, c.co))
                 off += c.co
+                if self.precision == 'fp32':
+                    c.w = ops.pack_weights_f32(self.host[c.key].to(device))
+                    continue
                 master = self.host[c.key].to(device).contiguous(memory_format=torch.channels_last)
                 c.w, _ = ops.pack_weights(master, want_w=True, want_wt=False)
             self._table = ops.BNEvalTable(entries, device)
@@ -262,6 +276,9 @@ class DrnSegEngine:
         key = (N, H, W)
         prog = self._programs.get(key)
         if prog is not None:
+            return prog
+        if self.precision == 'fp32':
+            prog = self._programs[key] = self._program_f32(N, H, W)
             return prog
         # sizes first: the largest activation decides the region
         steps, shapes = [], []
@@ -323,13 +340,58 @@ class DrnSegEngine:
         self._programs[key] = prog
         return prog
 
+    def _program_f32(self, N, H, W):
+        """the fp32 route's launches: ('conv', conv, source, destination, residual, dilation, relu) over views of an fp32 slab
+        (the same four regions, behind the input's 3 channels in an ld of 4).  Every activation is in the logical layout; a
+        block's last conv adds the residual and applies the ReLU in its own epilogue."""
+        steps, shapes = [], []
+        R = 4
+        live = SimpleNamespace(h=H, w=W)
+
+        def act(Cc, region):
+            shapes.append(N * live.h * live.w * Cc)
+            return SimpleNamespace(C=Cc, region=region, h=live.h, w=live.w, d=1, view=None)
+
+        def pick(*avoid):
+            used = set(a.region for a in avoid if a is not None)
+            return next(r for r in range(R) if r not in used)
+
+        x = SimpleNamespace(C=3, region=-1, h=H, w=W, d=1, view=None)
+        for L in range(9):
+            d = LEVEL_DILATION[L]
+            for it in self.arch.levels[L]:
+                if isinstance(it, _Conv):
+                    live.h, live.w = live.h // it.stride, live.w // it.stride
+                    y = act(it.co, pick(x))
+                    steps.append(('conv', it, x, y, None, d if it.k > 1 else 1, it.relu))
+                    x = y
+                    continue
+                cur = x
+                for c in it.convs[:-1]:
+                    live.h, live.w = live.h // c.stride, live.w // c.stride
+                    y = act(c.co, pick(x, cur))
+                    steps.append(('conv', c, cur, y, None, d if c.k > 1 else 1, c.relu))
+                    cur = y
+                res = x
+                if it.downsample is not None:
+                    res = act(it.downsample.co, pick(x, cur))
+                    steps.append(('conv', it.downsample, x, res, None, 1, False))
+                last = it.convs[-1]
+                y = act(last.co, pick(x, cur, res))
+                steps.append(('conv', last, cur, y, res, d if last.k > 1 else 1, True))
+                x = y
+        size_in = N * H * W * 4
+        return SimpleNamespace(steps=steps, size_in=size_in, size_r=max(shapes), total=size_in + R * max(shapes), last=x, slab=None,
+                               h=live.h, w=live.w)
+
     def _bind(self, N, H, W):
         """the program of an input size with its views of the slab.  The slab only grows; when it is replaced, the programs
         bound to the old one are dropped with it (their views would keep it alive) and made again on their next use."""
         prog = self._program(N, H, W)
         if self._slab is None or self._slab.numel() < prog.total:
             self._slab, self._programs = None, {}
-            self._slab = torch.zeros(prog.total, dtype=torch.bfloat16, device=self.device)
+            self._slab = torch.zeros(prog.total, dtype=torch.float32 if self.precision == 'fp32' else torch.bfloat16,
+                                     device=self.device)
             prog = self._program(N, H, W)
         if prog.slab is self._slab:
             return prog
@@ -338,7 +400,7 @@ class DrnSegEngine:
         def view(a):
             if a.view is None:
                 off = 0 if a.region < 0 else prog.size_in + a.region * prog.size_r
-                ld = 8 if a.region < 0 else a.C
+                ld = (4 if self.precision == 'fp32' else 8) if a.region < 0 else a.C
                 nb, h, w = N * a.d * a.d, a.h // a.d, a.w // a.d
                 a.view = slab[off:off + nb * h * w * ld].view(nb, h, w, ld).permute(0, 3, 1, 2)[:, :a.C]
             return a.view
@@ -367,6 +429,13 @@ class DrnSegEngine:
         for st in prog.steps:
             if st[0] != 'conv':
                 continue
+            if self.precision == 'fp32':
+                _, c, src, dst, _, dil, _ = st
+                if ops.conv_eval_f32(src.view, c.w, c.co, c.k, c.stride, dil * (c.k // 2), dst.view, dilation=dil, route_only=True) < 0:
+                    raise GccError('DrnSegEngine: the library declines the fp32 geometry of %s (%d -> %d channels, %d x %d, stride '
+                                   '%d, dilation %d, on %d x %d x %d): there is no other route'
+                                   % ((c.key, c.ci, c.co, c.k, c.k, c.stride, dil) + tuple(src.view.shape[i] for i in (0, 2, 3))))
+                continue
             _, c, src, dst, _ = st
             _, Nb, Ci, h, w, ldx = ops.geom(src.view)
             d = ops.conv_desc(Nb, h, w, Ci, c.co, c.k, c.stride, c.pad, ldx, ops.geom(dst.view)[5])
@@ -387,6 +456,8 @@ class DrnSegEngine:
         if self.device is None:
             raise GccError('DrnSegEngine: .to(device) first')
         prog = self._bind(N, H, W)
+        if self.precision == 'fp32':
+            return self._run_f32(prog, x, N, H, W, count_only)
         if count_only:
             n = 1 + 2
             for st in prog.steps:
@@ -416,6 +487,23 @@ class DrnSegEngine:
         scores = torch.empty((N, self.classes, h, w), dtype=torch.float32, device=self.device)
         logp = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=self.device)
         ops.seg_head(prog.last.view, self.seg_w, self.seg_b, self.up_w, scores, logp)
+        return logp, scores
+
+    def _run_f32(self, prog, x, N, H, W, count_only):
+        from .. import _lib, ops
+        if count_only:
+            return 1 + len(prog.steps) + 2           # the input, one launch per convolution, the head's two
+        ops.nchw_to_nhwc_f32(x, prog.x_in, 4)
+        RELU, NONE = _lib.EVAL_ACT_RELU, _lib.EVAL_ACT_NONE
+        for _, c, src, dst, res, dil, relu in prog.steps:
+            try:
+                ops.conv_eval_f32(src.view, c.w, c.co, c.k, c.stride, dil * (c.k // 2), dst.view, dilation=dil, scale=c.scale,
+                                  shift=c.shift, act=RELU if relu else NONE, residual=res.view if res is not None else None)
+            except GccError as e:
+                raise GccError('DrnSegEngine: %s: %s' % (c.key, e))
+        scores = torch.empty((N, self.classes, prog.h, prog.w), dtype=torch.float32, device=self.device)
+        logp = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=self.device)
+        ops.seg_head_f32(prog.last.view, self.seg_w, self.seg_b, self.up_w, scores, logp)
         return logp, scores
 
     def __call__(self, x):

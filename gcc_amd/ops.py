@@ -672,6 +672,67 @@ def conv_eval_ex(x, w, Co, k, stride, pad, out, transposed=False, scale=None, sh
     return out
 
 
+# ---- the fp32 inference route (gcc_conv_eval_f32: f32-input MFMA; metric/drn_seg.py precision 'fp32') ----------------------
+def new_act_f32(N, Cc, H, W, device, ld=None):
+    """Zero-initialised NHWC fp32 activation [N, Cc, H, W] with pixel stride ld >= Cc (a multiple of 4 floats)."""
+    ld = ld or (Cc + 3) // 4 * 4
+    return torch.zeros((N, H, W, ld), dtype=torch.float32, device=device).permute(0, 3, 1, 2)[:, :Cc]
+
+
+def geom_f32(t):
+    """(ptr, N, C, H, W, ld) of an NHWC fp32 activation view (ld in floats, a multiple of 4; 16-byte aligned)"""
+    N, Cc, H, W = t.shape
+    s0, s1, s2, ld = t.stride()
+    p = t.data_ptr()
+    if (t.dtype is not torch.float32 or (s1 != 1 and Cc != 1) or (H > 1 and s2 != W * ld) or (N > 1 and s0 != H * W * ld)
+            or (ld & 3) or (p & 15)):
+        raise _lib.GccError('not an NHWC fp32 activation view: %s %s %s' % (t.dtype, tuple(t.shape), t.stride()))
+    return p, N, Cc, H, W, ld
+
+
+def pack_weights_f32(master):
+    """the packing gcc_conv_eval_f32 reads (include/gcc_hip.h): fp32 [Co][Kp], k = (kh KW + kw) Cip + ci with Cip = 4 for a
+    3-channel input and Ci otherwise, zeros at ci >= Ci and from KH KW Cip to Kp.  master: [Co, Ci, KH, KW] on its device."""
+    Co, Ci, KH, KW = master.shape
+    kp = lib().gcc_conv_eval_f32_kp(Ci, KH, KW)
+    check(min(kp, 0), 'gcc_conv_eval_f32_kp')
+    cip = 4 if Ci == 3 else Ci
+    w = torch.zeros((Co, kp), dtype=torch.float32, device=master.device)
+    w[:, :KH * KW * cip].view(Co, KH * KW, cip)[:, :, :Ci] = master.detach().float().permute(0, 2, 3, 1).reshape(Co, KH * KW, Ci)
+    return w
+
+
+def conv_eval_f32(x, w, Co, k, stride, pad, out, dilation=1, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, residual=None,
+                  route_only=False):
+    """fp32 inference conv (gcc_conv_eval_f32): out = act(scale[c] conv(x, w) + shift[c] + residual), NHWC fp32 views, w from
+    pack_weights_f32; the residual is added BEFORE the activation.  One launch, no workspace.
+    route_only: the library's answer for the geometry (>= 0: the tile it takes; < 0: declined), nothing launched."""
+    xp, N, Ci, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    d = conv_desc(N, H, W, Ci, Co, k, stride, pad, ldx, ldy)
+    if route_only:
+        return lib().gcc_conv_eval_f32_route(C.byref(d), dilation)
+    ep = _lib.eval_f32_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, dilation)
+    if residual is not None:
+        rp, _, _, _, _, ldr = geom_f32(residual)
+        ep.residual, ep.ld_residual = rp, ldr
+    check(lib().gcc_conv_eval_f32(C.byref(d), xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_f32')
+    return out
+
+
+def nchw_to_nhwc_f32(src, dst, cfill=None):
+    """src fp32 [N, C, H, W] contiguous -> the channels of the NHWC fp32 view dst (+ zero fill to cfill, a multiple of 4)"""
+    N, Cc, H, W = src.shape
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise _lib.GccError('nchw_to_nhwc_f32: expected a contiguous fp32 tensor, got %s' % src.dtype)
+    dp, Nd, _, Hd, Wd, ld = geom_f32(dst)
+    if (Nd, Hd, Wd) != (N, H, W):
+        raise _lib.GccError('nchw_to_nhwc_f32: %s into %s' % (tuple(src.shape), tuple(dst.shape)))
+    check(lib().gcc_nchw_f32_to_nhwc_f32(src.data_ptr(), dp, N, Cc, H, W, ld, 0, cfill if cfill else (Cc + 3) // 4 * 4, stream()),
+          'gcc_nchw_f32_to_nhwc_f32')
+    return dst
+
+
 def image_to_u8(x, out=None):
     """uint8 [N, H, W, 3] of an NHWC bf16 image (gcc_image_to_u8): the bytes of the reference's util.tensor2im"""
     xp, N, Cx, H, W, ld = geom(x)
@@ -986,6 +1047,22 @@ def seg_head(x, seg_w, seg_b, up_w, scores, logp=None):
         raise _lib.GccError('seg_head: log-probabilities %s / up weights against scores %s' % (tuple(logp.shape), tuple(scores.shape)))
     check(lib().gcc_seg_head(xp, ld, 0, N, h, w, Cin, _p(seg_w), _p(seg_b), Cc, _p(up_w), scores.data_ptr(), _p(logp), stream()),
           'gcc_seg_head')
+    return scores, logp
+
+
+def seg_head_f32(x, seg_w, seg_b, up_w, scores, logp=None):
+    """gcc_seg_head_f32: seg_head with x an NHWC fp32 feature map (the fp32 route's output end)"""
+    N, Cc, h, w = scores.shape
+    xp, Nx, Cin, hx, wx, ld = geom_f32(x)
+    if (Nx, hx, wx) != (N, h, w) or tuple(seg_w.shape) != (Cc, Cin):
+        raise _lib.GccError('seg_head_f32: features %s, weights %s, scores %s' % (tuple(x.shape), tuple(seg_w.shape), tuple(scores.shape)))
+    for t in (seg_w, seg_b, up_w, scores, logp):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != scores.device):
+            raise _lib.GccError('seg_head_f32: fp32 contiguous tensors on one device expected')
+    if logp is not None and (tuple(logp.shape) != (N, Cc, 8 * h, 8 * w) or up_w is None or up_w.numel() != Cc * 256):
+        raise _lib.GccError('seg_head_f32: log-probabilities %s / up weights against scores %s' % (tuple(logp.shape), tuple(scores.shape)))
+    check(lib().gcc_seg_head_f32(xp, ld, 0, N, h, w, Cin, _p(seg_w), _p(seg_b), Cc, _p(up_w), scores.data_ptr(), _p(logp), stream()),
+          'gcc_seg_head_f32')
     return scores, logp
 
 

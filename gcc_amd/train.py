@@ -124,7 +124,9 @@ def builtin_evaluator(opt, logger):
         if segmenter is None:
             logger.info('no Cityscapes mIoU evaluation: %s' % why)
             return None
-        logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s' % (opt.save_epoch_freq, opt.drn_path))
+        precision = getattr(segmenter, 'precision', None)          # the native engine's; a TorchScript archive has none
+        logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s%s'
+                    % (opt.save_epoch_freq, opt.drn_path, ' (native, %s)' % precision if precision else ''))
         return cityscapes_evaluator(segmenter, logger)
     if str(opt.dataroot).startswith('synthetic'):
         return None

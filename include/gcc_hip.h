@@ -486,6 +486,40 @@ size_t gcc_conv_eval_ex_workspace(const gcc_conv_t* c, int transposed);
  * with the whole epilogue), 0 igemm_kernel un-split (one launch); < 0 for an invalid geometry */
 int gcc_conv_eval_ex_route(const gcc_conv_t* c, int transposed, size_t workspace_bytes);
 
+/* Inference convolution in fp32 on the f32-input matrix instructions (v_mfma_f32_32x32x2_f32; gcc_amd/csrc/conv_f32.hip): the
+ * evaluator networks at the reference's own precision.  x, y and the residual are NHWC FP32, the weights fp32:
+ *     y[p][c] = act(scale[c] * acc[p][c] + shift[c] + residual[p][c])      -- the residual is added BEFORE the activation, as in
+ * a ResNet block (gcc_conv_fprop_eval adds it after).  acc is the sum over K = KH KW Ci products in ONE order, which depends on
+ * nothing but K: one workgroup per output tile walks K in steps of 16 (inside a step k, k + 4, k + 1, k + 5, ... of each half of
+ * 8), every product an fmaf onto the running sum; no split-K, no atomics, no workspace.  A pixel's result therefore does not
+ * depend on its batch or on the tile (or tile shape) it fell into.  One launch.  Added without a GCC_HIP_ABI bump (additions only).
+ * Geometry: KH == KW in {1, 3, 7}, stride 1 or 2, dilation 1, 2 or 4 (taps at ih = oh stride - pad + kh dilation),
+ *   pad == dilation (KH / 2), Ci == 3 or a multiple of 8, Co a multiple of 8, any pixel count; GCC_ERR_UNSUPPORTED otherwise.
+ *   The plan of gcc_conv_t is not read.
+ * Layout: ldx / xoff / ldy / yoff / ld_residual / residual_off in floats, multiples of 4; pointers 16-byte aligned; a window
+ *   must fit its ld (x: ceil4(Ci) channels -- with Ci == 3 the fourth channel is read and ignored); dilation < 1, an act other
+ *   than GCC_EVAL_ACT_NONE / _RELU, a null pointer: GCC_ERR_BAD_ARG.  Only channels [yoff, yoff + Co) of y are written.
+ * Weights: fp32 [Co][Kp], row co holding k = (kh KW + kw) Cip + ci with Cip = 4 for Ci == 3 and Ci otherwise, zero-filled at
+ *   ci >= Ci and from KH KW Cip up to Kp = the next multiple of 16 (gcc_conv_eval_f32_kp).
+ * gcc_conv_eval_f32_route: the tile the call would take (0: 128 pixels x 128 channels, 1: 64 x 64, 2: 128 x 32), or the error
+ *   the call would return for the geometry; launches nothing. */
+typedef struct {
+    const float* scale;     /* [Co] or NULL (1): folded BatchNorm */
+    const float* shift;     /* [Co] or NULL (0) */
+    const float* residual;  /* NULL, or NHWC fp32 with the output's geometry, added BEFORE the activation */
+    int ld_residual, residual_off;
+    int act;                /* GCC_EVAL_ACT_NONE | GCC_EVAL_ACT_RELU */
+    int dilation;           /* >= 1; taps at ih = oh*stride - pad + kh*dilation */
+} gcc_eval_f32_epilogue_t;
+int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const float* w, float* y, const gcc_eval_f32_epilogue_t* ep,
+                      gcc_stream_t stream);
+int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation);
+int gcc_conv_eval_f32_kp(int Ci, int KH, int KW);
+/* dst[p][off + c] = src[n][c][h][w] for c < C and 0 for C <= c < cfill: an NCHW fp32 image as the NHWC fp32 input of
+ * gcc_conv_eval_f32 (ld, off, cfill multiples of 4; off + cfill <= ld; dst 16-byte aligned).  One launch. */
+int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,
+                             gcc_stream_t stream);
+
 /* Image bytes of the reference's util.tensor2im: out[p][k] = (uint8)(((x + 1) * 0.5) * 255) of channel k < 3 of pixel p of an
  * NHWC bf16 tensor (ld, off: multiples of 8), evaluated in fp32 in that order with no contraction, then truncated (values
  * outside [-1, 1] are clamped to 0 / 255).  out: DEVICE uint8 [pixels][3]. */
@@ -849,12 +883,16 @@ int gcc_miou_score(const float* scores, int N, int C, int h, int w, const unsign
  *       weights up_w fp32 [C][1][16][16] (read, never assumed bilinear), NCHW fp32 [N][C][8h][8w]; at most 2 x 2 taps reach an
  *       output pixel, whose C values stay in one thread's registers.
  *   C <= 64, GCC_ERR_UNSUPPORTED beyond.
+ * gcc_seg_head_f32: the same two launches with x an NHWC FP32 feature map (ld, off in floats, multiples of 4): the output end of
+ *   the fp32 route (gcc_conv_eval_f32).  Same sums in the same order; x == NULL is gcc_seg_head's x == NULL.
  * --------------------------------------------------------------------------------------------- */
 int gcc_phase_regroup(const void* src, int lds, int soff, int d_src, void* dst, int ldd, int doff, int d_dst, int N, int H, int W,
                       int C, gcc_stream_t stream);
 int gcc_relu_bf16(void* x, int ld, int off, int C, size_t pixels, gcc_stream_t stream);
 int gcc_seg_head(const void* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b, int C,
                  const float* up_w, float* scores, float* logp, gcc_stream_t stream);
+int gcc_seg_head_f32(const float* x, int ld, int off, int N, int h, int w, int Cin, const float* seg_w, const float* seg_b, int C,
+                     const float* up_w, float* scores, float* logp, gcc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The FID Inception-v3 network (metric/inception.py:166-315 fid_inception_v3 under InceptionV3([3])): its convolutions are
