@@ -20,22 +20,23 @@ the conv's epilogue -- no regroup and no separate ReLU launches:
 
 Construction parses the state_dict on the host (no device, no library); .to(device) packs the weights and folds the BatchNorms
 once -- the weights of an evaluator never change."""
-import ctypes as C
 import re
 from types import SimpleNamespace
 
 import torch
 
-from .._lib import GccError
+from .. import ops
+from .._lib import EVAL_ACT_NONE as NONE, EVAL_ACT_RELU as RELU, GccError
+from ._native import Act, SlabProgramEngine, _shape, conv_shape
 
 LEVEL_STRIDE = (1, 1, 2, 2, 2, 1, 1, 1, 1)          # base.0 .. base.8 (metric/drn.py:127-158)
 LEVEL_DILATION = (1, 1, 1, 1, 1, 2, 4, 2, 1)
 CONV_LEVELS = (1, 2, 7, 8)                           # Sequential(conv, BatchNorm, ReLU, ...); 3 .. 6 are residual blocks
 HEAD_KEYS = ('base.0.0.weight', 'seg.weight', 'seg.bias', 'up.weight')
-BN_FIELDS = ('weight', 'bias', 'running_mean', 'running_var')
 PRECISIONS = ('bf16', 'fp32')
 BN_EPS = 1e-5                                        # nn.BatchNorm2d's default: a state_dict does not carry it
 MAX_CLASSES = 64
+WHAT = 'DRNSeg state_dict'
 SIZE_MULTIPLE = 32                                   # 8x downsampling, then sub-grids of dilation 4
 
 _BN = r'(?:weight|bias|running_mean|running_var|num_batches_tracked)'
@@ -47,10 +48,6 @@ _KEY_RES = [re.compile(p) for p in (
 
 
 _CONV_LEVEL_KEY = re.compile(r'base\.[1278]\.(\d+)\.(' + _BN[3:-1] + r')$')
-
-
-def _shape(v):
-    return tuple(v.shape) if hasattr(v, 'shape') else tuple(v)
 
 
 def is_drn_seg_state_dict(sd):
@@ -107,21 +104,8 @@ def parse_drn_seg(sd):
             raise GccError('DRNSeg state_dict: %s is missing' % key)
 
     def conv(key, bn, k, stride, relu=True):
-        if key not in sd:
-            raise GccError('DRNSeg state_dict: %s is missing' % key)
-        for f in BN_FIELDS:
-            if '%s.%s' % (bn, f) not in sd:
-                raise GccError('DRNSeg state_dict: %s.%s is missing (BatchNorm behind %s)' % (bn, f, key))
         c = _Conv(key, bn, k, stride, k // 2, relu)
-        s = _shape(sd[key])
-        if len(s) != 4 or s[2] != k or s[3] != k:
-            raise GccError('DRNSeg state_dict: %s has shape %s, expected a %d x %d convolution' % (key, s, k, k))
-        c.co, c.ci = s[0], s[1]
-        if c.co % 8:
-            raise GccError('DRNSeg state_dict: %s has %d output channels; widths must be multiples of 8' % (key, c.co))
-        for f in BN_FIELDS:
-            if _shape(sd['%s.%s' % (bn, f)]) != (c.co,):
-                raise GccError('DRNSeg state_dict: %s.%s has shape %s, expected (%d,)' % (bn, f, _shape(sd['%s.%s' % (bn, f)]), c.co))
+        c.co, c.ci = conv_shape(sd, WHAT, key, bn, (k, k))
         return c
 
     def indices(prefix):
@@ -208,241 +192,122 @@ def _all_convs(arch):
     return out
 
 
-class DrnSegEngine:
+class DrnSegEngine(SlabProgramEngine):
     """segmenter(x) for cityscapes._Batcher / mIoU_score.test: x NCHW fp32 [N, 3, H, W] (H, W multiples of 32) ->
     (log-softmax [N, C, H, W] fp32, scores [N, C, H / 8, W / 8] fp32), DRNSeg.forward's tuple.  Activations are bf16 with one
     rounding per conv + BatchNorm (+ ReLU) and per residual sum; the head is fp32.  precision='fp32': activations, weights and
-    every sum are fp32 (the reference's own arithmetic), one launch per convolution."""
+    every sum are fp32 (the reference's own arithmetic), one launch per convolution.  The engine's scaffold -- .to(), the slab
+    and its programs, the route check -- is metric/_native.py's."""
+    BN_EPS = BN_EPS
 
     def __init__(self, state_dict, precision='bf16'):
         if precision not in PRECISIONS:
             raise GccError('DrnSegEngine: precision %r; expected one of %s' % (precision, ', '.join(PRECISIONS)))
         self.precision = precision
+        if precision == 'fp32':
+            self._slab_dtype = torch.float32
         self.arch = parse_drn_seg(state_dict)
-        self.convs = _all_convs(self.arch)
-        keys = set(c.key for c in self.convs) | set('%s.%s' % (c.bn, f) for c in self.convs for f in BN_FIELDS) | set(HEAD_KEYS)
-        self.host = {k: state_dict[k].detach().to('cpu', torch.float32).contiguous() for k in keys}
+        super().__init__(state_dict, _all_convs(self.arch), HEAD_KEYS)
         self.classes = self.arch.classes
-        self.device = None
-        self._slab, self._programs = None, {}
 
     # ---- host -> device: once -------------------------------------------------------------------------------------------
-    def to(self, device):
-        from .. import ops
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise GccError('DrnSegEngine runs on the GPU only (asked for %s)' % device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if self.device == device:
-            return self
-        self.device = device
-        self._slab, self._programs = None, {}
-        with torch.cuda.device(device):
-            n = sum(c.co for c in self.convs)
-            self._bn = torch.empty((4, n), dtype=torch.float32)
-            off = 0
-            for c in self.convs:
-                for i, f in enumerate(BN_FIELDS):
-                    self._bn[i, off:off + c.co] = self.host['%s.%s' % (c.bn, f)]
-                off += c.co
-            self._bn = self._bn.to(device)
-            entries, off = [], 0
-            for c in self.convs:
-                g, b, rm, rv = (self._bn[i, off:off + c.co] for i in range(4))
-                entries.append((SimpleNamespace(weight=g, bias=b, running_mean=rm, running_var=rv, eps=BN_EPS), None, c.co))
-                off += c.co
-                if self.precision == 'fp32':
-                    c.w = ops.pack_weights_f32(self.host[c.key].to(device))
-                    continue
-                master = self.host[c.key].to(device).contiguous(memory_format=torch.channels_last)
-                c.w, _ = ops.pack_weights(master, want_w=True, want_wt=False)
-            self._table = ops.BNEvalTable(entries, device)
-            self._table.run()
-            for i, c in enumerate(self.convs):
-                c.scale, c.shift = self._table.scale[i], self._table.shift[i]
-            self.seg_w = self.host['seg.weight'].reshape(self.classes, -1).contiguous().to(device)
-            self.seg_b = self.host['seg.bias'].to(device)
-            self.up_w = self.host['up.weight'].reshape(self.classes, 256).contiguous().to(device)
-        return self
+    def _pack(self, c, master):
+        return ops.pack_weights_f32(master) if self.precision == 'fp32' else super()._pack(c, master)
 
-    def eval(self):
-        return self
+    def _to_extra(self, device):
+        self.seg_w = self.host['seg.weight'].reshape(self.classes, -1).contiguous().to(device)
+        self.seg_b = self.host['seg.bias'].to(device)
+        self.up_w = self.host['up.weight'].reshape(self.classes, 256).contiguous().to(device)
 
     # ---- the launch program of one input size ---------------------------------------------------------------------------
-    def _program(self, N, H, W):
-        """the launches of an [N, 3, H, W] input as a list of tuples over views of the activation slab (grow-only; four regions
-        the layers rotate through, behind the 8-channel input)"""
-        key = (N, H, W)
-        prog = self._programs.get(key)
-        if prog is not None:
-            return prog
-        if self.precision == 'fp32':
-            prog = self._programs[key] = self._program_f32(N, H, W)
-            return prog
-        # sizes first: the largest activation decides the region
-        steps, shapes = [], []
-        size_in = N * H * W * 8
+    def _plan(self, N, H, W):
+        """the launches of an [N, 3, H, W] input as a list of tuples over activations of the slab (four regions the layers rotate
+        through, behind the input's 3 channels in an ld of 8, or of 4 in fp32).  bf16: ('conv', conv, source, destination,
+        residual), ('relu', a) behind a block's last conv, ('regroup', a, b) where the level's dilation changes.  fp32: only
+        ('conv', conv, source, destination, residual, dilation, relu): every activation is in the logical layout, and a block's
+        last conv adds the residual and applies the ReLU in its own epilogue."""
+        f32 = self.precision == 'fp32'
+        steps, shapes = [], []                             # sizes first: the largest activation decides the region
         R = 4
         live = SimpleNamespace(h=H, w=W, d=1)
 
         def act(Cc, region):
             """symbolic activation: Cc channels of the current logical size in the current layout"""
             shapes.append(N * live.h * live.w * Cc)
-            return SimpleNamespace(C=Cc, region=region, h=live.h, w=live.w, d=live.d, view=None)
+            return Act(Cc, live.h, live.w, region, d=live.d)
 
         def pick(*avoid):
             used = set(a.region for a in avoid if a is not None)
             return next(r for r in range(R) if r not in used)
 
         def run_conv(c, src, dst, residual=None):
-            steps.append(('conv', c, src, dst, residual))
+            st = ('conv', c, src, dst, residual)
+            if f32:                                        # dilation rides on the step, and so does the ReLU behind the sum
+                st += (dil if c.k > 1 else 1, c.relu or residual is not None)
+            steps.append(st)
 
-        x = SimpleNamespace(C=3, region=-1, h=H, w=W, d=1, view=None)
+        ld_in = 4 if f32 else 8
+        x = Act(3, H, W, -1, ld=ld_in)
         for L in range(9):
-            d = LEVEL_DILATION[L]
-            if d != live.d:
-                y = SimpleNamespace(C=x.C, region=pick(x), h=live.h, w=live.w, d=d, view=None)
-                shapes.append(N * live.h * live.w * x.C)
+            dil = LEVEL_DILATION[L]
+            if dil != live.d and not f32:                  # bf16: dilation is a change of layout
+                live.d = dil
+                y = act(x.C, pick(x))
                 steps.append(('regroup', x, y))
-                live.d, x = d, y
+                x = y
             for it in self.arch.levels[L]:
                 blk = [it] if isinstance(it, _Conv) else it.convs
                 s = max(c.stride for c in blk)
                 if s != 1 and live.d != 1:
                     raise GccError('DrnSegEngine: %s has stride %d inside a dilated level' % (blk[0].key, s))
-                if isinstance(it, _Conv):
-                    live.h, live.w = live.h // s, live.w // s
-                    y = act(it.co, pick(x))
-                    run_conv(it, x, y)
-                    x = y
-                    continue
                 cur = x
                 for c in blk[:-1]:
                     live.h, live.w = live.h // c.stride, live.w // c.stride
                     y = act(c.co, pick(x, cur))
                     run_conv(c, cur, y)
                     cur = y
-                res = x
-                if it.downsample is not None:
-                    # the block's inner activations other than `cur` are dead once `cur` exists: their regions may be reused
-                    res = act(it.downsample.co, pick(x, cur))
-                    run_conv(it.downsample, x, res)
+                live.h, live.w = live.h // blk[-1].stride, live.w // blk[-1].stride
+                res = None
+                if not isinstance(it, _Conv):
+                    res = x
+                    if it.downsample is not None:
+                        # the block's inner activations other than `cur` are dead once `cur` exists: their regions may be reused
+                        res = act(it.downsample.co, pick(x, cur))
+                        run_conv(it.downsample, x, res)
                 y = act(blk[-1].co, pick(x, cur, res))
                 run_conv(blk[-1], cur, y, residual=res)
-                steps.append(('relu', y))
+                if res is not None and not f32:
+                    steps.append(('relu', y))
                 x = y
         if live.d != 1:
             raise GccError('DrnSegEngine: the last level leaves phase layout %d' % live.d)
-        size_r = max(shapes)
-        prog = SimpleNamespace(steps=steps, size_in=size_in, size_r=size_r, total=size_in + R * size_r, last=x, slab=None,
-                               h=live.h, w=live.w)
-        self._programs[key] = prog
-        return prog
+        size_in, size_r = N * H * W * ld_in, max(shapes)
+        return SimpleNamespace(steps=steps, size_in=size_in, size_r=size_r, total=size_in + R * size_r, last=x, slab=None,
+                               h=live.h, w=live.w, x_in=None)
 
-    def _program_f32(self, N, H, W):
-        """the fp32 route's launches: ('conv', conv, source, destination, residual, dilation, relu) over views of an fp32 slab
-        (the same four regions, behind the input's 3 channels in an ld of 4).  Every activation is in the logical layout; a
-        block's last conv adds the residual and applies the ReLU in its own epilogue."""
-        steps, shapes = [], []
-        R = 4
-        live = SimpleNamespace(h=H, w=W)
+    def _conv(self, st, route_only=False):
+        """launch the 'conv' step st, or with route_only the library's answer for it: its launches, -1 if it declines"""
+        c, src, dst, res = st[1:5]
+        if self.precision == 'fp32':
+            dil, relu = st[5:]
+            rc = ops.conv_eval_f32(src.view, c.w, c.co, c.k, c.stride, dil * (c.k // 2), dst.view, dilation=dil, scale=c.scale,
+                                   shift=c.shift, act=RELU if relu else NONE, residual=res.view if res is not None else None,
+                                   route_only=route_only)
+            return (1 if rc >= 0 else -1) if route_only else rc          # the route's answer is a tile: always one launch
+        if res is None:
+            return ops.conv_eval_ex(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, scale=c.scale, shift=c.shift,
+                                    act=RELU if c.relu else NONE, slot='drn_eval', route_only=route_only)
+        return ops.conv_fprop_eval(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, scale=c.scale, shift=c.shift, act=NONE,
+                                   residual=res.view, slot='drn_eval', route_only=route_only)
 
-        def act(Cc, region):
-            shapes.append(N * live.h * live.w * Cc)
-            return SimpleNamespace(C=Cc, region=region, h=live.h, w=live.w, d=1, view=None)
-
-        def pick(*avoid):
-            used = set(a.region for a in avoid if a is not None)
-            return next(r for r in range(R) if r not in used)
-
-        x = SimpleNamespace(C=3, region=-1, h=H, w=W, d=1, view=None)
-        for L in range(9):
-            d = LEVEL_DILATION[L]
-            for it in self.arch.levels[L]:
-                if isinstance(it, _Conv):
-                    live.h, live.w = live.h // it.stride, live.w // it.stride
-                    y = act(it.co, pick(x))
-                    steps.append(('conv', it, x, y, None, d if it.k > 1 else 1, it.relu))
-                    x = y
-                    continue
-                cur = x
-                for c in it.convs[:-1]:
-                    live.h, live.w = live.h // c.stride, live.w // c.stride
-                    y = act(c.co, pick(x, cur))
-                    steps.append(('conv', c, cur, y, None, d if c.k > 1 else 1, c.relu))
-                    cur = y
-                res = x
-                if it.downsample is not None:
-                    res = act(it.downsample.co, pick(x, cur))
-                    steps.append(('conv', it.downsample, x, res, None, 1, False))
-                last = it.convs[-1]
-                y = act(last.co, pick(x, cur, res))
-                steps.append(('conv', last, cur, y, res, d if last.k > 1 else 1, True))
-                x = y
-        size_in = N * H * W * 4
-        return SimpleNamespace(steps=steps, size_in=size_in, size_r=max(shapes), total=size_in + R * max(shapes), last=x, slab=None,
-                               h=live.h, w=live.w)
-
-    def _bind(self, N, H, W):
-        """the program of an input size with its views of the slab.  The slab only grows; when it is replaced, the programs
-        bound to the old one are dropped with it (their views would keep it alive) and made again on their next use."""
-        prog = self._program(N, H, W)
-        if self._slab is None or self._slab.numel() < prog.total:
-            self._slab, self._programs = None, {}
-            self._slab = torch.zeros(prog.total, dtype=torch.float32 if self.precision == 'fp32' else torch.bfloat16,
-                                     device=self.device)
-            prog = self._program(N, H, W)
-        if prog.slab is self._slab:
-            return prog
-        slab = self._slab
-
-        def view(a):
-            if a.view is None:
-                off = 0 if a.region < 0 else prog.size_in + a.region * prog.size_r
-                ld = (4 if self.precision == 'fp32' else 8) if a.region < 0 else a.C
-                nb, h, w = N * a.d * a.d, a.h // a.d, a.w // a.d
-                a.view = slab[off:off + nb * h * w * ld].view(nb, h, w, ld).permute(0, 3, 1, 2)[:, :a.C]
-            return a.view
-        for st in prog.steps:
-            for a in st[1:]:
-                if isinstance(a, SimpleNamespace) and hasattr(a, 'region'):
-                    view(a)
-        prog.x_in = prog.steps[0][2].view              # the stem's source: 3 channels in an ld of 8, ahead of the regions
-        prog.slab = slab
-        self._check_routes(prog)
-        return prog
-
-    def _conv_launches(self, c, src, dst, residual):
-        from .. import ops
-        if residual is None:
-            return ops.conv_eval_ex(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, slot='drn_eval', route_only=True)
-        xp, Nb, Ci, h, w, ldx = ops.geom(src.view)
-        d = ops.conv_desc(Nb, h, w, Ci, c.co, c.k, c.stride, c.pad, ldx, ops.geom(dst.view)[5])
-        need = ops.lib().gcc_conv_eval_workspace(C.byref(d))
-        ws = ops.workspace(need, self.device, 'drn_eval') if need else None
-        return 2 if ops.lib().gcc_conv_eval_route(C.byref(d), ws.numel() if ws is not None else 0) == 5 else 1
-
-    def _check_routes(self, prog):
-        """every conv geometry asked of the library before anything runs: a declined one names its layer; there is no other route"""
-        from .. import ops
-        for st in prog.steps:
-            if st[0] != 'conv':
-                continue
-            if self.precision == 'fp32':
-                _, c, src, dst, _, dil, _ = st
-                if ops.conv_eval_f32(src.view, c.w, c.co, c.k, c.stride, dil * (c.k // 2), dst.view, dilation=dil, route_only=True) < 0:
-                    raise GccError('DrnSegEngine: the library declines the fp32 geometry of %s (%d -> %d channels, %d x %d, stride '
-                                   '%d, dilation %d, on %d x %d x %d): there is no other route'
-                                   % ((c.key, c.ci, c.co, c.k, c.k, c.stride, dil) + tuple(src.view.shape[i] for i in (0, 2, 3))))
-                continue
-            _, c, src, dst, _ = st
-            _, Nb, Ci, h, w, ldx = ops.geom(src.view)
-            d = ops.conv_desc(Nb, h, w, Ci, c.co, c.k, c.stride, c.pad, ldx, ops.geom(dst.view)[5])
-            rc = ops.lib().gcc_conv_eval_ex_route(C.byref(d), 0, 0) if st[4] is None else ops.lib().gcc_conv_eval_route(C.byref(d), 0)
-            if rc < 0:
-                raise GccError('DrnSegEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, on '
-                               '%d x %d x %d): there is no other route' % (c.key, c.ci, c.co, c.k, c.k, c.stride, Nb, h, w))
+    def _declined(self, st):
+        c, src = st[1:3]
+        on = tuple(src.view.shape[i] for i in (0, 2, 3))
+        if self.precision == 'fp32':
+            return ('DrnSegEngine: the library declines the fp32 geometry of %s (%d -> %d channels, %d x %d, stride %d, dilation '
+                    '%d, on %d x %d x %d): there is no other route' % ((c.key, c.ci, c.co, c.k, c.k, c.stride, st[5]) + on))
+        return ('DrnSegEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, on %d x %d x %d): '
+                'there is no other route' % ((c.key, c.ci, c.co, c.k, c.k, c.stride) + on))
 
     @staticmethod
     def _check_size(H, W):
@@ -451,71 +316,37 @@ class DrnSegEngine:
                            'of dilation 4)' % (H, W, SIZE_MULTIPLE))
 
     def _run(self, x, N, H, W, count_only=False):
-        from .. import _lib, ops
         self._check_size(H, W)
-        if self.device is None:
-            raise GccError('DrnSegEngine: .to(device) first')
+        self._check_device()
         prog = self._bind(N, H, W)
-        if self.precision == 'fp32':
-            return self._run_f32(prog, x, N, H, W, count_only)
-        if count_only:
-            n = 1 + 2
-            for st in prog.steps:
-                n += self._conv_launches(*st[1:]) if st[0] == 'conv' else 1
-            return n
-        ops.nchw_to_nhwc(x, prog.x_in, 0, 8)
-        RELU, NONE = _lib.EVAL_ACT_RELU, _lib.EVAL_ACT_NONE
+        f32 = self.precision == 'fp32'
+        if count_only:                                     # the input, the steps, the head's two
+            return 1 + sum(self._conv(st, route_only=True) if st[0] == 'conv' else 1 for st in prog.steps) + 2
+        if f32:
+            ops.nchw_to_nhwc_f32(x, prog.x_in, 4)
+        else:
+            ops.nchw_to_nhwc(x, prog.x_in, 0, 8)
         for st in prog.steps:
-            kind = st[0]
-            if kind == 'conv':
-                _, c, src, dst, res = st
+            if st[0] == 'conv':
                 try:
-                    if res is None:
-                        ops.conv_eval_ex(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, scale=c.scale, shift=c.shift,
-                                         act=RELU if c.relu else NONE, slot='drn_eval')
-                    else:
-                        ops.conv_fprop_eval(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, scale=c.scale, shift=c.shift,
-                                            act=NONE, residual=res.view, slot='drn_eval')
+                    self._conv(st)
                 except GccError as e:
-                    raise GccError('DrnSegEngine: %s: %s' % (c.key, e))
-            elif kind == 'relu':
+                    raise self._conv_error(st, e)
+            elif st[0] == 'relu':
                 ops.relu_(st[1].view)
             else:
                 _, a, b = st
                 ops.phase_regroup(a.view, b.view, a.d, b.d)
-        h, w = prog.h, prog.w
-        scores = torch.empty((N, self.classes, h, w), dtype=torch.float32, device=self.device)
-        logp = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=self.device)
-        ops.seg_head(prog.last.view, self.seg_w, self.seg_b, self.up_w, scores, logp)
-        return logp, scores
-
-    def _run_f32(self, prog, x, N, H, W, count_only):
-        from .. import _lib, ops
-        if count_only:
-            return 1 + len(prog.steps) + 2           # the input, one launch per convolution, the head's two
-        ops.nchw_to_nhwc_f32(x, prog.x_in, 4)
-        RELU, NONE = _lib.EVAL_ACT_RELU, _lib.EVAL_ACT_NONE
-        for _, c, src, dst, res, dil, relu in prog.steps:
-            try:
-                ops.conv_eval_f32(src.view, c.w, c.co, c.k, c.stride, dil * (c.k // 2), dst.view, dilation=dil, scale=c.scale,
-                                  shift=c.shift, act=RELU if relu else NONE, residual=res.view if res is not None else None)
-            except GccError as e:
-                raise GccError('DrnSegEngine: %s: %s' % (c.key, e))
         scores = torch.empty((N, self.classes, prog.h, prog.w), dtype=torch.float32, device=self.device)
         logp = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=self.device)
-        ops.seg_head_f32(prog.last.view, self.seg_w, self.seg_b, self.up_w, scores, logp)
+        (ops.seg_head_f32 if f32 else ops.seg_head)(prog.last.view, self.seg_w, self.seg_b, self.up_w, scores, logp)
         return logp, scores
 
     def __call__(self, x):
-        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
-            raise GccError('DrnSegEngine: expected an NCHW fp32 [N, 3, H, W] tensor, got %s %s'
-                           % (getattr(x, 'dtype', type(x).__name__), tuple(getattr(x, 'shape', ()))))
+        self._check_input(x)
         N, _, H, W = x.shape
         self._check_size(H, W)
-        if self.device is None:
-            raise GccError('DrnSegEngine: .to(device) first')
-        if x.device != self.device:
-            raise GccError('DrnSegEngine: the input is on %s, the engine on %s' % (x.device, self.device))
+        self._check_device(x)
         return self._run(x.contiguous(), N, H, W)
 
     def infer_launches(self, N, H, W):
@@ -524,17 +355,6 @@ class DrnSegEngine:
 
     def flops(self, H, W):
         """multiply-adds x 2 of one image from the shapes (convolutions and the seg conv; the streaming kernels not counted)"""
-        total, h, w = 0, H, W
-        for L in range(9):
-            for it in self.arch.levels[L]:
-                if isinstance(it, _Conv):
-                    h, w = h // it.stride, w // it.stride
-                    total += 2 * h * w * it.co * it.ci * it.k * it.k
-                    continue
-                if it.downsample is not None:
-                    c = it.downsample
-                    total += 2 * (h // c.stride) * (w // c.stride) * c.co * c.ci
-                for c in it.convs:
-                    h, w = h // c.stride, w // c.stride
-                    total += 2 * h * w * c.co * c.ci * c.k * c.k
-        return total + 2 * h * w * self.classes * self.arch.out_channels
+        prog = self._program(1, H, W)
+        total = sum(2 * st[3].h * st[3].w * st[1].co * st[1].ci * st[1].k * st[1].k for st in prog.steps if st[0] == 'conv')
+        return total + 2 * prog.h * prog.w * self.classes * self.arch.out_channels

@@ -18,9 +18,10 @@ from types import SimpleNamespace
 
 import torch
 
-from .._lib import GccError
+from .. import ops
+from .._lib import EVAL_ACT_RELU, GccError
+from ._native import BN_FIELDS, Act, SlabProgramEngine, conv_shape
 
-BN_FIELDS = ('weight', 'bias', 'running_mean', 'running_var')
 BN_EPS = 1e-3                                        # BasicConv2d's BatchNorm2d(eps=0.001): a state_dict does not carry it
 UNUSED_KEYS = ('fc.weight', 'fc.bias')
 MAX_S2, MAX_S1P1, AVG_S1P1 = 0, 1, 2                 # _lib.POOL3_*
@@ -105,10 +106,6 @@ def _net_convs(net):
     return out
 
 
-def _shape(v):
-    return tuple(v.shape) if hasattr(v, 'shape') else tuple(v)
-
-
 def is_fid_inception_state_dict(sd):
     """an Inception3 state_dict by its keys (the first and the last convolution of the FID network)"""
     return isinstance(sd, dict) and 'Conv2d_1a_3x3.conv.weight' in sd and 'Mixed_7c.branch_pool.conv.weight' in sd
@@ -131,22 +128,9 @@ def parse_fid_inception(sd):
             raise GccError('%s: unknown key %s' % (WHAT, key))
 
     def read(c, cin):
-        if c.key not in sd:
-            raise GccError('%s: %s is missing' % (WHAT, c.key))
-        s = _shape(sd[c.key])
-        if len(s) != 4 or s[2:] != c.k:
-            raise GccError('%s: %s has shape %s, expected a %d x %d convolution' % (WHAT, c.key, s, c.k[0], c.k[1]))
-        c.co, c.ci = s[0], s[1]
+        c.co, c.ci = conv_shape(sd, WHAT, c.key, c.bn, c.k)
         if c.ci != cin:
             raise GccError('%s: %s takes %d channels, the layer before it gives %d' % (WHAT, c.key, c.ci, cin))
-        if c.co % 8 or c.co <= 0:
-            raise GccError('%s: %s has %d output channels; widths must be multiples of 8' % (WHAT, c.key, c.co))
-        for f in BN_FIELDS:
-            k = '%s.%s' % (c.bn, f)
-            if k not in sd:
-                raise GccError('%s: %s is missing (BatchNorm behind %s)' % (WHAT, k, c.key))
-            if _shape(sd[k]) != (c.co,):
-                raise GccError('%s: %s has shape %s, expected (%d,)' % (WHAT, k, _shape(sd[k]), c.co))
         return c.co
 
     cin, widths = 3, {}
@@ -168,60 +152,21 @@ def _out(size, k, stride, pad):
     return (size + 2 * pad - k) // stride + 1
 
 
-class InceptionFidEngine:
+class InceptionFidEngine(SlabProgramEngine):
     """inception(x)[0] for fid_eval.ImageStatistics: x NCHW fp32 [N, 3, H, W] in [0, 1] on the device, any H, W -> [features],
     features fp32 [N, d, 1, 1] (d = 2048 for the real network), InceptionV3([3]).forward's list.  Activations are NHWC bf16 with
-    one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic."""
+    one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic.  The
+    engine's scaffold -- .to(), the slab and its programs, the route check -- is metric/_native.py's."""
+    BN_EPS = BN_EPS
 
     def __init__(self, state_dict, resize=299):
         self.arch = parse_fid_inception(state_dict)
-        self.convs = self.arch.convs
         self.d = self.arch.d
         self.resize = int(resize)
         if self.resize <= 0:
             raise GccError('InceptionFidEngine: resize must be positive, got %r' % (resize,))
-        keys = set(c.key for c in self.convs) | set('%s.%s' % (c.bn, f) for c in self.convs for f in BN_FIELDS)
-        self.host = {k: state_dict[k].detach().to('cpu', torch.float32).contiguous() for k in keys}
+        super().__init__(state_dict, self.arch.convs)
         self._plan(1)                                  # a resize too small for the network is refused here, on the host
-        self.device = None
-        self._slab, self._programs = None, {}
-
-    # ---- host -> device: once -------------------------------------------------------------------------------------------
-    def to(self, device):
-        from .. import ops
-        device = torch.device(device)
-        if device.type != 'cuda':
-            raise GccError('InceptionFidEngine runs on the GPU only (asked for %s)' % device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if self.device == device:
-            return self
-        self.device = device
-        self._slab, self._programs = None, {}
-        with torch.cuda.device(device):
-            n = sum(c.co for c in self.convs)
-            bn = torch.empty((4, n), dtype=torch.float32)
-            off = 0
-            for c in self.convs:
-                for i, f in enumerate(BN_FIELDS):
-                    bn[i, off:off + c.co] = self.host['%s.%s' % (c.bn, f)]
-                off += c.co
-            self._bn = bn.to(device)
-            entries, off = [], 0
-            for c in self.convs:
-                g, b, rm, rv = (self._bn[i, off:off + c.co] for i in range(4))
-                entries.append((SimpleNamespace(weight=g, bias=b, running_mean=rm, running_var=rv, eps=BN_EPS), None, c.co))
-                off += c.co
-                master = self.host[c.key].to(device).contiguous(memory_format=torch.channels_last)
-                c.w, _ = ops.pack_weights(master, want_w=True, want_wt=False)
-            self._table = ops.BNEvalTable(entries, device)
-            self._table.run()                          # scale = gamma / sqrt(var + 1e-3), shift = beta - mean scale, fp32
-            for i, c in enumerate(self.convs):
-                c.scale, c.shift = self._table.scale[i], self._table.shift[i]
-        return self
-
-    def eval(self):
-        return self
 
     # ---- the launch program ---------------------------------------------------------------------------------------------
     def _plan(self, N):
@@ -235,10 +180,12 @@ class InceptionFidEngine:
         def act(Cc, h, w, region, ld=None, off=0):
             if h <= 0 or w <= 0:
                 raise GccError('InceptionFidEngine: resize = %d leaves no pixel at %s' % (R, where[0]))
-            ld = ld or Cc
+            a = Act(Cc, h, w, region, ld=ld, off=off)
+            if a.off % 8 or a.ld % 8:
+                raise GccError('InceptionFidEngine: a channel slice at %d of %d is off the 8-channel grid' % (a.off, a.ld))
             if off == 0:
-                sizes.append(N * h * w * ld)
-            return SimpleNamespace(C=Cc, h=h, w=w, region=region, ld=ld, off=off, view=None)
+                sizes.append(N * h * w * a.ld)
+            return a
 
         def free(a):
             """the temporary `a` is not in"""
@@ -265,7 +212,7 @@ class InceptionFidEngine:
             steps.append(('pool', mode, cur, dst))
             return dst
 
-        x = SimpleNamespace(C=3, h=R, w=R, region=-1, ld=8, off=0, view=None)
+        x = Act(3, R, R, -1, ld=8)
         for item in self.arch.net:
             if item[0] == 'conv':
                 c = item[1]
@@ -303,81 +250,34 @@ class InceptionFidEngine:
         return SimpleNamespace(steps=steps, size_in=N * R * R * 8, size_r=max(sizes), last=x, slab=None, x_in=None,
                                total=N * R * R * 8 + 4 * max(sizes))
 
-    def _program(self, N):
-        prog = self._programs.get(N)
-        if prog is None:
-            prog = self._programs[N] = self._plan(N)
-        return prog
-
-    def _bind(self, N):
-        """the program of a batch size with its views of the slab.  The slab only grows; when it is replaced, the programs bound
-        to the old one are dropped with it (their views would keep it alive) and made again on their next use."""
-        prog = self._program(N)
-        if self._slab is None or self._slab.numel() < prog.total:
-            self._slab, self._programs = None, {}
-            self._slab = torch.zeros(prog.total, dtype=torch.bfloat16, device=self.device)
-            prog = self._program(N)
-        if prog.slab is self._slab:
-            return prog
-        slab = self._slab
-
-        def view(a):
-            if a.view is None:
-                base = 0 if a.region < 0 else prog.size_in + a.region * prog.size_r
-                if a.off % 8 or a.ld % 8:
-                    raise GccError('InceptionFidEngine: a channel slice at %d of %d is off the 8-channel grid' % (a.off, a.ld))
-                a.view = slab[base:base + N * a.h * a.w * a.ld].view(N, a.h, a.w, a.ld).permute(0, 3, 1, 2)[:, a.off:a.off + a.C]
-            return a.view
-        for st in prog.steps:
-            for a in st[1:]:
-                if isinstance(a, SimpleNamespace) and hasattr(a, 'region'):
-                    view(a)
-        view(prog.last)
-        prog.x_in = prog.steps[0][2].view               # the first conv's source: 3 channels in an ld of 8, ahead of the regions
-        prog.slab = slab
-        self._check_routes(prog)
-        return prog
-
-    def _conv(self, c, src, dst, route_only=False):
-        from .. import _lib, ops
-        kw = dict(slot='inception_eval', route_only=route_only)
-        if not route_only:
-            kw.update(scale=c.scale, shift=c.shift, act=_lib.EVAL_ACT_RELU)
+    def _conv(self, st, route_only=False):
+        """launch the 'conv' step st, or with route_only the library's answer for it: its launches, -1 if it declines"""
+        _, c, src, dst = st
         if c.k[0] != c.k[1]:
-            return ops.conv_eval_rect(src.view, c.w, c.co, c.k, c.stride, dst.view, **kw)
-        return ops.conv_eval_ex(src.view, c.w, c.co, c.k[0], c.stride, c.pad[0], dst.view, **kw)
+            return ops.conv_eval_rect(src.view, c.w, c.co, c.k, c.stride, dst.view, scale=c.scale, shift=c.shift, act=EVAL_ACT_RELU,
+                                      slot='inception_eval', route_only=route_only)
+        return ops.conv_eval_ex(src.view, c.w, c.co, c.k[0], c.stride, c.pad[0], dst.view, scale=c.scale, shift=c.shift,
+                                act=EVAL_ACT_RELU, slot='inception_eval', route_only=route_only)
 
-    def _check_routes(self, prog):
-        """every conv geometry asked of the library before anything runs: a declined one names its layer; there is no other route"""
-        import ctypes as C
-        from .. import ops
-        for st in prog.steps:
-            if st[0] != 'conv':
-                continue
-            _, c, src, dst = st
-            _, Nb, Ci, h, w, ldx = ops.geom(src.view)
-            square = c.k[0] == c.k[1]
-            d = ops.conv_desc(Nb, h, w, Ci, c.co, c.k[0], c.stride, c.pad[0] if square else 0, ldx, ops.geom(dst.view)[5])
-            d.KW = c.k[1]
-            if ops.lib().gcc_conv_eval_ex_route(C.byref(d), 0, 0) < 0:
-                raise GccError('InceptionFidEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, '
-                               'on %d x %d x %d): there is no other route' % (c.key, c.ci, c.co, c.k[0], c.k[1], c.stride, Nb, h, w))
+    def _declined(self, st):
+        c, src = st[1:3]
+        return ('InceptionFidEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, on %d x %d x '
+                '%d): there is no other route' % ((c.key, c.ci, c.co, c.k[0], c.k[1], c.stride)
+                                                  + tuple(src.view.shape[i] for i in (0, 2, 3))))
 
     def _run(self, x, N, count_only=False):
-        from .. import ops
-        if self.device is None:
-            raise GccError('InceptionFidEngine: .to(device) first')
+        self._check_device()
         prog = self._bind(N)
         if count_only:
-            return 2 + sum(self._conv(*st[1:], route_only=True) if st[0] == 'conv' else 1 for st in prog.steps)
+            return 2 + sum(self._conv(st, route_only=True) if st[0] == 'conv' else 1 for st in prog.steps)
         ops.fid_resize(x, prog.x_in)
         for st in prog.steps:
             kind = st[0]
             if kind == 'conv':
                 try:
-                    self._conv(*st[1:])
+                    self._conv(st)
                 except GccError as e:
-                    raise GccError('InceptionFidEngine: %s: %s' % (st[1].key, e))
+                    raise self._conv_error(st, e)
             elif kind == 'pool':
                 ops.pool3x3(st[1], st[2].view, st[3].view)
             else:
@@ -387,13 +287,8 @@ class InceptionFidEngine:
         return [out]
 
     def __call__(self, x):
-        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or 0 in x.shape:
-            raise GccError('InceptionFidEngine: expected an NCHW fp32 [N, 3, H, W] tensor, got %s %s'
-                           % (getattr(x, 'dtype', type(x).__name__), tuple(getattr(x, 'shape', ()))))
-        if self.device is None:
-            raise GccError('InceptionFidEngine: .to(device) first')
-        if x.device != self.device:
-            raise GccError('InceptionFidEngine: the input is on %s, the engine on %s' % (x.device, self.device))
+        self._check_input(x, refuse_empty=True)
+        self._check_device(x)
         return self._run(x.contiguous(), x.shape[0])
 
     def infer_launches(self, N, H=None, W=None):

@@ -626,20 +626,26 @@ def conv_y2_in_launch(x, w, Co, k, stride, pad, out):
 
 
 def conv_fprop_eval(x, w, Co, k, stride, pad, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slope=None, residual=None,
-                    slot='eval'):
+                    slot='eval', route_only=False):
     """inference conv (gcc_conv_fprop_eval): out = act(scale[c] conv(x, w) + shift[c]) (+ residual), one bf16 rounding, no
     statistics.  slope: the PReLU slope as a DEVICE tensor (never read on the host).  Split-K scratch comes from the grow-only
-    workspace `slot` (not the training path's)."""
+    workspace `slot` (not the training path's).
+    route_only: -1 when the library declines the geometry, else the launches the call would make (1, or 2: split-K partials +
+    fold) without launching."""
     xp, N, Ci, H, W, ldx = geom(x)
     yp, _, _, _, _, ldy = geom(out)
     d = conv_desc(N, H, W, Ci, Co, k, stride, pad, ldx, ldy)
+    if route_only and lib().gcc_conv_eval_route(C.byref(d), 0) < 0:
+        return -1
+    need = lib().gcc_conv_eval_workspace(C.byref(d))
+    ws = workspace(need, x.device, slot) if need else None
+    if route_only:
+        return 2 if lib().gcc_conv_eval_route(C.byref(d), ws.numel() if ws is not None else 0) == 5 else 1
     ep = _lib.eval_epilogue_t(_p(scale), _p(shift), _p(slope), None, 0, 0, act, 0, None, 0)
     if residual is not None:
         rp, _, _, _, _, ldr = geom(residual)
         ep.residual, ep.ld_residual = rp, ldr
-    need = lib().gcc_conv_eval_workspace(C.byref(d))
-    if need:
-        ws = workspace(need, x.device, slot)
+    if ws is not None:
         ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws.numel()
     check(lib().gcc_conv_fprop_eval(C.byref(d), xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_fprop_eval')
     return out
@@ -650,7 +656,8 @@ def conv_eval_ex(x, w, Co, k, stride, pad, out, transposed=False, scale=None, sh
     """inference conv, forward or transposed (gcc_conv_eval_ex): z = scale[c] conv(x, w) + shift[c]; out = act(z), y2 = act2(z),
     one bf16 rounding each, no statistics.  Forward: w = W, Co output channels.  Transposed (ConvTranspose2d forward, what
     conv_dgrad computes): w = Wt, Co = channels of `out`.  Split-K scratch from the grow-only workspace `slot`.
-    route_only: return the launches the call would make (1 or 2: split-K partials + fold) without launching."""
+    route_only: -1 when the library declines the geometry, else the launches the call would make (1, or 2: split-K partials +
+    fold) without launching."""
     xp, N, Cx, Hx, Wx, ldx = geom(x)
     yp, _, Cy, Hy, Wy, ldy = geom(out)
     if not transposed:
@@ -658,6 +665,8 @@ def conv_eval_ex(x, w, Co, k, stride, pad, out, transposed=False, scale=None, sh
     else:
         d = conv_desc(N, Hy, Wy, Co, Cx, k, stride, pad, ldy, ldx)
     tr = 1 if transposed else 0
+    if route_only and lib().gcc_conv_eval_ex_route(C.byref(d), tr, 0) < 0:
+        return -1
     need = lib().gcc_conv_eval_ex_workspace(C.byref(d), tr)
     ws = workspace(need, x.device, slot) if need else None
     if route_only:

@@ -1,7 +1,8 @@
 """Host side of the native DRN-D segmenter (gcc_amd.metric.drn_seg): the architecture read from a DRNSeg state_dict's keys and
 shapes, every refusal, the phase-layout rule against torch's dilated convolution, the engine's launch program executed
 with torch on the host against the reference's results (tests/golden/drn_seg.npz, written by tests/golden/make_drn_fixtures.py
-from the reference's own DRNSeg), builtin_segmenter's selection rule and the ABI surface.  No GPU."""
+from the reference's own DRNSeg), the launch count and the slab's life against a recording stand-in for gcc_amd.ops,
+builtin_segmenter's selection rule and the ABI surface.  No GPU."""
 import os
 import re
 from collections import OrderedDict
@@ -209,6 +210,129 @@ def test_emulation_error_is_what_the_fixture_stores(z):
         _, se = E.forward(sd, x, emulate=True)
         e = float((se - torch.from_numpy(z[name + '.scores'])).abs().max())
         assert abs(e - float(z[name + '.emul_err'])) <= 0.05 * float(z[name + '.emul_err']), (name, e)
+
+
+# ---- 3b. the launch count and the slab, against a recording stand-in for gcc_amd.ops -----------------------------------------------
+class _Recorder:
+    """stands in for gcc_amd.ops under an engine: records what would be launched.  A bf16 conv with 16 or more input channels takes
+    the split-K route (two launches), so the count has to come from the route and not from the number of steps; the fp32 conv's
+    route answer is a tile index, never a count: it is one launch whatever the answer."""
+
+    def __init__(self):
+        self.calls = []
+
+    def route(self, x):
+        return 2 if x.shape[1] >= 16 else 1
+
+    def _conv(self, name, x, k, stride, pad, out, dilation, act, residual):
+        return (name, k, stride, pad, dilation, act, residual is not None, tuple(x.shape), tuple(out.shape))
+
+    def conv_eval_ex(self, x, w, Co, k, stride, pad, out, act=None, slot=None, route_only=False, **kw):
+        assert slot == 'drn_eval'
+        if route_only:
+            return self.route(x)
+        self.calls += [self._conv('conv_eval_ex', x, k, stride, pad, out, 1, act, None)] * self.route(x)
+
+    def conv_fprop_eval(self, x, w, Co, k, stride, pad, out, act=None, residual=None, slot=None, route_only=False, **kw):
+        assert slot == 'drn_eval'
+        if route_only:
+            return self.route(x)
+        self.calls += [self._conv('conv_fprop_eval', x, k, stride, pad, out, 1, act, residual)] * self.route(x)
+
+    def conv_eval_f32(self, x, w, Co, k, stride, pad, out, dilation=1, act=None, residual=None, route_only=False, **kw):
+        if route_only:
+            return self.route(x)
+        self.calls.append(self._conv('conv_eval_f32', x, k, stride, pad, out, dilation, act, residual))
+
+    def nchw_to_nhwc(self, src, dst, off=0, cfill=None):
+        self.calls.append(('input', tuple(src.shape), tuple(dst.shape), cfill))
+
+    def nchw_to_nhwc_f32(self, src, dst, cfill=None):
+        self.calls.append(('input', tuple(src.shape), tuple(dst.shape), cfill))
+
+    def phase_regroup(self, src, dst, d_src, d_dst):
+        self.calls.append(('regroup', d_src, d_dst, tuple(src.shape), tuple(dst.shape)))
+
+    def relu_(self, x):
+        self.calls.append(('relu', tuple(x.shape)))
+
+    def seg_head(self, x, seg_w, seg_b, up_w, scores, logp=None):
+        self.calls += [('head', tuple(x.shape), tuple(scores.shape), tuple(logp.shape))] * 2       # the seg conv, then up + LogSoftmax
+
+    seg_head_f32 = seg_head
+
+
+def _inside(view, slab):
+    """the storage a view can reach lies inside the slab"""
+    first = view.data_ptr()
+    last = first + sum((n - 1) * s for n, s in zip(view.shape, view.stride())) * view.element_size()
+    return slab.data_ptr() <= first and last < slab.data_ptr() + slab.numel() * slab.element_size()
+
+
+@pytest.mark.parametrize('precision', ['bf16', 'fp32'])
+def test_infer_launches_and_the_slab_against_a_recording_stand_in(monkeypatch, z, precision):
+    from gcc_amd import _lib, ops
+    from gcc_amd.metric.drn_seg import DrnSegEngine
+    rec = _Recorder()
+    for name in ('conv_eval_ex', 'conv_fprop_eval', 'conv_eval_f32', 'nchw_to_nhwc', 'nchw_to_nhwc_f32', 'phase_regroup', 'relu_',
+                 'seg_head', 'seg_head_f32'):
+        monkeypatch.setattr(ops, name, getattr(rec, name))
+    sd, x = E.fixture_net(z, 'bneck')
+    N, _, H, W = x.shape
+    eng = DrnSegEngine(sd, precision=precision)
+    monkeypatch.setattr(eng, '_check_routes', lambda prog: None)          # the library's say: asked on the GPU
+    eng.device = torch.device('cpu')                                        # as .to() leaves it, without packing anything
+    for c in eng.convs:
+        c.w = c.scale = c.shift = None
+    eng.seg_w = eng.seg_b = eng.up_w = None
+    # the shared _bind on a host slab: N = 1, then the full batch, then N = 1 again
+    eng._run(torch.zeros(1, 3, H, W), 1, H, W)
+    small, old = eng._slab, eng._program(1, H, W)
+    assert old.slab is small
+    predicted = eng.infer_launches(N, H, W)
+    assert eng._slab is not small and eng._slab.numel() > small.numel()     # replaced by a larger one ...
+    assert all(p.slab is eng._slab and p is not old for p in eng._programs.values())       # ... and no program keeps the old
+    ptr = eng._slab.data_ptr()
+    eng._run(torch.zeros(1, 3, H, W), 1, H, W)
+    assert eng._slab.data_ptr() == ptr and sorted(eng._programs) == [(1, H, W), (N, H, W)]
+    for prog in eng._programs.values():
+        assert prog.slab is eng._slab and _inside(prog.x_in, eng._slab)
+        views = [a.view for st in prog.steps for a in st[1:] if hasattr(a, 'region')] + [prog.last.view]
+        assert len(views) > len(eng.convs) and all(v is not None and _inside(v, eng._slab) for v in views)
+    # the count
+    rec.calls.clear()
+    assert eng.infer_launches(N, H, W) == predicted and rec.calls == []     # counting launches nothing
+    logp, scores = eng._run(x, N, H, W)
+    assert tuple(logp.shape) == (N, 19, H, W) and tuple(scores.shape) == (N, 19, H // 8, W // 8)
+    assert len(rec.calls) == predicted
+    kinds = [c[0] for c in rec.calls]
+    assert kinds[0] == 'input' and kinds[-1] == 'head' and kinds.count('input') == 1 and kinds.count('head') == 2
+    blocks = [b for L in (3, 4, 5, 6) for b in eng.arch.levels[L]]
+    lasts = {b.convs[-1].key for b in blocks}
+    convs = [c for c in rec.calls if c[0].startswith('conv')]
+    with_res = [c for c in convs if c[6]]
+    if precision == 'bf16':
+        assert kinds.count('regroup') == 4 and [c[1:3] for c in rec.calls if c[0] == 'regroup'] == [(1, 2), (2, 4), (4, 2), (2, 1)]
+        assert kinds.count('relu') == len(blocks)
+        assert rec.calls[1][-2][1] == 3 and rec.calls[0][3] == 8            # 3 channels in an ld of 8
+        # a residual goes to exactly the blocks' last convs, through conv_fprop_eval, without an activation
+        assert {c[0] for c in with_res} == {'conv_fprop_eval'} and all(c[5] == _lib.EVAL_ACT_NONE for c in with_res)
+        assert all(c[6] for c in convs if c[0] == 'conv_fprop_eval')
+        steps = [st for st in eng._program(N, H, W).steps if st[0] == 'conv']
+        assert {st[1].key for st in steps if st[4] is not None} == lasts
+        assert len(with_res) == sum(rec.route(st[2].view) for st in steps if st[4] is not None)
+        assert 'conv_eval_f32' not in kinds and len(convs) > len(eng.convs)  # some convs took two launches
+    else:
+        assert len(convs) == len(eng.convs) and {c[0] for c in convs} == {'conv_eval_f32'}
+        assert 'regroup' not in kinds and 'relu' not in kinds and rec.calls[0][3] == 4
+        steps = eng._program(N, H, W).steps
+        assert sorted(st[1].key for st in steps) == sorted(c.key for c in eng.convs)
+        assert {st[1].key for st in steps if st[4] is not None} == lasts and len(with_res) == len(blocks)
+        assert all(c[5] == _lib.EVAL_ACT_RELU for c in with_res)            # the ReLU behind the sum rides on the conv
+        assert {c[4] for c in convs} == {1, 2, 4}
+        assert all(c[3] == c[4] for c in convs if c[1] == 3) and all(c[3] == 0 and c[4] == 1 for c in convs if c[1] == 1)
+        assert all(c[3] == 3 and c[4] == 1 for c in convs if c[1] == 7)
+        assert predicted == 1 + len(eng.convs) + 2
 
 
 # ---- 4. selection ---------------------------------------------------------------------------------------------------------------

@@ -73,6 +73,18 @@ def _check_variants(ops, _lib, x, w, scale, shift, res, wp, Co):
             assert bool((base[..., Co:] == 0).all())
 
 
+def _assert_route_only(ops, case, Co, launches):
+    """conv_fprop_eval(route_only=True) gives the launches the call would make, and launches nothing"""
+    xd, wp = _nhwc(ops, case[0]), case[-1]
+    N, _, H, W = xd.shape
+    out = ops.new_act(N, Co, H, W, DEV)
+    torch.cuda.synchronize()
+    L = ops.lib()
+    L.gcc_launch_count(1)
+    assert ops.conv_fprop_eval(xd, wp, Co, 3, 1, 1, out, route_only=True) == launches
+    assert L.gcc_launch_count(0) == 0
+
+
 @pytest.mark.parametrize('thin', [1, 0])
 @pytest.mark.parametrize('Ci,Co', [(64, 64), (64, 24), (24, 64), (13, 64)])
 @pytest.mark.parametrize('geom', sorted(GEOMS))
@@ -87,6 +99,7 @@ def test_eval_epilogue_each_route(geom, Ci, Co, thin):
         expect = 4 if (thin and geom == 'ring3' and Ci % 8 == 0) else 0
         assert route == expect, (route, expect)
         case = _eval_case(ops, _lib, N, H, W, Ci, Co, Ci * 131 + Co * 7 + H)
+        _assert_route_only(ops, case, Co, 1)                 # route 0 and the ring kernel alike: one launch
         _check_variants(ops, _lib, *case, Co)
     finally:
         L.gcc_set_option(_lib.OPT_IGEMM_THIN, prev)
@@ -103,6 +116,7 @@ def test_eval_epilogue_split_k(Ci, Co):
     assert ops.lib().gcc_conv_eval_route(ctypes.byref(d), ws) == 5
     assert ops.lib().gcc_conv_eval_route(ctypes.byref(d), 0) == 0
     case = _eval_case(ops, _lib, N, H, W, Ci, Co, 77 + Co)
+    _assert_route_only(ops, case, Co, 2)                     # partials, then the fold
     _check_variants(ops, _lib, *case, Co)
 
 

@@ -162,6 +162,26 @@ def test_eval_ex_rejects_bad_arguments():
     assert L.gcc_conv_fprop_eval(ctypes.byref(d3), x.data_ptr(), w.data_ptr(), y.data_ptr(), ctypes.byref(ev), None) == -1
 
 
+def test_eval_ex_route_only_says_when_the_library_declines():
+    """ops.conv_eval_ex(route_only=True): -1 for a geometry gcc_conv_eval_ex_route declines, nothing launched.  (conv_eval_ex has
+    one k for both directions, so the declined geometries it can state are these: a kernel larger than the padded map, and a
+    transposed conv whose kernel is smaller than its stride.)"""
+    from gcc_amd import ops
+    L = ops.lib()
+    w = torch.zeros(16 * 9 * 16, dtype=torch.bfloat16, device=DEV)
+    x2, x8, y4, y16 = (ops.new_act(1, 16, s, s, DEV) for s in (2, 8, 4, 16))
+    d = ops.conv_desc(1, 2, 2, 16, 16, 3, 1, 0, 16, 16)                      # 3 x 3, no padding, on 2 x 2: no output pixel
+    assert L.gcc_conv_eval_ex_route(ctypes.byref(d), 0, 0) < 0
+    dt = ops.conv_desc(1, 16, 16, 16, 16, 1, 2, 0, 16, 16)                   # transposed 1 x 1 of stride 2: holes in the output
+    assert L.gcc_conv_eval_ex_route(ctypes.byref(dt), 1, 0) < 0
+    torch.cuda.synchronize()
+    L.gcc_launch_count(1)
+    assert ops.conv_eval_ex(x2, w, 16, 3, 1, 0, x2, route_only=True) == -1
+    assert ops.conv_eval_ex(x8, w, 16, 1, 2, 0, y16, transposed=True, route_only=True) == -1
+    assert ops.conv_eval_ex(x8, w, 16, 4, 2, 1, y4, route_only=True) in (1, 2)          # and an accepted one keeps its count
+    assert L.gcc_launch_count(0) == 0
+
+
 # ---- 2. against the reference's images -------------------------------------------------------------------------------
 def test_infer_matches_reference_eval_image(golden_dir):
     z = np.load(os.path.join(golden_dir, 'pix2pix_eval_d8.npz'))
