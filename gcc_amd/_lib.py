@@ -215,6 +215,7 @@ PROTOTYPES = {
     'gcc_dwconv3x3_wgrad_workspace': (_Z, [_I, _I, _I, _I]),
     'gcc_dwconv3x3_reflect_wgrad': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     'gcc_bn_eval_coeffs': (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P]),
+    'gcc_bn_eval_state': (_I, [_P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P]),
     'gcc_bnact_fwd': (_I, [C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _Z, _P]),
     'gcc_conv_bn_act_workspace': (_Z, [C.POINTER(conv_t), _I]),
     'gcc_conv_fprop_eval': (_I, [C.POINTER(conv_t), _P, _P, _P, C.POINTER(eval_epilogue_t), _P]),

@@ -81,13 +81,16 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
 }
 
 __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
-                                      int C, float* scale, float* shift) {
+                                      int C, float* scale, float* shift, float* mean, float* rstd) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) {
         const float r = 1.f / sqrtf(rv[c] + eps);
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         scale[c] = g * r;
         shift[c] = b - rm[c] * g * r;
+        // what the eval-mode backward reads (gcc_bnact_bwd, bn_eval): the statistics the forward normalised with
+        if (mean) mean[c] = rm[c];
+        if (rstd) rstd[c] = r;
     }
 }
 
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(256) void bnact_fwd_kernel(const FwdArgs a) {
             float rv[8];
             unpack8(rres, rv);
 #pragma unroll
-            for (int j = 0; j < 8; j++) o1[j] += rv[j];
+            for (int j = 0; j < 8; j++) o1[j] = c0 + j < a.C ? o1[j] + rv[j] : o1[j];     // pad channels stay zero whatever the residual's hold
         }
         if (yg) *(i32x4*)(yg + pix * a.ldy + a.yoff + c0) = pack8(o1);
         if (y2g) *(i32x4*)(y2g + pix * a.ldy2 + a.y2off + c0) = pack8(o2);
@@ -464,6 +467,14 @@ __global__ __launch_bounds__(NTH) void bnact_bwd_reduce_kernel(const BwdArgs a0)
 #pragma unroll
                 for (int j = 0; j < V; j++) dz[j] *= act_grad_from_out(xv[j], a.in_act, a.in_slope);
             }
+#pragma unroll
+            for (int j = 0; j < V; j++) {
+                const float xh = (xv[j] - mu[j]) * rs[j];
+                s0[j] += dz[j];
+                s1[j] += dz[j] * xh;
+            }
+            // eval mode: dx = gamma rstd dz, behind the sums (d(beta) = sum dz, d(gamma) = sum dz xhat: the gradient that
+            // reaches the normalisation's output, as in training mode)
             if (evs != 0.f) {
                 if constexpr (GATE || DROP) {
 #pragma unroll
@@ -472,12 +483,6 @@ __global__ __launch_bounds__(NTH) void bnact_bwd_reduce_kernel(const BwdArgs a0)
 #pragma unroll
                     for (int j = 0; j < V; j++) dz[j] *= rs[j] * (a.p.gamma ? a.p.gamma[c0 + j < a.C ? c0 + j : 0] : 1.f);
                 }
-            }
-#pragma unroll
-            for (int j = 0; j < V; j++) {
-                const float xh = (xv[j] - mu[j]) * rs[j];
-                s0[j] += dz[j];
-                s1[j] += dz[j] * xh;
             }
             stv<V>(a.dx + pix * a.lddx + a.dxoff + c0, dz);
         }
@@ -2259,15 +2264,22 @@ extern "C" int gcc_bn_finalize(const float* stats_partial, int tiles, int C, dou
     return GCC_OK;
 }
 
+extern "C" int gcc_bn_eval_state(const float* gamma, const float* beta, const float* running_mean,
+                                 const float* running_var, float eps, int C, float* mean, float* rstd, float* scale,
+                                 float* shift, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!running_mean || !running_var || !scale || !shift || C <= 0) return GCC_ERR_BAD_ARG;
+    hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta,
+                       running_mean, running_var, eps, C, scale, shift, mean, rstd);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
 extern "C" int gcc_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                                   const float* running_var, float eps, int C, float* scale, float* shift,
                                   gcc_stream_t stream) {
     GCC_ENTER();
-    if (!running_mean || !running_var || !scale || !shift || C <= 0) return GCC_ERR_BAD_ARG;
-    hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta,
-                       running_mean, running_var, eps, C, scale, shift);
-    GCC_CHECK_LAUNCH();
-    return GCC_OK;
+    return gcc_bn_eval_state(gamma, beta, running_mean, running_var, eps, C, nullptr, nullptr, scale, shift, stream);
 }
 
 // eval-mode coefficients of a group of BatchNorms / conv biases, one workgroup per item (include/gcc_hip.h)
@@ -2383,7 +2395,7 @@ extern "C" int gcc_bnact_bwd_ex(const gcc_bnact_bwd_t* p, int in_act, float in_s
     if (!p || !x || !g1 || !dx || !ws || C <= 0 || pixels == 0) return GCC_ERR_BAD_ARG;
     if (!aligned8(ldx, xoff) || !aligned8(ldg1, g1off) || !aligned8(lddx, dxoff)) return GCC_ERR_BAD_ARG;
     if ((y && !aligned8(ldy, yoff)) || (g2 && !aligned8(ldg2, g2off))) return GCC_ERR_BAD_ARG;
-    if (p->bn && !p->bn_eval && (!p->mean || !p->rstd)) return GCC_ERR_BAD_ARG;
+    if (p->bn && (!p->mean || !p->rstd)) return GCC_ERR_BAD_ARG;      // eval mode reads them too (gcc_bn_eval_state)
     const int groups = p->groups > 1 ? p->groups : 1;
     if (ws_bytes < gcc_bnact_bwd_workspace(C, pixels) * groups) return GCC_ERR_WORKSPACE;
     if (groups > 1 && (p->dgamma || p->dbeta || p->dalpha)) return GCC_ERR_UNSUPPORTED;

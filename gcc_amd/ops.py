@@ -1092,9 +1092,10 @@ def bn_finalize(stats, count, gamma, beta, running_mean, running_var, st, eps=1e
 
 
 def bn_eval_coeffs(gamma, beta, running_mean, running_var, st, eps=1e-5):
-    check(lib().gcc_bn_eval_coeffs(gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
-                                   eps, gamma.numel(), st.scale.data_ptr(), st.shift.data_ptr(), stream()),
-          'gcc_bn_eval_coeffs')
+    """eval mode: scale / shift of the forward, and mean / rstd (the running statistics) for a backward pass through it"""
+    check(lib().gcc_bn_eval_state(gamma.data_ptr(), beta.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
+                                  eps, gamma.numel(), st.mean.data_ptr(), st.rstd.data_ptr(), st.scale.data_ptr(),
+                                  st.shift.data_ptr(), stream()), 'gcc_bn_eval_state')
 
 
 def _p(t):

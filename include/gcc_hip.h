@@ -374,6 +374,10 @@ int gcc_channel_stats(const void* x, int ld, int off, int C, size_t pixels_per_g
 int gcc_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, int C, float* scale, float* shift,
                        gcc_stream_t stream);
+/* ... and, for a backward pass through the eval-mode layer (gcc_bnact_bwd with bn_eval), the statistics it normalised with:
+ * mean = running_mean, rstd = 1 / sqrt(running_var + eps) (either may be NULL).  Added without a GCC_HIP_ABI bump (an addition). */
+int gcc_bn_eval_state(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                      int C, float* mean, float* rstd, float* scale, float* shift, gcc_stream_t stream);
 
 typedef struct {
     const float* scale;   /* [C] or NULL (identity) */
@@ -533,7 +537,8 @@ int gcc_image_to_u8(const void* x, int ld, int off, size_t pixels, void* out, gc
  * bn == 0 : no normalisation (plain act backward: dx = g*m, no statistics). */
 typedef struct {
     int bn;                  /* 1: through BatchNorm (training statistics) */
-    int bn_eval;             /* 1: BN used running stats (dx = dz*scale) */
+    int bn_eval;             /* 1: BN used running stats (dx = dz*scale); mean / rstd are then the running statistics
+                                (gcc_bn_eval_state), dgamma / dbeta the sums over the unscaled dz */
     const float* mean;       /* saved mean [C] */
     const float* rstd;       /* saved rstd [C] */
     const float* gamma;      /* [C] */

@@ -11,7 +11,9 @@ at their loop edges in tests/test_misc_kernels_gpu.py, which also says which tes
 replay and event entry points; the depthwise / reflection-pad kernels of dwconv.hip, and spectral.hip
 and the training kernels of attention.hip, at pruned channel counts, small planes, strides, slices and
 loop edges, per element against float64, in tests/test_dwconv_kernels_gpu.py and
-tests/test_sagan_kernels_gpu.py.  The one-shape tests of those kernels below stay as they are."""
+tests/test_sagan_kernels_gpu.py; the norm and activation kernels of norm_act.hip, per element against float64 on every
+backward route, in channel windows and in eval mode, in tests/test_norm_kernels_gpu.py.  The one-shape tests of those kernels
+below stay as they are."""
 import math
 import os
 
