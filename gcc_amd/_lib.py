@@ -228,6 +228,8 @@ PROTOTYPES = {
     'gcc_conv_eval_f32': (_I, [C.POINTER(conv_t), _P, _P, _P, C.POINTER(eval_f32_epilogue_t), _P]),
     'gcc_conv_eval_f32_route': (_I, [C.POINTER(conv_t), _I]),
     'gcc_conv_eval_f32_kp': (_I, [_I, _I, _I]),
+    'gcc_conv_eval_f32_ex': (_I, [C.POINTER(conv_t), _I, _I, _P, _P, _P, C.POINTER(eval_f32_epilogue_t), _P]),
+    'gcc_conv_eval_f32_ex_route': (_I, [C.POINTER(conv_t), _I, _I, _I]),
     'gcc_nchw_f32_to_nhwc_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_dw_inorm_fwd': (_I, [C.POINTER(dw_inorm_t), _P]),
@@ -266,6 +268,9 @@ PROTOTYPES = {
     'gcc_pool3x3': (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_border_copy': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_global_avgpool': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'gcc_fid_resize_f32': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
+    'gcc_pool3x3_f32': (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'gcc_global_avgpool_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'gcc_argmax_channels': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_confusion_hist': (_I, [_P, _P, _Z, _I, _P, _P]),
     'gcc_psnr_workspace': (_Z, []),

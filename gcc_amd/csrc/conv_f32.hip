@@ -1,6 +1,7 @@
 // Inference convolution in fp32 on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain,
 // at 1/16 of the bf16 MFMA rate): gcc_conv_eval_f32, the evaluator networks at the reference's own precision
-// (gcc_amd/metric/drn_seg.py, precision 'fp32').
+// (gcc_amd/metric/drn_seg.py, precision 'fp32'), and gcc_conv_eval_f32_ex, the same kernel with KH, KW and the two paddings
+// independent (gcc_amd/metric/inception_fid.py, precision 'fp32': 5 x 5, (1, 7) / (7, 1), padding 0).
 //
 // Implicit GEMM: M = N Ho Wo output pixels, N = Co, K = KH KW Cip (Cip = Ci, or 4 for the 3-channel stem).  A workgroup of four
 // waves owns one BM x BN output tile and walks ALL of K in steps of 16: no split-K, no atomics, no inter-workgroup state.
@@ -25,7 +26,7 @@ constexpr int CF_BK = 16, CF_LDK = CF_BK + 4, CF_THREADS = 256;
 struct ConvF32Args {
     const float* x; const float* w; float* y;
     const float* scale; const float* shift; const float* res;
-    int M, H, W, Ho, Wo, Ci, Cip, Co, KW, stride, pad, dil;
+    int M, H, W, Ho, Wo, Ci, Cip, Co, KW, stride, pad_h, pad_w, dil;
     int ldx, xoff, ldy, yoff, ldr, roff, Kreal, Kp, relu;
     FastDiv dWo, dHo, dCip, dKW;
 };
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
         if (m < a.M) {
             const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;
             const int n = fdiv(q, a.dHo), oh = q - n * a.Ho;
-            ih0[i] = oh * a.stride - a.pad; iw0[i] = ow * a.stride - a.pad; nb[i] = n * a.H * a.W;
+            ih0[i] = oh * a.stride - a.pad_h; iw0[i] = ow * a.stride - a.pad_w; nb[i] = n * a.H * a.W;
         } else {
             ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
         }
@@ -172,56 +173,73 @@ __global__ __launch_bounds__(CF_THREADS) void nchw_to_nhwc_f32_kernel(const floa
 inline int cf_cip(int Ci) { return Ci == 3 ? 4 : Ci; }
 inline int cf_kp(int Ci, int KH, int KW) { return (KH * KW * cf_cip(Ci) + CF_BK - 1) / CF_BK * CF_BK; }
 
-// the tile of a geometry (0: 128 x 128, 1: 64 x 64, 2: 128 x 32), or the error the call returns for it
-int cf_route(const gcc_conv_t* c, int dilation) {
+// the tile of M pixels x Co channels (0: 128 x 128, 1: 64 x 64, 2: 128 x 32)
+inline int cf_tile(long long M, int Co) {
+    if (Co <= 32) return 2;
+    const long long big = ((M + 127) / 128) * ((Co + 127) / 128);
+    return (Co >= 128 && big >= 256) ? 0 : 1;              // 128 x 128 tiles once they fill the chip, else 64 x 64
+}
+
+// what both entries refuse alike, the kernel's shape aside; 0 when there is nothing to refuse
+int cf_common(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
     if (!c || c->N <= 0 || c->H <= 0 || c->W <= 0 || c->Ci <= 0 || c->Co <= 0 || c->KH <= 0 || c->KW <= 0 || c->stride <= 0 ||
-        c->pad < 0 || dilation < 1)
+        pad_h < 0 || pad_w < 0 || dilation < 1)
         return GCC_ERR_BAD_ARG;
     if (c->ldx <= 0 || c->ldy <= 0 || c->xoff < 0 || c->yoff < 0 || (c->ldx & 3) || (c->xoff & 3) || (c->ldy & 3) || (c->yoff & 3))
         return GCC_ERR_BAD_ARG;
-    if (c->KH != c->KW || (c->KH != 1 && c->KH != 3 && c->KH != 7) || (c->stride != 1 && c->stride != 2)) return GCC_ERR_UNSUPPORTED;
-    if ((dilation != 1 && dilation != 2 && dilation != 4) || c->pad != dilation * (c->KH / 2)) return GCC_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// the tile of a geometry whose kernel and paddings have passed, or the error the call returns for it
+int cf_finish(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
     if ((c->Ci != 3 && (c->Ci & 7)) || (c->Co & 7)) return GCC_ERR_UNSUPPORTED;
     if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
-    const int span = dilation * (c->KH - 1) + 1;
-    if (c->H + 2 * c->pad < span || c->W + 2 * c->pad < span) return GCC_ERR_BAD_ARG;
-    const long long Ho = (c->H + 2 * c->pad - span) / c->stride + 1, Wo = (c->W + 2 * c->pad - span) / c->stride + 1;
+    const int span_h = dilation * (c->KH - 1) + 1, span_w = dilation * (c->KW - 1) + 1;
+    if (c->H + 2 * pad_h < span_h || c->W + 2 * pad_w < span_w) return GCC_ERR_BAD_ARG;
+    const long long Ho = (c->H + 2 * pad_h - span_h) / c->stride + 1, Wo = (c->W + 2 * pad_w - span_w) / c->stride + 1;
     const long long M = (long long)c->N * Ho * Wo, Min = (long long)c->N * c->H * c->W;
     if (M >= (1ll << 31) - 256 || Min >= (1ll << 31) || (long long)c->KH * c->KW * cf_cip(c->Ci) >= (1ll << 30))
         return GCC_ERR_UNSUPPORTED;
-    if (c->Co <= 32) return 2;
-    const long long big = ((M + 127) / 128) * ((c->Co + 127) / 128);
-    return (c->Co >= 128 && big >= 256) ? 0 : 1;           // 128 x 128 tiles once they fill the chip, else 64 x 64
+    return cf_tile(M, c->Co);
 }
 
-}  // namespace
-
-extern "C" int gcc_conv_eval_f32_kp(int Ci, int KH, int KW) {
-    if (Ci <= 0 || KH <= 0 || KW <= 0 || (long long)KH * KW * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
-    return cf_kp(Ci, KH, KW);
+// gcc_conv_eval_f32: square 1 / 3 / 7 kernels with "same" padding, c->pad for both directions
+int cf_route(const gcc_conv_t* c, int dilation) {
+    const int bad = cf_common(c, c ? c->pad : 0, c ? c->pad : 0, dilation);
+    if (bad) return bad;
+    if (c->KH != c->KW || (c->KH != 1 && c->KH != 3 && c->KH != 7) || (c->stride != 1 && c->stride != 2)) return GCC_ERR_UNSUPPORTED;
+    if ((dilation != 1 && dilation != 2 && dilation != 4) || c->pad != dilation * (c->KH / 2)) return GCC_ERR_UNSUPPORTED;
+    return cf_finish(c, c->pad, c->pad, dilation);
 }
 
-extern "C" int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation) { return cf_route(c, dilation); }
+// gcc_conv_eval_f32_ex: KH and KW each of 1 / 3 / 5 / 7, each padding from 0 to "same"; c->pad must be 0
+int cf_route_ex(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
+    const int bad = cf_common(c, pad_h, pad_w, dilation);
+    if (bad) return bad;
+    if (c->pad != 0) return GCC_ERR_BAD_ARG;               // the paddings are arguments: a descriptor that carries one is a mistake
+    auto k_ok = [](int k) { return k == 1 || k == 3 || k == 5 || k == 7; };
+    if (!k_ok(c->KH) || !k_ok(c->KW) || (c->stride != 1 && c->stride != 2)) return GCC_ERR_UNSUPPORTED;
+    if ((dilation != 1 && dilation != 2 && dilation != 4) || pad_h > dilation * (c->KH / 2) || pad_w > dilation * (c->KW / 2))
+        return GCC_ERR_UNSUPPORTED;
+    return cf_finish(c, pad_h, pad_w, dilation);
+}
 
-extern "C" int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const float* w, float* y, const gcc_eval_f32_epilogue_t* ep,
-                                 gcc_stream_t stream) {
-    GCC_ENTER();
-    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
-    if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
-    const int route = cf_route(c, ep->dilation);
-    if (route < 0) return route;
+// the one launch of both entries; route: the tile, from cf_route / cf_route_ex
+int cf_launch(const gcc_conv_t* c, int route, int pad_h, int pad_w, const float* x, const float* w, float* y,
+              const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream) {
     if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)ep->residual)) & 15) return GCC_ERR_BAD_ARG;
     if (ep->residual && (ep->ld_residual <= 0 || ep->residual_off < 0 || (ep->ld_residual & 3) || (ep->residual_off & 3) ||
                          ep->ld_residual < ep->residual_off + c->Co))
         return GCC_ERR_BAD_ARG;
     ConvF32Args a;
-    const int span = ep->dilation * (c->KH - 1) + 1;
+    const int span_h = ep->dilation * (c->KH - 1) + 1, span_w = ep->dilation * (c->KW - 1) + 1;
     a.x = x; a.w = w; a.y = y; a.scale = ep->scale; a.shift = ep->shift; a.res = ep->residual;
     a.H = c->H; a.W = c->W;
-    a.Ho = (c->H + 2 * c->pad - span) / c->stride + 1;
-    a.Wo = (c->W + 2 * c->pad - span) / c->stride + 1;
+    a.Ho = (c->H + 2 * pad_h - span_h) / c->stride + 1;
+    a.Wo = (c->W + 2 * pad_w - span_w) / c->stride + 1;
     a.M = c->N * a.Ho * a.Wo;
-    a.Ci = c->Ci; a.Cip = cf_cip(c->Ci); a.Co = c->Co; a.KW = c->KW; a.stride = c->stride; a.pad = c->pad; a.dil = ep->dilation;
+    a.Ci = c->Ci; a.Cip = cf_cip(c->Ci); a.Co = c->Co; a.KW = c->KW; a.stride = c->stride; a.pad_h = pad_h; a.pad_w = pad_w;
+    a.dil = ep->dilation;
     a.ldx = c->ldx; a.xoff = c->xoff; a.ldy = c->ldy; a.yoff = c->yoff;
     a.ldr = ep->residual ? ep->ld_residual : 0; a.roff = ep->residual ? ep->residual_off : 0;
     a.Kreal = c->KH * c->KW * a.Cip; a.Kp = cf_kp(c->Ci, c->KH, c->KW);
@@ -236,6 +254,39 @@ extern "C" int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const floa
         hipLaunchKernelGGL((conv_f32_kernel<1, 1, 4, 1>), dim3(cdiv(a.M, 128), 1), dim3(CF_THREADS), 0, st, a);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
+}
+
+}  // namespace
+
+extern "C" int gcc_conv_eval_f32_kp(int Ci, int KH, int KW) {
+    if (Ci <= 0 || KH <= 0 || KW <= 0 || (long long)KH * KW * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
+    return cf_kp(Ci, KH, KW);
+}
+
+extern "C" int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation) { return cf_route(c, dilation); }
+
+extern "C" int gcc_conv_eval_f32_ex_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
+    return cf_route_ex(c, pad_h, pad_w, dilation);
+}
+
+extern "C" int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const float* w, float* y, const gcc_eval_f32_epilogue_t* ep,
+                                 gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
+    const int route = cf_route(c, ep->dilation);
+    if (route < 0) return route;
+    return cf_launch(c, route, c->pad, c->pad, x, w, y, ep, stream);
+}
+
+extern "C" int gcc_conv_eval_f32_ex(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
+                                    const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
+    const int route = cf_route_ex(c, pad_h, pad_w, ep->dilation);
+    if (route < 0) return route;
+    return cf_launch(c, route, pad_h, pad_w, x, w, y, ep, stream);
 }
 
 extern "C" int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,

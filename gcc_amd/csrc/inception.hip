@@ -7,7 +7,10 @@
 //   gcc_border_copy      an NHWC bf16 channel window copied into the middle of a map with a zero border of (ph, pw) pixels, border
 //                        included: a (1, 7) / (7, 1) / (1, 3) / (3, 1) convolution with its own padding is then a padding-0 call
 //   gcc_global_avgpool   the mean over the pixels of an NHWC bf16 channel window in fp32
-// One thread per 16-byte chunk (8 channels) of the DESTINATION: consecutive threads write consecutive chunks of a pixel, then the
+// gcc_fid_resize_f32 / gcc_pool3x3_f32 / gcc_global_avgpool_f32 are the same kernels on NHWC fp32 maps (the network at the
+// reference's own precision, around gcc_conv_eval_f32_ex): the same arithmetic in the same order without the bf16 roundings, a
+// 16-byte chunk holding 4 channels.  Rectangular padding is the fp32 convolution's own index arithmetic: no fp32 border copy.
+// One thread per 16-byte chunk (8 bf16 or 4 fp32 channels) of the DESTINATION: consecutive threads write consecutive chunks of a pixel, then the
 // next pixel.  Every thread owns its outputs: no atomics, no inter-workgroup communication, no grid-wide state.
 #include <math.h>
 #include "common.hpp"
@@ -20,12 +23,31 @@ inline unsigned in_blocks(size_t items, size_t cap = 1u << 20) {
     const size_t b = (items + IN_THREADS - 1) / IN_THREADS;
     return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
-// an NHWC bf16 channel window of C channels at `off` inside pixels of `ld` elements, 16-byte chunks throughout
-inline bool in_window_ok(const void* p, int ld, int off, int C) {
-    return p && ld > 0 && off >= 0 && !(ld & 7) && !(off & 7) && ld >= off + C && !(((uintptr_t)p) & 15);
+// an NHWC channel window of C channels at `off` inside pixels of `ld` elements, 16-byte chunks (ch elements) throughout
+inline bool in_window_ok(const void* p, int ld, int off, int C, int ch = 8) {
+    return p && ld > 0 && off >= 0 && !(ld & (ch - 1)) && !(off & (ch - 1)) && ld >= off + C && !(((uintptr_t)p) & 15);
 }
 
-// torch's area_pixel_compute_source_index (align_corners = False, not cubic): index and the weight of the upper neighbour
+// a map's element type: the channels of a 16-byte chunk, and a chunk as floats and back (bf16: one rounding on the way back)
+template <typename T> struct Chunk;
+template <> struct Chunk<bf16_t> {
+    static constexpr int CH = 8;
+    static __device__ __forceinline__ void load(const bf16_t* p, float* f) { unpack8(*(const i32x4*)p, f); }
+    static __device__ __forceinline__ void store(bf16_t* p, const float* f) { *(i32x4*)p = pack8(f); }
+};
+template <> struct Chunk<float> {
+    static constexpr int CH = 4;
+    static __device__ __forceinline__ void load(const float* p, float* f) {
+        const f32x4 v = *(const f32x4*)p;
+#pragma unroll
+        for (int j = 0; j < 4; j++) f[j] = v[j];
+    }
+    static __device__ __forceinline__ void store(float* p, const float* f) { *(f32x4*)p = f32x4{f[0], f[1], f[2], f[3]}; }
+};
+
+// torch's area_pixel_compute_source_index (align_corners = False, not cubic): index and the weight of the upper neighbour.  The
+// product and the subtraction contract into one fused multiply-add (the intrinsics are plain operators to the compiler), which is
+// what torch's own fp32 builds compute: tests/test_inception_f32_kernels_gpu.py holds both to the same fp32 taps.
 __device__ __forceinline__ void resize_tap(int d, float scale, int in, int& i0, int& i1, float& l1) {
     float s = __fsub_rn(__fmul_rn(scale, (float)d + 0.5f), 0.5f);
     s = s < 0.f ? 0.f : s;
@@ -35,8 +57,10 @@ __device__ __forceinline__ void resize_tap(int d, float scale, int in, int& i0, 
     l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
 }
 
-__global__ __launch_bounds__(IN_THREADS) void fid_resize_kernel(const float* __restrict__ x, int H, int W, bf16_t* __restrict__ y,
+template <typename T>
+__global__ __launch_bounds__(IN_THREADS) void fid_resize_kernel(const float* __restrict__ x, int H, int W, T* __restrict__ y,
                                                                  int ld, int off, int Ho, int Wo, float sh, float sw, size_t total) {
+    constexpr int CH = Chunk<T>::CH;
     const size_t plane = (size_t)H * W, oplane = (size_t)Ho * Wo;
     for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
         const size_t n = i / oplane, r = i - n * oplane;
@@ -46,7 +70,7 @@ __global__ __launch_bounds__(IN_THREADS) void fid_resize_kernel(const float* __r
         resize_tap(oy, sh, H, y0, y1, ly);
         resize_tap(ox, sw, W, x0, x1, lx);
         const float ky = 1.f - ly, kx = 1.f - lx;
-        float f[8];
+        float f[CH];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float* p = x + (n * 3 + c) * plane;
@@ -56,16 +80,17 @@ __global__ __launch_bounds__(IN_THREADS) void fid_resize_kernel(const float* __r
             f[c] = 2.f * v - 1.f;
         }
 #pragma unroll
-        for (int c = 3; c < 8; c++) f[c] = 0.f;
-        *(i32x4*)(y + i * ld + off) = pack8(f);
+        for (int c = 3; c < CH; c++) f[c] = 0.f;
+        Chunk<T>::store(y + i * ld + off, f);
     }
 }
 
 // MODE: GCC_POOL3_MAX_S2 / GCC_POOL3_MAX_S1P1 / GCC_POOL3_AVG_S1P1.  Taps are visited row by row, left to right (torch's order:
 // of equal maxima the first met stays, a NaN wins); the average sums in fp32 in that order and divides by the taps inside the map.
-template <int MODE>
-__global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const bf16_t* __restrict__ x, int ldx, int xoff, bf16_t* __restrict__ y,
+template <int MODE, typename T>
+__global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const T* __restrict__ x, int ldx, int xoff, T* __restrict__ y,
                                                               int ldy, int yoff, int H, int W, int Ho, int Wo, int chunks, size_t total) {
+    constexpr int CH = Chunk<T>::CH;
     constexpr int S = MODE == GCC_POOL3_MAX_S2 ? 2 : 1, P = MODE == GCC_POOL3_MAX_S2 ? 0 : 1;
     for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
         const size_t dp = i / chunks;
@@ -74,9 +99,9 @@ __global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const bf16_t* __res
         const int ox = (int)(t % Wo); t /= Wo;
         const int oy = (int)(t % Ho); t /= Ho;
         const size_t n = t;
-        float acc[8];
+        float acc[CH];
 #pragma unroll
-        for (int j = 0; j < 8; j++) acc[j] = MODE == GCC_POOL3_AVG_S1P1 ? 0.f : -INFINITY;
+        for (int j = 0; j < CH; j++) acc[j] = MODE == GCC_POOL3_AVG_S1P1 ? 0.f : -INFINITY;
         int count = 0;
 #pragma unroll
         for (int ky = 0; ky < 3; ky++) {
@@ -86,11 +111,11 @@ __global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const bf16_t* __res
             for (int kx = 0; kx < 3; kx++) {
                 const int ix = ox * S - P + kx;
                 if ((unsigned)ix >= (unsigned)W) continue;
-                float f[8];
-                unpack8(*(const i32x4*)(x + ((n * H + iy) * W + ix) * ldx + xoff + ch * 8), f);
+                float f[CH];
+                Chunk<T>::load(x + ((n * H + iy) * W + ix) * ldx + xoff + ch * CH, f);
                 count++;
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
+                for (int j = 0; j < CH; j++) {
                     if (MODE == GCC_POOL3_AVG_S1P1) acc[j] += f[j];
                     else if (f[j] > acc[j] || f[j] != f[j]) acc[j] = f[j];
                 }
@@ -99,9 +124,9 @@ __global__ __launch_bounds__(IN_THREADS) void pool3x3_kernel(const bf16_t* __res
         if (MODE == GCC_POOL3_AVG_S1P1) {
             const float cnt = (float)count;       // >= 1: the centre tap is always inside
 #pragma unroll
-            for (int j = 0; j < 8; j++) acc[j] = acc[j] / cnt;
+            for (int j = 0; j < CH; j++) acc[j] = acc[j] / cnt;
         }
-        *(i32x4*)(y + dp * ldy + yoff + ch * 8) = pack8(acc);
+        Chunk<T>::store(y + dp * ldy + yoff + ch * CH, acc);
     }
 }
 
@@ -125,90 +150,133 @@ __global__ __launch_bounds__(IN_THREADS) void border_copy_kernel(const bf16_t* _
 
 // out[n][c] = (sum over the pixels of x[n][.][c]) / pixels: eight fp32 partial sums (pixel p goes to partial p mod 8), added as
 // ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) -- the order is fixed by the shape alone, and a sum of 64 terms takes 10 roundings
-__global__ __launch_bounds__(IN_THREADS) void global_avgpool_kernel(const bf16_t* __restrict__ x, int ld, int off, int pixels, int C,
+template <typename T>
+__global__ __launch_bounds__(IN_THREADS) void global_avgpool_kernel(const T* __restrict__ x, int ld, int off, int pixels, int C,
                                                                      int chunks, float* __restrict__ out, size_t total) {
+    constexpr int CH = Chunk<T>::CH;
     for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
         const size_t n = i / chunks;
         const int ch = (int)(i - n * chunks);
-        const bf16_t* p = x + n * pixels * ld + off + ch * 8;
-        float part[8][8];
+        const T* p = x + n * pixels * ld + off + ch * CH;
+        float part[8][CH];
 #pragma unroll
         for (int a = 0; a < 8; a++)
 #pragma unroll
-            for (int j = 0; j < 8; j++) part[a][j] = 0.f;
+            for (int j = 0; j < CH; j++) part[a][j] = 0.f;
         int q = 0;
         for (; q + 8 <= pixels; q += 8) {
 #pragma unroll
             for (int a = 0; a < 8; a++) {
-                float f[8];
-                unpack8(*(const i32x4*)(p + (size_t)(q + a) * ld), f);
+                float f[CH];
+                Chunk<T>::load(p + (size_t)(q + a) * ld, f);
 #pragma unroll
-                for (int j = 0; j < 8; j++) part[a][j] += f[j];
+                for (int j = 0; j < CH; j++) part[a][j] += f[j];
             }
         }
 #pragma unroll
         for (int a = 0; a < 8; a++) {
             if (q + a < pixels) {
-                float f[8];
-                unpack8(*(const i32x4*)(p + (size_t)(q + a) * ld), f);
+                float f[CH];
+                Chunk<T>::load(p + (size_t)(q + a) * ld, f);
 #pragma unroll
-                for (int j = 0; j < 8; j++) part[a][j] += f[j];
+                for (int j = 0; j < CH; j++) part[a][j] += f[j];
             }
         }
         const float cnt = (float)pixels;
-        float o[8];
+        float o[CH];
 #pragma unroll
-        for (int j = 0; j < 8; j++)
+        for (int j = 0; j < CH; j++)
             o[j] = (((part[0][j] + part[1][j]) + (part[2][j] + part[3][j])) + ((part[4][j] + part[5][j]) + (part[6][j] + part[7][j]))) / cnt;
-        float* op = out + n * C + ch * 8;
-        *(f32x4*)op = f32x4{o[0], o[1], o[2], o[3]};
-        *(f32x4*)(op + 4) = f32x4{o[4], o[5], o[6], o[7]};
+        float* op = out + n * C + ch * CH;
+#pragma unroll
+        for (int j = 0; j < CH; j += 4) *(f32x4*)(op + j) = f32x4{o[j], o[j + 1], o[j + 2], o[j + 3]};
     }
 }
 
 }  // namespace
 
-extern "C" int gcc_fid_resize(const float* x, int N, int H, int W, void* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream) {
+namespace {
+
+template <typename T>
+int fid_resize_impl(const float* x, int N, int H, int W, T* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream) {
     GCC_ENTER();
     if (!x || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return GCC_ERR_BAD_ARG;
-    if (!in_window_ok(y, ld, off, 8) || (((uintptr_t)x) & 3)) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(y, ld, off, Chunk<T>::CH, Chunk<T>::CH) || (((uintptr_t)x) & 3)) return GCC_ERR_BAD_ARG;
     const size_t total = (size_t)N * Ho * Wo;
     if ((size_t)N * 3 * H * W >= (size_t)1 << 40 || total >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
     // torch's area_pixel_compute_scale<float>: the ratio of the sizes in fp32
     const float sh = (float)H / (float)Ho, sw = (float)W / (float)Wo;
-    hipLaunchKernelGGL(fid_resize_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, x, H, W, (bf16_t*)y, ld,
-                       off, Ho, Wo, sh, sw, total);
+    hipLaunchKernelGGL(fid_resize_kernel<T>, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, x, H, W, y, ld, off,
+                       Ho, Wo, sh, sw, total);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
 
-extern "C" int gcc_pool3x3(int mode, const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int N, int H, int W, int C,
-                           gcc_stream_t stream) {
+template <typename T>
+int pool3x3_impl(int mode, const T* xp, int ldx, int xoff, T* yp, int ldy, int yoff, int N, int H, int W, int C,
+                 gcc_stream_t stream) {
+    constexpr int CH = Chunk<T>::CH;
     GCC_ENTER();
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return GCC_ERR_BAD_ARG;
     if (mode != GCC_POOL3_MAX_S2 && mode != GCC_POOL3_MAX_S1P1 && mode != GCC_POOL3_AVG_S1P1) return GCC_ERR_BAD_ARG;
-    if (!in_window_ok(x, ldx, xoff, ceil8(C)) || !in_window_ok(y, ldy, yoff, ceil8(C))) return GCC_ERR_BAD_ARG;
-    if (C & 7) return GCC_ERR_UNSUPPORTED;
+    const int Cc = (C + CH - 1) / CH * CH;
+    if (!in_window_ok(xp, ldx, xoff, Cc, CH) || !in_window_ok(yp, ldy, yoff, Cc, CH)) return GCC_ERR_BAD_ARG;
+    if (C & (CH - 1)) return GCC_ERR_UNSUPPORTED;
     int Ho = H, Wo = W;
     if (mode == GCC_POOL3_MAX_S2) {
         if (H < 3 || W < 3) return GCC_ERR_UNSUPPORTED;            // no output pixel
         Ho = (H - 3) / 2 + 1; Wo = (W - 3) / 2 + 1;
     }
-    const int chunks = C / 8;
+    const int chunks = C / CH;
     const size_t total = (size_t)N * Ho * Wo * chunks;
     if ((size_t)N * H * W * ldx >= (size_t)1 << 40 || (size_t)N * Ho * Wo * ldy >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid(in_blocks(total)), block(IN_THREADS);
-    const bf16_t* xp = (const bf16_t*)x;
-    bf16_t* yp = (bf16_t*)y;
     if (mode == GCC_POOL3_MAX_S2)
-        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_MAX_S2>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+        hipLaunchKernelGGL((pool3x3_kernel<GCC_POOL3_MAX_S2, T>), grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
     else if (mode == GCC_POOL3_MAX_S1P1)
-        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_MAX_S1P1>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+        hipLaunchKernelGGL((pool3x3_kernel<GCC_POOL3_MAX_S1P1, T>), grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
     else
-        hipLaunchKernelGGL(pool3x3_kernel<GCC_POOL3_AVG_S1P1>, grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
+        hipLaunchKernelGGL((pool3x3_kernel<GCC_POOL3_AVG_S1P1, T>), grid, block, 0, st, xp, ldx, xoff, yp, ldy, yoff, H, W, Ho, Wo, chunks, total);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
+}
+
+template <typename T>
+int global_avgpool_impl(const T* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream) {
+    constexpr int CH = Chunk<T>::CH;
+    GCC_ENTER();
+    if (!out || N <= 0 || h <= 0 || w <= 0 || C <= 0) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(x, ld, off, (C + CH - 1) / CH * CH, CH) || (((uintptr_t)out) & 15)) return GCC_ERR_BAD_ARG;
+    if (C & (CH - 1)) return GCC_ERR_UNSUPPORTED;
+    if ((size_t)h * w >= (size_t)1 << 24 || (size_t)N * h * w * ld >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    const int chunks = C / CH;
+    const size_t total = (size_t)N * chunks;
+    hipLaunchKernelGGL(global_avgpool_kernel<T>, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, x, ld, off, h * w,
+                       C, chunks, out, total);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+}  // namespace
+
+extern "C" int gcc_fid_resize(const float* x, int N, int H, int W, void* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream) {
+    return fid_resize_impl(x, N, H, W, (bf16_t*)y, ld, off, Ho, Wo, stream);
+}
+
+extern "C" int gcc_fid_resize_f32(const float* x, int N, int H, int W, float* y, int ld, int off, int Ho, int Wo,
+                                  gcc_stream_t stream) {
+    return fid_resize_impl(x, N, H, W, y, ld, off, Ho, Wo, stream);
+}
+
+extern "C" int gcc_pool3x3(int mode, const void* x, int ldx, int xoff, void* y, int ldy, int yoff, int N, int H, int W, int C,
+                           gcc_stream_t stream) {
+    return pool3x3_impl(mode, (const bf16_t*)x, ldx, xoff, (bf16_t*)y, ldy, yoff, N, H, W, C, stream);
+}
+
+extern "C" int gcc_pool3x3_f32(int mode, const float* x, int ldx, int xoff, float* y, int ldy, int yoff, int N, int H, int W, int C,
+                               gcc_stream_t stream) {
+    return pool3x3_impl(mode, x, ldx, xoff, y, ldy, yoff, N, H, W, C, stream);
 }
 
 extern "C" int gcc_border_copy(const void* src, int lds, int soff, void* dst, int ldd, int doff, int N, int H, int W, int C, int ph,
@@ -233,15 +301,9 @@ extern "C" int gcc_border_copy(const void* src, int lds, int soff, void* dst, in
 }
 
 extern "C" int gcc_global_avgpool(const void* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream) {
-    GCC_ENTER();
-    if (!out || N <= 0 || h <= 0 || w <= 0 || C <= 0) return GCC_ERR_BAD_ARG;
-    if (!in_window_ok(x, ld, off, ceil8(C)) || (((uintptr_t)out) & 15)) return GCC_ERR_BAD_ARG;
-    if (C & 7) return GCC_ERR_UNSUPPORTED;
-    if ((size_t)h * w >= (size_t)1 << 24 || (size_t)N * h * w * ld >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
-    const int chunks = C / 8;
-    const size_t total = (size_t)N * chunks;
-    hipLaunchKernelGGL(global_avgpool_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, (hipStream_t)stream, (const bf16_t*)x, ld,
-                       off, h * w, C, chunks, out, total);
-    GCC_CHECK_LAUNCH();
-    return GCC_OK;
+    return global_avgpool_impl((const bf16_t*)x, ld, off, N, h, w, C, out, stream);
+}
+
+extern "C" int gcc_global_avgpool_f32(const float* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream) {
+    return global_avgpool_impl(x, ld, off, N, h, w, C, out, stream);
 }

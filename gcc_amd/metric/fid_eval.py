@@ -215,25 +215,34 @@ def fid_evaluator(inception, logger=None, batch_size=50):
     return evaluate
 
 
+PRECISION_ENV = 'GCC_FID_PRECISION'
+
+
 def _native_inception(path):
     """(InceptionFidEngine on the host, None) when `path` is the reference's own weight file -- the plain state_dict of
-    fid_inception_v3() --, (None, why) when it is one this package does not run, (None, None) for any other file"""
-    from .inception_fid import InceptionFidEngine, is_fid_inception_state_dict
+    fid_inception_v3() --, (None, why) when it is one this package does not run, (None, None) for any other file.  The environment
+    variable GCC_FID_PRECISION ('bf16', the default, or 'fp32': the reference's own arithmetic on the f32-input matrix
+    instructions) chooses the engine's precision; any other value raises GccError."""
+    from .inception_fid import PRECISIONS, InceptionFidEngine, is_fid_inception_state_dict
     try:
         sd = torch.load(path, map_location='cpu', weights_only=True)
     except Exception:
         return None, None
     if not is_fid_inception_state_dict(sd):
         return None, None
+    precision = os.environ.get(PRECISION_ENV) or 'bf16'
+    if precision not in PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (PRECISION_ENV, precision, ', '.join(PRECISIONS)))
     try:
-        return InceptionFidEngine(sd), None
+        return InceptionFidEngine(sd, precision=precision), None
     except GccError as e:
         return None, '%s %s holds an Inception state_dict this package does not run: %s' % (ENV, path, e)
 
 
 def load_inception():
     """(network, None) from the file GCC_FID_INCEPTION names -- a TorchScript archive of InceptionV3([3]), or the reference's own
-    pt_inception weight file (a plain state_dict: InceptionFidEngine runs it natively) --, else (None, the condition that failed)"""
+    pt_inception weight file (a plain state_dict: InceptionFidEngine runs it natively, at the precision GCC_FID_PRECISION names)
+    --, else (None, the condition that failed).  A TorchScript archive runs as it was exported and ignores GCC_FID_PRECISION."""
     path = os.environ.get(ENV)
     if not path:
         return None, '%s is not set (the path of a TorchScript archive of the Inception network)' % ENV
@@ -248,6 +257,12 @@ def load_inception():
             return engine, refusal
         return None, 'torch.jit.load could not read %s %s as a TorchScript archive (%s: %s); a plain state_dict needs the ' \
                      'network\'s code: export InceptionV3([3]) with torch.jit once' % (ENV, path, type(e).__name__, first)
+
+
+def network_label(inception):
+    """' (native, bf16|fp32)' for a native engine, '' for a TorchScript archive: the log lines' word on which network scores"""
+    precision = getattr(inception, 'precision', None)
+    return ' (native, %s)' % precision if precision else ''
 
 
 def builtin_inception(opt):

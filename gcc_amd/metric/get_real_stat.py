@@ -8,6 +8,8 @@ dataset's real images, the real_stat*.npz a FID evaluation compares against.
 
 The reference's arguments and defaults; ``--dataset_mode unaligned`` is accepted as well (domain B for AtoB, A for BtoA), so
 that CycleGAN roots get theirs.  The network is the file GCC_FID_INCEPTION names: the reference's weight file or a TorchScript archive (gcc_amd.metric.fid_eval).
+The weight file runs natively at the precision GCC_FID_PRECISION names (bf16, the default, or fp32: the reference's own); the tool
+prints which one wrote the file.  Write the real statistics through the same route as the scores compared against them.
 Images are read through gcc_amd.data, keyed by path (a repeated path counts once), turned into the network's input by
 gcc_fid_input -- util.tensor2imgs' byte of the loader's [-1, 1] tensor over 255, exactly: 63 of the 256 byte values come back
 one lower from that round trip, and the reference's statistics are statistics of those bytes -- and go through the network at
@@ -88,6 +90,8 @@ def main(argv=None, inception=None):
             raise GccError('get_real_stat: %s' % why)
     mu, sigma = real_statistics(opt, inception, device)
     np.savez(opt.output_path, mu=mu.cpu().numpy(), sigma=sigma.cpu().numpy())
+    from .fid_eval import network_label
+    print('get_real_stat: %s written with the Inception network%s' % (opt.output_path, network_label(inception) or ' (TorchScript)'))
     return opt.output_path
 
 

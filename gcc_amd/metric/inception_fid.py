@@ -11,6 +11,15 @@ gcc_conv_t has one padding for both directions, so the (1, 7) / (7, 1) / (1, 3) 
 input inside its own zero border) and a padding-0 call with KH != KW.  Mixed_7c's pooling branch is a MAX pool: the FID network's
 known quirk (metric/inception.py:301-304), kept.
 
+precision='fp32' is the same network at the reference's own precision: NHWC fp32 activations and fp32 weights through
+gcc_conv_eval_f32_ex (f32-input MFMA), whose two paddings are arguments, so a rectangular kernel is ONE launch and the program has
+no 'border' step:
+
+    x NCHW fp32 -> gcc_fid_resize_f32 (3 channels in an ld of 4) -> one gcc_conv_eval_f32_ex per BasicConv2d, gcc_pool3x3_f32
+        -> gcc_global_avgpool_f32
+
+There is no split-K on that route: an image's features do not depend on the batch it is in, bit for bit.
+
 Every width is read from the shapes: the only constraints are that concatenations match and that widths are multiples of 8, so a
 thin seeded network runs through the same code as the real one.  Construction parses the state_dict on the host (no device, no
 library); .to(device) packs the weights and folds the BatchNorms once -- the weights of an evaluator never change."""
@@ -26,6 +35,7 @@ BN_EPS = 1e-3                                        # BasicConv2d's BatchNorm2d
 UNUSED_KEYS = ('fc.weight', 'fc.bias')
 MAX_S2, MAX_S1P1, AVG_S1P1 = 0, 1, 2                 # _lib.POOL3_*
 WHAT = 'FID Inception state_dict'
+PRECISIONS = ('bf16', 'fp32')
 
 
 def _c(name, k=1, stride=1, pad=0):
@@ -155,11 +165,17 @@ def _out(size, k, stride, pad):
 class InceptionFidEngine(SlabProgramEngine):
     """inception(x)[0] for fid_eval.ImageStatistics: x NCHW fp32 [N, 3, H, W] in [0, 1] on the device, any H, W -> [features],
     features fp32 [N, d, 1, 1] (d = 2048 for the real network), InceptionV3([3]).forward's list.  Activations are NHWC bf16 with
-    one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic.  The
+    one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic.
+    precision='fp32': activations, weights and every sum are fp32 (the reference's own arithmetic), one launch per convolution.  The
     engine's scaffold -- .to(), the slab and its programs, the route check -- is metric/_native.py's."""
     BN_EPS = BN_EPS
 
-    def __init__(self, state_dict, resize=299):
+    def __init__(self, state_dict, resize=299, precision='bf16'):
+        if precision not in PRECISIONS:
+            raise GccError('InceptionFidEngine: precision %r; expected one of %s' % (precision, ', '.join(PRECISIONS)))
+        self.precision = precision
+        if precision == 'fp32':
+            self._slab_dtype = torch.float32
         self.arch = parse_fid_inception(state_dict)
         self.d = self.arch.d
         self.resize = int(resize)
@@ -168,21 +184,28 @@ class InceptionFidEngine(SlabProgramEngine):
         super().__init__(state_dict, self.arch.convs)
         self._plan(1)                                  # a resize too small for the network is refused here, on the host
 
+    def _pack(self, c, master):
+        return ops.pack_weights_f32(master) if self.precision == 'fp32' else super()._pack(c, master)
+
     # ---- the launch program ---------------------------------------------------------------------------------------------
     def _plan(self, N):
-        """the launches of a batch of N as tuples over symbolic activations of the slab: behind the 8-channel resized input, four
-        regions -- a block's input and output, which swap from layer to layer, and two temporaries the branches alternate between.
-        The input's own H and W appear in no launch but gcc_fid_resize, so a program depends on N alone."""
+        """the launches of a batch of N as tuples over symbolic activations of the slab: behind the 8-channel resized input (4 in
+        fp32), four regions -- a block's input and output, which swap from layer to layer, and two temporaries the branches
+        alternate between.  The input's own H and W appear in no launch but gcc_fid_resize, so a program depends on N alone.
+        bf16: ('conv', conv, source, destination), ('pool', mode, source, destination), ('border', source, destination, ph, pw)
+        in front of a rectangular kernel.  fp32: no 'border' -- a 'conv' step's (ph, pw) are its conv's own .pad."""
         steps, sizes, where = [], [], ['the input']
         R = self.resize
+        f32 = self.precision == 'fp32'
+        grid = 4 if f32 else 8                         # the channels of a 16-byte chunk: every slice starts and ends on one
         reg = SimpleNamespace(x=0, y=1, t1=2, t2=3)
 
         def act(Cc, h, w, region, ld=None, off=0):
             if h <= 0 or w <= 0:
                 raise GccError('InceptionFidEngine: resize = %d leaves no pixel at %s' % (R, where[0]))
             a = Act(Cc, h, w, region, ld=ld, off=off)
-            if a.off % 8 or a.ld % 8:
-                raise GccError('InceptionFidEngine: a channel slice at %d of %d is off the 8-channel grid' % (a.off, a.ld))
+            if a.off % grid or a.ld % grid:
+                raise GccError('InceptionFidEngine: a channel slice at %d of %d is off the %d-channel grid' % (a.off, a.ld, grid))
             if off == 0:
                 sizes.append(N * h * w * a.ld)
             return a
@@ -196,7 +219,7 @@ class InceptionFidEngine(SlabProgramEngine):
             kernel's padding is a zero border first (in the temporary `cur` is not in: `cur` may have other readers)."""
             where[0] = c.key
             ph, pw = c.pad
-            if c.k[0] != c.k[1]:
+            if c.k[0] != c.k[1] and not f32:
                 b = act(cur.C, cur.h + 2 * ph, cur.w + 2 * pw, free(cur))
                 steps.append(('border', cur, b, ph, pw))
                 cur, ph, pw = b, 0, 0
@@ -212,7 +235,7 @@ class InceptionFidEngine(SlabProgramEngine):
             steps.append(('pool', mode, cur, dst))
             return dst
 
-        x = Act(3, R, R, -1, ld=8)
+        x = Act(3, R, R, -1, ld=grid)
         for item in self.arch.net:
             if item[0] == 'conv':
                 c = item[1]
@@ -240,19 +263,23 @@ class InceptionFidEngine(SlabProgramEngine):
                     for c in b.chain:
                         cur = apply(c, cur)
                     for c in b.tails:
-                        if off % 8:
+                        if off % grid:
                             raise GccError('InceptionFidEngine: %s would be written at channel %d of %s' % (c.key, off, name))
                         apply(c, cur, act(c.co, ho, wo, reg.y, width, off))
                         off += c.co
                 if off != width:
                     raise GccError('InceptionFidEngine: %s concatenates %d channels, expected %d' % (name, off, width))
             x, reg.x, reg.y = y, reg.y, reg.x
-        return SimpleNamespace(steps=steps, size_in=N * R * R * 8, size_r=max(sizes), last=x, slab=None, x_in=None,
-                               total=N * R * R * 8 + 4 * max(sizes))
+        return SimpleNamespace(steps=steps, size_in=N * R * R * grid, size_r=max(sizes), last=x, slab=None, x_in=None,
+                               total=N * R * R * grid + 4 * max(sizes))
 
     def _conv(self, st, route_only=False):
         """launch the 'conv' step st, or with route_only the library's answer for it: its launches, -1 if it declines"""
         _, c, src, dst = st
+        if self.precision == 'fp32':
+            rc = ops.conv_eval_f32_ex(src.view, c.w, c.co, c.k, c.stride, c.pad, dst.view, scale=c.scale, shift=c.shift,
+                                      act=EVAL_ACT_RELU, route_only=route_only)
+            return (1 if rc >= 0 else -1) if route_only else rc          # the route's answer is a tile: always one launch
         if c.k[0] != c.k[1]:
             return ops.conv_eval_rect(src.view, c.w, c.co, c.k, c.stride, dst.view, scale=c.scale, shift=c.shift, act=EVAL_ACT_RELU,
                                       slot='inception_eval', route_only=route_only)
@@ -261,6 +288,10 @@ class InceptionFidEngine(SlabProgramEngine):
 
     def _declined(self, st):
         c, src = st[1:3]
+        if self.precision == 'fp32':
+            return ('InceptionFidEngine: the library declines the fp32 geometry of %s (%d -> %d channels, %d x %d, stride %d, '
+                    'padding (%d, %d), on %d x %d x %d): there is no other route'
+                    % ((c.key, c.ci, c.co, c.k[0], c.k[1], c.stride) + tuple(c.pad) + tuple(src.view.shape[i] for i in (0, 2, 3))))
         return ('InceptionFidEngine: the library declines the geometry of %s (%d -> %d channels, %d x %d, stride %d, on %d x %d x '
                 '%d): there is no other route' % ((c.key, c.ci, c.co, c.k[0], c.k[1], c.stride)
                                                   + tuple(src.view.shape[i] for i in (0, 2, 3))))
@@ -270,7 +301,9 @@ class InceptionFidEngine(SlabProgramEngine):
         prog = self._bind(N)
         if count_only:
             return 2 + sum(self._conv(st, route_only=True) if st[0] == 'conv' else 1 for st in prog.steps)
-        ops.fid_resize(x, prog.x_in)
+        f32 = self.precision == 'fp32'
+        (ops.fid_resize_f32 if f32 else ops.fid_resize)(x, prog.x_in)
+        pool3x3 = ops.pool3x3_f32 if f32 else ops.pool3x3
         for st in prog.steps:
             kind = st[0]
             if kind == 'conv':
@@ -279,11 +312,11 @@ class InceptionFidEngine(SlabProgramEngine):
                 except GccError as e:
                     raise self._conv_error(st, e)
             elif kind == 'pool':
-                ops.pool3x3(st[1], st[2].view, st[3].view)
+                pool3x3(st[1], st[2].view, st[3].view)
             else:
                 ops.border_copy(st[1].view, st[2].view, st[3], st[4])
         out = torch.empty((N, self.d, 1, 1), dtype=torch.float32, device=self.device)
-        ops.global_avgpool(prog.last.view, out)
+        (ops.global_avgpool_f32 if f32 else ops.global_avgpool)(prog.last.view, out)
         return [out]
 
     def __call__(self, x):

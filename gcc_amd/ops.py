@@ -729,6 +729,27 @@ def conv_eval_f32(x, w, Co, k, stride, pad, out, dilation=1, scale=None, shift=N
     return out
 
 
+def conv_eval_f32_ex(x, w, Co, kernel, stride, pad, out, dilation=1, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, residual=None,
+                     route_only=False):
+    """conv_eval_f32 with a (kh, kw) kernel and a (ph, pw) padding of its own (gcc_conv_eval_f32_ex): each side of 1 / 3 / 5 / 7,
+    each padding from 0 to dilation (k // 2).  NHWC fp32 views, w from pack_weights_f32.  One launch, no workspace.
+    route_only: the library's answer for the geometry (>= 0: the tile it takes; < 0: declined), nothing launched."""
+    kh, kw = kernel
+    ph, pw = pad
+    xp, N, Ci, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    d = conv_desc(N, H, W, Ci, Co, kh, stride, 0, ldx, ldy)                # the descriptor's own pad stays 0: (ph, pw) are arguments
+    d.KW = kw
+    if route_only:
+        return lib().gcc_conv_eval_f32_ex_route(C.byref(d), ph, pw, dilation)
+    ep = _lib.eval_f32_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, dilation)
+    if residual is not None:
+        rp, _, _, _, _, ldr = geom_f32(residual)
+        ep.residual, ep.ld_residual = rp, ldr
+    check(lib().gcc_conv_eval_f32_ex(C.byref(d), ph, pw, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_f32_ex')
+    return out
+
+
 def nchw_to_nhwc_f32(src, dst, cfill=None):
     """src fp32 [N, C, H, W] contiguous -> the channels of the NHWC fp32 view dst (+ zero fill to cfill, a multiple of 4)"""
     N, Cc, H, W = src.shape
@@ -1012,6 +1033,41 @@ def global_avgpool(x, out=None):
     if out.dtype != torch.float32 or out.numel() != N * Cc or not out.is_contiguous():
         raise _lib.GccError('global_avgpool: out must be a contiguous fp32 tensor of %d x %d elements' % (N, Cc))
     check(lib().gcc_global_avgpool(xp, ld, 0, N, h, w, Cc, out.data_ptr(), stream()), 'gcc_global_avgpool')
+    return out
+
+
+def fid_resize_f32(x, out):
+    """gcc_fid_resize_f32: fid_resize without the bf16 rounding into an NHWC fp32 view of 3 channels in an ld of at least 4
+    (channel 3 of each pixel is written as zero)"""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise _lib.GccError('fid_resize_f32: expected a contiguous NCHW fp32 [N, 3, H, W] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+    N, _, H, W = x.shape
+    yp, Ny, Cy, Ho, Wo, ld = geom_f32(out)
+    if Ny != N or Cy != 3:
+        raise _lib.GccError('fid_resize_f32: %s into %s' % (tuple(x.shape), tuple(out.shape)))
+    check(lib().gcc_fid_resize_f32(x.data_ptr(), N, H, W, yp, ld, 0, Ho, Wo, stream()), 'gcc_fid_resize_f32')
+    return out
+
+
+def pool3x3_f32(mode, x, out):
+    """gcc_pool3x3_f32 (mode: _lib.POOL3_*) of an NHWC fp32 view into another of the same channels (a channel slice works)"""
+    xp, N, Cc, H, W, ldx = geom_f32(x)
+    yp, Ny, Cy, Ho, Wo, ldy = geom_f32(out)
+    want = ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == _lib.POOL3_MAX_S2 else (H, W)
+    if (Ny, Cy, Ho, Wo) != (N, Cc) + want:
+        raise _lib.GccError('pool3x3_f32 mode %d: %s into %s' % (mode, tuple(x.shape), tuple(out.shape)))
+    check(lib().gcc_pool3x3_f32(mode, xp, ldx, 0, yp, ldy, 0, N, H, W, Cc, stream()), 'gcc_pool3x3_f32')
+    return out
+
+
+def global_avgpool_f32(x, out=None):
+    """gcc_global_avgpool_f32: fp32 [N, C] mean over the pixels of an NHWC fp32 view"""
+    xp, N, Cc, h, w, ld = geom_f32(x)
+    if out is None:
+        out = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.numel() != N * Cc or not out.is_contiguous():
+        raise _lib.GccError('global_avgpool_f32: out must be a contiguous fp32 tensor of %d x %d elements' % (N, Cc))
+    check(lib().gcc_global_avgpool_f32(xp, ld, 0, N, h, w, Cc, out.data_ptr(), stream()), 'gcc_global_avgpool_f32')
     return out
 
 

@@ -130,13 +130,14 @@ def builtin_evaluator(opt, logger):
         return cityscapes_evaluator(segmenter, logger)
     if str(opt.dataroot).startswith('synthetic'):
         return None
-    from .metric.fid_eval import ENV, builtin_inception, fid_evaluator, wants_fid
+    from .metric.fid_eval import ENV, builtin_inception, fid_evaluator, network_label, wants_fid
     if wants_fid(opt):
         inception, why = builtin_inception(opt)
         if inception is None:
             logger.info('no FID evaluation: %s' % why)
             return None
-        logger.info('FID evaluation every %d epochs with the Inception network %s' % (opt.save_epoch_freq, os.environ[ENV]))
+        logger.info('FID evaluation every %d epochs with the Inception network %s%s'
+                    % (opt.save_epoch_freq, os.environ[ENV], network_label(inception)))
         return fid_evaluator(inception, logger)
     if opt.model != 'srgan':
         return None

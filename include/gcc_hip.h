@@ -519,6 +519,21 @@ int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const float* w, float
                       gcc_stream_t stream);
 int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation);
 int gcc_conv_eval_f32_kp(int Ci, int KH, int KW);
+/* gcc_conv_eval_f32_ex: gcc_conv_eval_f32 with the kernel's two sides and the two paddings independent -- the same kernel, weight
+ * packing (gcc_conv_eval_f32_kp), epilogue, tile shapes and order of K; what a pixel gets does not depend on its batch or tile.
+ * The FID Inception network at the reference's own precision (gcc_amd/metric/inception_fid.py, precision 'fp32'): 5 x 5, (1, 7),
+ * (7, 1), (1, 3), (3, 1) and padding-0 3 x 3 convolutions.  One launch.  Added without a GCC_HIP_ABI bump (additions only).
+ * Geometry: KH and KW each in {1, 3, 5, 7}; 0 <= pad_h <= dilation (KH / 2) and 0 <= pad_w <= dilation (KW / 2), zeros on both
+ *   sides of a direction (taps at ih = oh stride - pad_h + kh dilation, iw = ow stride - pad_w + kw dilation), so Ho = (H + 2 pad_h
+ *   - dilation (KH - 1) - 1) / stride + 1 and Wo alike; stride 1 or 2; dilation 1, 2 or 4; Ci == 3 or a multiple of 8; Co a
+ *   multiple of 8: GCC_ERR_UNSUPPORTED otherwise.  A negative padding, or a map smaller than the kernel's span: GCC_ERR_BAD_ARG.
+ * c->pad MUST BE 0: the paddings of this call are its arguments, and a descriptor that carries one of its own was filled in for
+ *   another call -- GCC_ERR_BAD_ARG, not a convolution with a padding the caller did not mean.  The plan of gcc_conv_t is not read.
+ * Layout, weights, epilogue and the other refusals: gcc_conv_eval_f32's.  Every refusal happens before anything is launched.
+ * gcc_conv_eval_f32_ex_route: the tile the call would take (0 / 1 / 2 as above) or its error for the geometry; launches nothing. */
+int gcc_conv_eval_f32_ex(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
+                         const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream);
+int gcc_conv_eval_f32_ex_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation);
 /* dst[p][off + c] = src[n][c][h][w] for c < C and 0 for C <= c < cfill: an NCHW fp32 image as the NHWC fp32 input of
  * gcc_conv_eval_f32 (ld, off, cfill multiples of 4; off + cfill <= ld; dst 16-byte aligned).  One launch. */
 int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,
@@ -929,6 +944,21 @@ int gcc_pool3x3(int mode, const void* x, int ldx, int xoff, void* y, int ldy, in
 int gcc_border_copy(const void* src, int lds, int soff, void* dst, int ldd, int doff, int N, int H, int W, int C, int ph, int pw,
                     gcc_stream_t stream);
 int gcc_global_avgpool(const void* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream);
+/* The same three kernels on NHWC FP32 maps, around gcc_conv_eval_f32_ex (the network at the reference's own precision): the same
+ * arithmetic in the same order without the bf16 roundings.  A 16-byte chunk is 4 channels: ld / offsets multiples of 4 floats,
+ * C a multiple of 4 (GCC_ERR_UNSUPPORTED otherwise); the refusals are the bf16 entries' otherwise, all before any launch.  There
+ * is no fp32 border copy: rectangular padding is gcc_conv_eval_f32_ex's own index arithmetic.
+ * gcc_fid_resize_f32: y[n][oy][ox][off + c] = 2 v - 1 for c < 3, and channel off + 3 is written as zero (the 3-in-4 input of
+ *   gcc_conv_eval_f32_ex with Ci == 3).  The source index (o + 0.5) (in / out) - 0.5 is one fused multiply-add on the fp32
+ *   ratio of the sizes, in both entries: what torch's fp32 builds compute (a float64 index differs by up to 7e-5 in v).
+ * gcc_pool3x3_f32: the maxima are the inputs' own bits (of equal maxima the first met, a NaN wins); the average is the fp32 sum
+ *   in tap order (row by row, left to right) over the taps inside the map, then one IEEE division by their count.
+ * gcc_global_avgpool_f32: pixel p goes to partial sum p mod 8, the partials are added as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 +
+ *   7)), then one IEEE division by h w. */
+int gcc_fid_resize_f32(const float* x, int N, int H, int W, float* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream);
+int gcc_pool3x3_f32(int mode, const float* x, int ldx, int xoff, float* y, int ldy, int yoff, int N, int H, int W, int C,
+                    gcc_stream_t stream);
+int gcc_global_avgpool_f32(const float* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * FID around the Inception network (metric/test_metric.py:15-45, 129-204, metric/get_real_stat.py; the network itself is the
