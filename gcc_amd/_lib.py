@@ -87,6 +87,13 @@ class eval_f32_epilogue_t(C.Structure):
                 ('residual_off', C.c_int), ('act', C.c_int), ('dilation', C.c_int)]
 
 
+class eval_f32_act_epilogue_t(C.Structure):
+    """include/gcc_hip.h gcc_eval_f32_act_epilogue_t: the epilogue of gcc_conv_eval_f32_act (PReLU by a device slope, tanh, shuffle)"""
+    _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('residual', C.c_void_p), ('ld_residual', C.c_int),
+                ('residual_off', C.c_int), ('act', C.c_int), ('shuffle', C.c_int), ('slope', C.c_void_p), ('dilation', C.c_int),
+                ('pad_', C.c_int)]
+
+
 FID_IN_BF16, FID_IN_U8, FID_IN_F32 = 0, 1, 2               # include/gcc_hip.h GCC_FID_IN_*
 POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2     # include/gcc_hip.h GCC_POOL3_*
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
@@ -230,8 +237,12 @@ PROTOTYPES = {
     'gcc_conv_eval_f32_kp': (_I, [_I, _I, _I]),
     'gcc_conv_eval_f32_ex': (_I, [C.POINTER(conv_t), _I, _I, _P, _P, _P, C.POINTER(eval_f32_epilogue_t), _P]),
     'gcc_conv_eval_f32_ex_route': (_I, [C.POINTER(conv_t), _I, _I, _I]),
+    'gcc_conv_eval_f32_act': (_I, [C.POINTER(conv_t), _I, _I, _P, _P, _P, C.POINTER(eval_f32_act_epilogue_t), _P]),
+    'gcc_conv_eval_f32_act_route': (_I, [C.POINTER(conv_t), _I, _I, _I, _I]),
+    'gcc_nhwc_f32_to_nchw_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_nchw_f32_to_nhwc_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),
+    'gcc_image_to_u8_f32': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_dw_inorm_fwd': (_I, [C.POINTER(dw_inorm_t), _P]),
     'gcc_dw_inorm_route': (_I, [C.POINTER(dw_inorm_t)]),
     'gcc_conv_bn_act': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(bn_t), C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _Z, _P]),

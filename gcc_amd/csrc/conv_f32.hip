@@ -16,6 +16,10 @@
 //   C       col = lane & 31 (a channel: 32 lanes store 128 contiguous bytes), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 // The next step's global loads are issued into registers before the current step's MFMAs and stored to the other LDS stage behind
 // them: one barrier per step.
+//
+// gcc_conv_eval_f32_act is the same kernel (EXT) with sides up to 9, PReLU (a device slope) and tanh in the epilogue, and an
+// optional PixelShuffle(2) store: SRResNet at the reference's own precision (engine.SRResNetEngine.infer, precision 'fp32').  With
+// the shuffle a 32-lane store group (32 consecutive channels of one pixel) puts 8 consecutive floats on each of the 4 sub-pixels.
 #include "common.hpp"
 
 namespace {
@@ -29,9 +33,11 @@ struct ConvF32Args {
     int M, H, W, Ho, Wo, Ci, Cip, Co, KW, stride, pad_h, pad_w, dil;
     int ldx, xoff, ldy, yoff, ldr, roff, Kreal, Kp, relu;
     FastDiv dWo, dHo, dCip, dKW;
+    const float* slope; int act, shuffle;           // EXT only (gcc_conv_eval_f32_act)
 };
 
-template <int MI, int NI, int WM, int WN>
+// EXT = false is the kernel of gcc_conv_eval_f32 / _ex as it was; EXT = true has the epilogue of gcc_conv_eval_f32_act
+template <int MI, int NI, int WM, int WN, bool EXT>
 __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
     static_assert(WM * WN == 4, "four waves");
     constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
@@ -134,6 +140,8 @@ __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
     }
 
     // epilogue: act(scale acc + shift + residual); only pixels < M and channels < Co are touched
+    float slope = 0.f;
+    if (EXT && a.act == GCC_EVAL_ACT_PRELU) slope = *a.slope;
 #pragma unroll
     for (int ni = 0; ni < NI; ni++) {
         const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
@@ -147,8 +155,22 @@ __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
                 if (m >= a.M) continue;
                 float v = fmaf(acc[mi][ni][r], sc, sh);
                 if (a.res) v += a.res[(size_t)m * a.ldr + a.roff + co];
-                if (a.relu) v = v < 0.f ? 0.f : v;
-                a.y[(size_t)m * a.ldy + a.yoff + co] = v;
+                if (!EXT) {
+                    if (a.relu) v = v < 0.f ? 0.f : v;
+                    a.y[(size_t)m * a.ldy + a.yoff + co] = v;
+                } else {
+                    if (a.act == GCC_EVAL_ACT_RELU) v = v < 0.f ? 0.f : v;
+                    else if (a.act == GCC_EVAL_ACT_PRELU) v = v >= 0.f ? v : __fmul_rn(slope, v);
+                    else if (a.act == GCC_EVAL_ACT_TANH) v = tanhf(v);
+                    if (!a.shuffle) {
+                        a.y[(size_t)m * a.ldy + a.yoff + co] = v;
+                    } else {
+                        // nn.PixelShuffle(2): channel co of pixel (n, oh, ow) is channel co >> 2 of pixel (2 oh + bit 1, 2 ow + bit 0)
+                        const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;           // q = n Ho + oh
+                        const size_t p = ((size_t)q * 2 + ((co >> 1) & 1)) * ((size_t)a.Wo * 2) + 2 * ow + (co & 1);
+                        a.y[p * a.ldy + a.yoff + (co >> 2)] = v;
+                    }
+                }
             }
         }
     }
@@ -167,6 +189,17 @@ __global__ __launch_bounds__(CF_THREADS) void nchw_to_nhwc_f32_kernel(const floa
             for (int j = 0; j < 4; j++) v[j] = (c4 + j < C) ? s[(size_t)(c4 + j) * plane] : 0.f;
             *(f32x4*)(d + c4) = v;
         }
+    }
+}
+
+// the way back: one thread per pixel reads its C floats, consecutive threads write consecutive floats of each plane
+__global__ __launch_bounds__(CF_THREADS) void nhwc_to_nchw_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
+                                                                       size_t plane, size_t pixels, int ld, int off) {
+    for (size_t p = (size_t)blockIdx.x * CF_THREADS + threadIdx.x; p < pixels; p += (size_t)gridDim.x * CF_THREADS) {
+        const size_t n = p / plane, q = p - n * plane;
+        const float* s = src + p * ld + off;
+        float* d = dst + n * C * plane + q;
+        for (int c = 0; c < C; c++) d[(size_t)c * plane] = s[c];
     }
 }
 
@@ -191,9 +224,9 @@ int cf_common(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
 }
 
 // the tile of a geometry whose kernel and paddings have passed, or the error the call returns for it
-int cf_finish(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
-    if ((c->Ci != 3 && (c->Ci & 7)) || (c->Co & 7)) return GCC_ERR_UNSUPPORTED;
-    if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
+int cf_finish(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle = 0) {
+    if ((c->Ci != 3 && (c->Ci & 7)) || (c->Co & 7) || (shuffle && (c->Co & 31))) return GCC_ERR_UNSUPPORTED;
+    if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + (shuffle ? c->Co / 4 : c->Co)) return GCC_ERR_BAD_ARG;
     const int span_h = dilation * (c->KH - 1) + 1, span_w = dilation * (c->KW - 1) + 1;
     if (c->H + 2 * pad_h < span_h || c->W + 2 * pad_w < span_w) return GCC_ERR_BAD_ARG;
     const long long Ho = (c->H + 2 * pad_h - span_h) / c->stride + 1, Wo = (c->W + 2 * pad_w - span_w) / c->stride + 1;
@@ -224,9 +257,23 @@ int cf_route_ex(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
     return cf_finish(c, pad_h, pad_w, dilation);
 }
 
-// the one launch of both entries; route: the tile, from cf_route / cf_route_ex
+// gcc_conv_eval_f32_act: cf_route_ex with sides up to 9 and the PixelShuffle(2) store (shuffle 0 or 2; Co a multiple of 32, the
+// window of y Co / 4 channels wide)
+int cf_route_act(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle) {
+    const int bad = cf_common(c, pad_h, pad_w, dilation);
+    if (bad) return bad;
+    if (c->pad != 0 || (shuffle != 0 && shuffle != 2)) return GCC_ERR_BAD_ARG;
+    auto k_ok = [](int k) { return k == 1 || k == 3 || k == 5 || k == 7 || k == 9; };
+    if (!k_ok(c->KH) || !k_ok(c->KW) || (c->stride != 1 && c->stride != 2)) return GCC_ERR_UNSUPPORTED;
+    if ((dilation != 1 && dilation != 2 && dilation != 4) || pad_h > dilation * (c->KH / 2) || pad_w > dilation * (c->KW / 2))
+        return GCC_ERR_UNSUPPORTED;
+    return cf_finish(c, pad_h, pad_w, dilation, shuffle);
+}
+
+// the one launch of all entries; route: the tile, from cf_route / cf_route_ex / cf_route_act; slope, shuffle: the act entry's (EXT)
+template <bool EXT>
 int cf_launch(const gcc_conv_t* c, int route, int pad_h, int pad_w, const float* x, const float* w, float* y,
-              const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream) {
+              const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream, const float* slope = nullptr, int shuffle = 0) {
     if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)ep->residual)) & 15) return GCC_ERR_BAD_ARG;
     if (ep->residual && (ep->ld_residual <= 0 || ep->residual_off < 0 || (ep->ld_residual & 3) || (ep->residual_off & 3) ||
                          ep->ld_residual < ep->residual_off + c->Co))
@@ -244,14 +291,15 @@ int cf_launch(const gcc_conv_t* c, int route, int pad_h, int pad_w, const float*
     a.ldr = ep->residual ? ep->ld_residual : 0; a.roff = ep->residual ? ep->residual_off : 0;
     a.Kreal = c->KH * c->KW * a.Cip; a.Kp = cf_kp(c->Ci, c->KH, c->KW);
     a.relu = ep->act == GCC_EVAL_ACT_RELU;
+    a.slope = slope; a.act = ep->act; a.shuffle = shuffle;
     a.dWo = make_fastdiv(a.Wo); a.dHo = make_fastdiv(a.Ho); a.dCip = make_fastdiv(a.Cip); a.dKW = make_fastdiv(a.KW);
     const hipStream_t st = (hipStream_t)stream;
     if (route == 0)
-        hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128)), dim3(CF_THREADS), 0, st, a);
+        hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2, EXT>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128)), dim3(CF_THREADS), 0, st, a);
     else if (route == 1)
-        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 2, 2>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64)), dim3(CF_THREADS), 0, st, a);
+        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 2, 2, EXT>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64)), dim3(CF_THREADS), 0, st, a);
     else
-        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 4, 1>), dim3(cdiv(a.M, 128), 1), dim3(CF_THREADS), 0, st, a);
+        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 4, 1, EXT>), dim3(cdiv(a.M, 128), 1), dim3(CF_THREADS), 0, st, a);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
@@ -276,7 +324,7 @@ extern "C" int gcc_conv_eval_f32(const gcc_conv_t* c, const float* x, const floa
     if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
     const int route = cf_route(c, ep->dilation);
     if (route < 0) return route;
-    return cf_launch(c, route, c->pad, c->pad, x, w, y, ep, stream);
+    return cf_launch<false>(c, route, c->pad, c->pad, x, w, y, ep, stream);
 }
 
 extern "C" int gcc_conv_eval_f32_ex(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
@@ -286,7 +334,39 @@ extern "C" int gcc_conv_eval_f32_ex(const gcc_conv_t* c, int pad_h, int pad_w, c
     if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU) return GCC_ERR_BAD_ARG;
     const int route = cf_route_ex(c, pad_h, pad_w, ep->dilation);
     if (route < 0) return route;
-    return cf_launch(c, route, pad_h, pad_w, x, w, y, ep, stream);
+    return cf_launch<false>(c, route, pad_h, pad_w, x, w, y, ep, stream);
+}
+
+extern "C" int gcc_conv_eval_f32_act_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle) {
+    return cf_route_act(c, pad_h, pad_w, dilation, shuffle);
+}
+
+extern "C" int gcc_conv_eval_f32_act(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
+                                     const gcc_eval_f32_act_epilogue_t* ep, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    if (ep->act != GCC_EVAL_ACT_NONE && ep->act != GCC_EVAL_ACT_RELU && ep->act != GCC_EVAL_ACT_PRELU && ep->act != GCC_EVAL_ACT_TANH)
+        return GCC_ERR_BAD_ARG;
+    if (ep->act == GCC_EVAL_ACT_PRELU && !ep->slope) return GCC_ERR_BAD_ARG;
+    if (ep->shuffle != 0 && ep->shuffle != 2) return GCC_ERR_BAD_ARG;
+    if (ep->shuffle && ep->residual) return GCC_ERR_UNSUPPORTED;
+    const int route = cf_route_act(c, pad_h, pad_w, ep->dilation, ep->shuffle);
+    if (route < 0) return route;
+    const gcc_eval_f32_epilogue_t base = {ep->scale, ep->shift, ep->residual, ep->ld_residual, ep->residual_off, ep->act, ep->dilation};
+    return cf_launch<true>(c, route, pad_h, pad_w, x, w, y, &base, stream, ep->act == GCC_EVAL_ACT_PRELU ? ep->slope : nullptr,
+                           ep->shuffle);
+}
+
+extern "C" int gcc_nhwc_f32_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!src || !dst || N <= 0 || C <= 0 || H <= 0 || W <= 0 || ld <= 0 || off < 0 || ld < off + C) return GCC_ERR_BAD_ARG;
+    const size_t plane = (size_t)H * W, pixels = plane * N;
+    size_t blocks = (pixels + CF_THREADS - 1) / CF_THREADS;
+    if (blocks > (1u << 20)) blocks = 1u << 20;
+    hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3((unsigned)blocks), dim3(CF_THREADS), 0, (hipStream_t)stream, src, dst, C, plane,
+                       pixels, ld, off);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
 }
 
 extern "C" int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,

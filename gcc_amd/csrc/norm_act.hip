@@ -2308,15 +2308,19 @@ extern "C" int gcc_bn_eval_coeffs_group(const gcc_bn_eval_item_t* items, int n, 
     return GCC_OK;
 }
 
-// util.tensor2im of an NHWC bf16 image: ((x + 1) * 0.5) * 255 in fp32 with explicitly rounded operations (no contraction into
-// an fma, no reassociation), truncated to uint8 -- the bytes numpy computes from the same fp32 values.  One thread per pixel.
-__global__ __launch_bounds__(256) void image_to_u8_kernel(const bf16_t* __restrict__ x, int ld, int off, size_t pixels,
+// util.tensor2im of an NHWC bf16 (or fp32) image: ((x + 1) * 0.5) * 255 in fp32 with explicitly rounded operations (no contraction
+// into an fma, no reassociation), truncated to uint8 -- the bytes numpy computes from the same fp32 values.  One thread per pixel.
+__device__ __forceinline__ float image_elem(bf16_t v) { return bf2f(v); }
+__device__ __forceinline__ float image_elem(float v) { return v; }
+
+template <typename T>
+__global__ __launch_bounds__(256) void image_to_u8_kernel(const T* __restrict__ x, int ld, int off, size_t pixels,
                                                           uint8_t* __restrict__ out) {
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (size_t)gridDim.x * 256) {
-        const bf16_t* px = x + p * ld + off;
+        const T* px = x + p * ld + off;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const float v = bf2f(px[k]);
+            const float v = image_elem(px[k]);
             float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.f), 0.5f), 255.f);
             t = t > 0.f ? (t < 255.f ? t : 255.f) : 0.f;          // also maps NaN to 0
             out[p * 3 + k] = (uint8_t)t;
@@ -2329,8 +2333,19 @@ extern "C" int gcc_image_to_u8(const void* x, int ld, int off, size_t pixels, vo
     if (!x || !out || ld <= 0 || off < 0 || (ld & 7) || (off & 7) || ld < off + 8) return GCC_ERR_BAD_ARG;
     if (!pixels) return GCC_OK;
     const size_t blocks = (pixels + 255) / 256;
-    hipLaunchKernelGGL(image_to_u8_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(image_to_u8_kernel<bf16_t>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ld, off, pixels, (uint8_t*)out);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
+
+extern "C" int gcc_image_to_u8_f32(const float* x, int ld, int off, size_t pixels, void* out, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!x || !out || ld <= 0 || off < 0 || ld < off + 3) return GCC_ERR_BAD_ARG;
+    if (!pixels) return GCC_OK;
+    const size_t blocks = (pixels + 255) / 256;
+    hipLaunchKernelGGL(image_to_u8_kernel<float>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       x, ld, off, pixels, (uint8_t*)out);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }

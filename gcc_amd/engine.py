@@ -2069,9 +2069,21 @@ class SRResNetEngine:
     # scratch in a workspace slot of its own.  It reads the packed bf16 weights of the last repack() and nothing it writes is
     # read by the training path.
 
-    def eval_coeffs(self):
+    PRECISIONS = ('bf16', 'fp32')
+
+    def _precision(self, precision, where):
+        if precision not in self.PRECISIONS:
+            raise _lib.GccError('SRResNetEngine.%s: precision %r; expected one of %s' % (where, precision, ', '.join(self.PRECISIONS)))
+        return precision == 'fp32'
+
+    def eval_coeffs(self, precision='bf16'):
         """scale / shift of the 33 BatchNorms (conv bias folded in) and the biases of the first and subpixel convs from the
-        current parameters and running statistics: ONE launch.  Call once per evaluation, before infer()."""
+        current parameters and running statistics: ONE launch.  Call once per evaluation, before infer().
+        precision='fp32': the coefficients of the fp32 route (a table of its own, the last conv's bias included, every entry
+        zero-padded to 8 channels) and the fp32 packings of all convolutions, refreshed from the master weights into buffers
+        allocated at the first call."""
+        if self._precision(precision, 'eval_coeffs'):
+            return self._eval_coeffs_f32()
         if getattr(self, '_ev_table', None) is None:
             bias = lambda conv: conv.bias.data if conv.bias is not None else None
             entries = [(None, bias(self.first), self.first.rows)]
@@ -2108,15 +2120,22 @@ class SRResNetEngine:
         v.out = view(B, 3, 8, 4)
         return v
 
-    def infer_input(self, N, h, w):
-        """the slab's input view (NHWC bf16, 3 channels): fill it, then infer(it)"""
+    def infer_input(self, N, h, w, precision='bf16'):
+        """the slab's input view (NHWC bf16, 3 channels; precision='fp32': NHWC fp32 in an ld of 4, the fp32 route's own slab):
+        fill it, then infer(it, precision)"""
+        if self._precision(precision, 'infer_input'):
+            return self._infer_bufs_f32(N, h, w).x_in
         return self._infer_bufs(N, h, w).x_in
 
-    def infer(self, x):
+    def infer(self, x, precision='bf16'):
         """eval-mode generator forward of an NHWC bf16 LR batch x [N, 3, h, w]: k9 conv + PReLU | blocks (conv+BN+PReLU,
         conv+BN + x) | conv+BN + long skip | 2 x (conv -> PixelShuffle(2) -> PReLU) | k9 conv + tanh.  One launch per conv
         (two per subpixel block).  Returns the NHWC bf16 image [N, 3, 4h, 4w], a view of the slab valid until the next call.
-        Needs eval_coeffs() of the current parameters."""
+        Needs eval_coeffs() of the current parameters.
+        precision='fp32': x and the image are NHWC fp32 and every layer is ONE gcc_conv_eval_f32_act launch (the reference's own
+        arithmetic: fp32 weights, fp32 activations, exact k-ordered sums); needs eval_coeffs('fp32')."""
+        if self._precision(precision, 'infer'):
+            return self._infer_f32(x)
         if getattr(self, '_ev_table', None) is None:
             raise _lib.GccError('SRResNetEngine.infer: eval_coeffs() first')
         N, _, h, w = x.shape
@@ -2140,6 +2159,92 @@ class SRResNetEngine:
         ops.conv_fprop(h, last.w, last.rows_k, last.k, last.stride, last.pad, out=v.out,
                        bias=last.bias.data if last.bias is not None else None, act=ACT_TANH, ws_slot=None)
         return v.out
+
+    # ---- the same program at the reference's own precision (gcc_conv_eval_f32_act) ------------------------------------------
+    # fp32 packings [Cop][Kp] of the master weights, a coefficient table and a slab of its own; every width is carried at the next
+    # multiple of 8 with zero weights, zero scale and zero shift in the pad channels, which therefore stay 0 through PReLU, the
+    # residual sums and the shuffle (a subpixel conv has 4 ceil8(C) rows: row 4 c + s is channel c of sub-pixel s).
+
+    def _convs_in_order(self):
+        return ([self.first] + [c for b in self.blocks for c in (b.conv1, b.conv2)] + [self.mid] + [c for c, _ in self.sub]
+                + [self.last])
+
+    def _eval_coeffs_f32(self):
+        if getattr(self, '_ev32', None) is None:
+            bias = lambda conv: conv.bias.data if conv.bias is not None else None
+            entries = [(None, bias(self.first), self.first.rows)]
+            for b in self.blocks:
+                entries += [(b.bn1.bn, bias(b.conv1), b.conv1.rows), (b.bn2.bn, bias(b.conv2), b.conv2.rows)]
+            entries.append((self.mid_bn.bn, bias(self.mid), self.mid.rows))
+            entries += [(None, bias(conv), conv.rows) for conv, _ in self.sub]
+            entries.append((None, bias(self.last), self.last.rows))
+            e = type('SREval32', (), {})()
+            subs = [c for c, _ in self.sub]
+            e.convs, e.w, e.dst = self._convs_in_order(), [], []
+            for op in e.convs:
+                Co, Ci, k = op.rows, op.cols, op.k
+                cip = 4 if op is self.first else ops.ceil8(Ci)          # the image: 3 channels in an ld of 4
+                kp = ops.lib().gcc_conv_eval_f32_kp(3 if op is self.first else cip, k, k)
+                _lib.check(min(kp, 0), 'gcc_conv_eval_f32_kp')
+                cop = 4 * ops.ceil8(Co // 4) if op in subs else ops.ceil8(Co)
+                w = torch.zeros((cop, kp), dtype=torch.float32, device=self.device)
+                e.w.append(w)
+                e.dst.append(w[:Co, :k * k * cip].view(Co, k, k, cip)[..., :Ci])
+            e.table = ops.BNEvalTable(entries, self.device, widths=[w.shape[0] for w in e.w])
+            self._ev32 = e
+        e = self._ev32
+        for op, dst in zip(e.convs, e.dst):
+            dst.copy_(op.weight.detach().permute(0, 2, 3, 1))          # strided both ways: no temporary
+        e.table.run()
+
+    def _infer_bufs_f32(self, N, h, w):
+        """views of the fp32 slab: region A the trunk (h0, two block outputs, the inner activation), then the second subpixel
+        block's output; region B the input (ld 4), the first subpixel block's output, then the image (ld 8)"""
+        P, C8 = N * h * w, ops.ceil8(self.C)
+        ci8 = max([ops.ceil8(b.conv1.rows) for b in self.blocks] or [C8])
+        size_a = max(3 * C8 + ci8, 16 * C8) * P
+        size_b = max(4 * C8, 16 * 8) * P
+        if getattr(self, '_ev32_slab', None) is None or self._ev32_slab.numel() < size_a + size_b:
+            self._ev32_slab = None
+            self._ev32_slab = torch.zeros(size_a + size_b, dtype=torch.float32, device=self.device)
+        slab = self._ev32_slab
+
+        def view(off, Cc, ld, s=1):
+            n = N * h * s * w * s * ld
+            return slab[off:off + n].view(N, h * s, w * s, ld).permute(0, 3, 1, 2)[:, :Cc]
+        B = size_a
+        v = type('SRInferBufs32', (), {})()
+        v.h0, v.h = view(0, C8, C8), [view(C8 * P, C8, C8), view(2 * C8 * P, C8, C8)]
+        v.a1 = [view(3 * C8 * P, ops.ceil8(b.conv1.rows), ops.ceil8(b.conv1.rows)) for b in self.blocks]
+        v.s_act = [view(B, C8, C8, 2), view(0, C8, C8, 4)]
+        v.x_in = view(B, 3, 4)
+        v.out = view(B, 8, 8, 4)
+        return v
+
+    def _infer_f32(self, x):
+        e = getattr(self, '_ev32', None)
+        if e is None:
+            raise _lib.GccError("SRResNetEngine.infer: eval_coeffs('fp32') first")
+        N, _, h, w = x.shape
+        v = self._infer_bufs_f32(N, h, w)
+        T, PRELU = e.table, _lib.EVAL_ACT_PRELU
+
+        def conv(i, src, dst, **kw):
+            op = e.convs[i]
+            ops.conv_eval_f32_act(src, e.w[i], e.w[i].shape[0], (op.k, op.k), (op.pad, op.pad), dst, shift=T.shift[i], **kw)
+        conv(0, x, v.h0, act=PRELU, slope=self.first_slope.data)
+        h_, nxt, i = v.h0, 0, 1
+        for b, a1 in zip(self.blocks, v.a1):
+            conv(i, h_, a1, scale=T.scale[i], act=PRELU, slope=b.slope.data)
+            conv(i + 1, a1, v.h[nxt], scale=T.scale[i + 1], residual=h_)
+            h_, nxt, i = v.h[nxt], 1 - nxt, i + 2
+        conv(i, h_, v.h[nxt], scale=T.scale[i], residual=v.h0)
+        h_, i = v.h[nxt], i + 1
+        for j, (_, slope) in enumerate(self.sub):
+            conv(i + j, h_, v.s_act[j], act=PRELU, slope=slope.data, shuffle=2)
+            h_ = v.s_act[j]
+        conv(i + len(self.sub), h_, v.out, act=_lib.EVAL_ACT_TANH)
+        return v.out[:, :3]
 
     def backward(self, c, g_feat=None, wgrad=True):
         """c.g_out holds dL/d(image); g_feat: optional gradients w.r.t. features(c)"""

@@ -9,9 +9,30 @@ import os
 import torch
 
 from .. import ops
-from .._lib import check
+from .._lib import GccError, check
 
 SR_TEST_SETS = ('Set5', 'Set14', 'B100', 'Urban100')      # train.py:37, in the reference's slot order
+PRECISION_ENV = 'GCC_SR_PRECISION'
+PRECISIONS = ('bf16', 'fp32')
+
+
+def sr_precision():
+    """the precision of the generator's inference path in every SRGAN evaluation and in gcc_amd.test --model srgan: the
+    environment variable GCC_SR_PRECISION, 'bf16' (the default) or 'fp32' (the reference's own arithmetic on the f32-input
+    matrix instructions: SRResNetEngine.infer(x, 'fp32')); any other value raises GccError.  The one place that reads it."""
+    precision = os.environ.get(PRECISION_ENV) or 'bf16'
+    if precision not in PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (PRECISION_ENV, precision, ', '.join(PRECISIONS)))
+    return precision
+
+
+def infer_image(G, lr, precision):
+    """the generator's image (an NHWC view of its slab: bf16, or fp32 with precision 'fp32') of an NCHW fp32 LR batch on the
+    device; eval_coeffs(precision) of the current parameters must have run"""
+    N, _, h, w = lr.shape
+    if precision == 'fp32':
+        return G.infer(ops.nchw_to_nhwc_f32(lr, G.infer_input(N, h, w, 'fp32')), 'fp32')
+    return G.infer(ops.nchw_to_nhwc(lr, G.infer_input(N, h, w), cfill=8))
 
 
 class _Scratch:
@@ -45,7 +66,8 @@ def score_batches(model, batches):
     device table, read once at the end; the result is the mean of the per-image values (the reference's)."""
     G, dev, L = model.G, model.device, ops.lib()
     scratch = _scratch(model)
-    G.eval_coeffs()
+    precision = sr_precision()
+    G.eval_coeffs(precision)
     slots = torch.zeros((2, max(len(batches), 1)), dtype=torch.float64, device=dev)      # [sse | ssim sum][image]
     sizes = []
     cur = torch.cuda.current_stream(dev)
@@ -62,14 +84,16 @@ def score_batches(model, batches):
             raise ValueError('score_batches: more batches than len(batches) = %d' % slots.shape[1])
         if N != 1:
             raise ValueError('score_batches: one image per batch (got %d)' % N)
-        x = ops.nchw_to_nhwc(lr, G.infer_input(1, h, w), cfill=8)
-        out = G.infer(x)
+        out = infer_image(G, lr, precision)
         H, W = 4 * h, 4 * w
         if tuple(hr.shape[2:]) != (H, W):
             raise ValueError('score_batches: hr %s is not 4 x lr %s' % (tuple(hr.shape[2:]), (h, w)))
         fake = scratch.image(3 * H * W)
-        op, _, _, _, _, ld = ops.geom(out)
-        check(L.gcc_nhwc_bf16_to_nchw_f32(op, fake.data_ptr(), 1, 3, H, W, ld, 0, ops.stream()), 'gcc_nhwc_bf16_to_nchw_f32')
+        if precision == 'fp32':
+            ops.nhwc_to_nchw_f32(out, fake)
+        else:
+            op, _, _, _, _, ld = ops.geom(out)
+            check(L.gcc_nhwc_bf16_to_nchw_f32(op, fake.data_ptr(), 1, 3, H, W, ld, 0, ops.stream()), 'gcc_nhwc_bf16_to_nchw_f32')
         i = len(sizes)
         ws = scratch.workspace()
         check(L.gcc_psnr_y_sse(fake.data_ptr(), hr.data_ptr(), 1, H, W, slots[0, i:].data_ptr(), 0, ws.data_ptr(), ws.numel(),

@@ -750,6 +750,38 @@ def conv_eval_f32_ex(x, w, Co, kernel, stride, pad, out, dilation=1, scale=None,
     return out
 
 
+def conv_eval_f32_act(x, w, Co, kernel, pad, out, stride=1, dilation=1, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slope=None,
+                      residual=None, shuffle=0, route_only=False):
+    """conv_eval_f32_ex with sides up to 9, PReLU (slope: a DEVICE scalar) and tanh, and shuffle=2 for a PixelShuffle(2) store
+    into out [N, Co / 4, 2 Ho, 2 Wo] (gcc_conv_eval_f32_act).  NHWC fp32 views, w from pack_weights_f32.  One launch."""
+    kh, kw = kernel
+    ph, pw = pad
+    xp, N, Ci, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    d = conv_desc(N, H, W, Ci, Co, kh, stride, 0, ldx, ldy)
+    d.KW = kw
+    if route_only:
+        return lib().gcc_conv_eval_f32_act_route(C.byref(d), ph, pw, dilation, shuffle)
+    ep = _lib.eval_f32_act_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, shuffle, _p(slope), dilation, 0)
+    if residual is not None:
+        rp, _, _, _, _, ldr = geom_f32(residual)
+        ep.residual, ep.ld_residual = rp, ldr
+    check(lib().gcc_conv_eval_f32_act(C.byref(d), ph, pw, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_f32_act')
+    return out
+
+
+def nhwc_to_nchw_f32(src, out=None, Cc=None):
+    """contiguous NCHW fp32 [N, Cc, H, W] of the first Cc channels of an NHWC fp32 view (gcc_nhwc_f32_to_nchw_f32)"""
+    sp, N, C0, H, W, ld = geom_f32(src)
+    Cc = Cc or C0
+    if out is None:
+        out = torch.empty((N, Cc, H, W), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != N * Cc * H * W:
+        raise _lib.GccError('nhwc_to_nchw_f32: out must be a contiguous fp32 tensor of %d elements' % (N * Cc * H * W))
+    check(lib().gcc_nhwc_f32_to_nchw_f32(sp, out.data_ptr(), N, Cc, H, W, ld, 0, stream()), 'gcc_nhwc_f32_to_nchw_f32')
+    return out
+
+
 def nchw_to_nhwc_f32(src, dst, cfill=None):
     """src fp32 [N, C, H, W] contiguous -> the channels of the NHWC fp32 view dst (+ zero fill to cfill, a multiple of 4)"""
     N, Cc, H, W = src.shape
@@ -764,10 +796,15 @@ def nchw_to_nhwc_f32(src, dst, cfill=None):
 
 
 def image_to_u8(x, out=None):
-    """uint8 [N, H, W, 3] of an NHWC bf16 image (gcc_image_to_u8): the bytes of the reference's util.tensor2im"""
-    xp, N, Cx, H, W, ld = geom(x)
+    """uint8 [N, H, W, 3] of an NHWC bf16 image (gcc_image_to_u8) or an NHWC fp32 one (gcc_image_to_u8_f32): the bytes of the
+    reference's util.tensor2im"""
+    f32 = x.dtype is torch.float32
+    xp, N, Cx, H, W, ld = geom_f32(x) if f32 else geom(x)
     if out is None:
         out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    if f32:
+        check(lib().gcc_image_to_u8_f32(xp, ld, 0, N * H * W, out.data_ptr(), stream()), 'gcc_image_to_u8_f32')
+        return out
     check(lib().gcc_image_to_u8(xp, ld, 0, N * H * W, out.data_ptr(), stream()), 'gcc_image_to_u8')
     return out
 
@@ -1162,13 +1199,15 @@ class BNEvalTable:
     """eval-mode scale / shift of a list of (BatchNorm2d or None, conv bias or None, channels) entries in ONE launch
     (gcc_bn_eval_coeffs_group).  The device item table is built once and again only when a parameter moved."""
 
-    def __init__(self, entries, device):
+    def __init__(self, entries, device, widths=None):
+        """widths: the length of every entry's scale / shift views where that is more than its channels; the tail stays zero"""
         self.entries = list(entries)
         self.C = [c for _, _, c in self.entries]
-        self.table = torch.zeros((2, sum(self.C)), dtype=torch.float32, device=device)
         offs = [0]
-        for c in self.C:
-            offs.append(offs[-1] + c)
+        for c, wd in zip(self.C, widths or self.C):
+            assert wd >= c
+            offs.append(offs[-1] + wd)
+        self.table = torch.zeros((2, offs[-1]), dtype=torch.float32, device=device)
         self.scale = [self.table[0, offs[i]:offs[i + 1]] for i in range(len(self.C))]
         self.shift = [self.table[1, offs[i]:offs[i + 1]] for i in range(len(self.C))]
         self.device, self._ptrs, self._items = device, None, None

@@ -6,7 +6,8 @@ Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
             on a Cityscapes root with table.txt and a segmenter at --drn_path (the reference's .pth or TorchScript): prints the mIoU afterwards
   pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
             --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written)
-  srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer
+  srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer, at the precision
+            GCC_SR_PRECISION names (bf16, the default, or fp32: the reference's own)
   cyclegan  phase test, visual_forward, visuals real_A / fake_B
   sagan     the first 1000 batches; the generator through SAGANModel.infer_nhwc (fused eval path)
 Generated images are converted to bytes on the device (gcc_image_to_u8: the reference's tensor2im) and copied to the host once
@@ -98,13 +99,16 @@ class _Writer:
         self.pending = []
 
     def write(self, visuals, img_path):
-        """visuals: label -> NHWC bf16 device view (generated) or NCHW fp32 tensor (input)"""
+        """visuals: label -> NHWC device view, bf16 or fp32 (generated), or NCHW fp32 tensor (input)"""
         from . import ops
         names = result_names(list(visuals), img_path, self.direction)
-        dev = [ops.image_to_u8(visuals[label])[0] for label, _ in names if visuals[label].dtype == torch.bfloat16]
+        # generated: NHWC bf16, or an NHWC fp32 view (channels innermost in a pixel stride of a multiple of 4: ops.geom_f32)
+        generated = lambda t: t.dtype == torch.bfloat16 or (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1
+                                                           and t.stride(3) % 4 == 0)
+        dev = [ops.image_to_u8(visuals[label])[0] for label, _ in names if generated(visuals[label])]
         host = iter(torch.stack(dev).cpu().numpy() if dev else [])        # one device-to-host copy per batch
         for label, rel in names:
-            im = next(host) if visuals[label].dtype == torch.bfloat16 else tensor2im_host(visuals[label])
+            im = next(host) if generated(visuals[label]) else tensor2im_host(visuals[label])
             path = os.path.join(self.dir, rel)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             # the reference passes `aspect_ratio==aspect_ratio` (True == 1.0) for the input image: only fakes are resized
@@ -140,14 +144,13 @@ def run(opt, model):
             sopt = copy.deepcopy(topt)
             sopt.phase = 'test/' + set_name
             w = _Writer(os.path.join(result_dir, set_name), opt.direction, opt.aspect_ratio)
-            G.eval_coeffs()
-            from . import ops
+            from .metric.sr_eval import infer_image, sr_precision
+            precision = sr_precision()
+            G.eval_coeffs(precision)
             for data in create_dataset(sopt, model.device):
                 model.set_input(data)
                 lr = data['lr'].to(model.device, torch.float32).contiguous()
-                N, _, h, wd = lr.shape
-                fake = G.infer(ops.nchw_to_nhwc(lr, G.infer_input(N, h, wd), cfill=8))
-                w.write({'fake_hr': fake}, model.image_paths)
+                w.write({'fake_hr': infer_image(G, lr, precision)}, model.image_paths)
             w.close()
         return result_dir
     w = _Writer(result_dir, opt.direction, opt.aspect_ratio)

@@ -141,11 +141,11 @@ def builtin_evaluator(opt, logger):
         return fid_evaluator(inception, logger)
     if opt.model != 'srgan':
         return None
-    from .metric.sr_eval import available_sets, srgan_evaluator
+    from .metric.sr_eval import available_sets, sr_precision, srgan_evaluator
     sets = available_sets(opt)
     if not sets:
         return None
-    logger.info('SRGAN evaluation every %d epochs on: %s' % (opt.save_epoch_freq, ', '.join(sets)))
+    logger.info('SRGAN evaluation every %d epochs (native, %s) on: %s' % (opt.save_epoch_freq, sr_precision(), ', '.join(sets)))
     return srgan_evaluator(logger, sets)
 
 

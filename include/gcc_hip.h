@@ -534,6 +534,37 @@ int gcc_conv_eval_f32_kp(int Ci, int KH, int KW);
 int gcc_conv_eval_f32_ex(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
                          const gcc_eval_f32_epilogue_t* ep, gcc_stream_t stream);
 int gcc_conv_eval_f32_ex_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation);
+/* gcc_conv_eval_f32_act: gcc_conv_eval_f32_ex's kernel with sides up to 9, PReLU and tanh, and an optional PixelShuffle(2) store --
+ * the same weight packing (gcc_conv_eval_f32_kp), tile shapes, single order of K and pad_h / pad_w arguments.  SRResNet at the
+ * reference's own precision (engine.SRResNetEngine.infer, precision 'fp32'; models/SRGAN.py:139-199).  One launch.  Added without
+ * a GCC_HIP_ABI bump (additions only); the two entries above keep their behaviour and their bits.
+ *     y = act(fmaf(acc, scale[c], shift[c]) + residual)         act: GCC_EVAL_ACT_NONE | _RELU | _PRELU | _TANH
+ *   PReLU is v >= 0 ? v : slope v with `slope` ONE DEVICE scalar read by the kernel (a learned parameter: the host does not read
+ *   it); a null slope with _PRELU, or any other act, is GCC_ERR_BAD_ARG.  tanh is the device library's tanhf.
+ * Geometry: KH and KW each in {1, 3, 5, 7, 9}; everything else, c->pad == 0 included, as gcc_conv_eval_f32_ex.
+ * shuffle: 0, or 2 for nn.PixelShuffle(2): output channel co of Co = 4 C goes to channel yoff + (co >> 2) of pixel
+ *   (2 oh + ((co >> 1) & 1), 2 ow + (co & 1)) of an [N][2 Ho][2 Wo] image with pixel stride ldy.  ldy >= yoff + Co / 4
+ *   (GCC_ERR_BAD_ARG otherwise); Co a multiple of 32, so that a 32-lane store group covers whole sub-pixels, and no residual
+ *   (GCC_ERR_UNSUPPORTED).  Any other value of shuffle: GCC_ERR_BAD_ARG.  One scalar slope commutes with the shuffle, so conv +
+ *   PixelShuffle + PReLU is this one launch.  Only channels [yoff, yoff + Co) -- shuffled: [yoff, yoff + Co / 4) -- are written.
+ * Every refusal happens before anything is launched.  gcc_conv_eval_f32_act_route: the tile (0 / 1 / 2) or the geometry's error. */
+typedef struct {
+    const float* scale;     /* [Co] or NULL (1) */
+    const float* shift;     /* [Co] or NULL (0) */
+    const float* residual;  /* NULL, or NHWC fp32 with the output's geometry, added BEFORE the activation */
+    int ld_residual, residual_off;
+    int act;                /* GCC_EVAL_ACT_NONE | _RELU | _PRELU | _TANH */
+    int shuffle;            /* 0, or 2: the store is nn.PixelShuffle(2) */
+    const float* slope;     /* DEVICE scalar, GCC_EVAL_ACT_PRELU only */
+    int dilation;           /* >= 1 */
+    int pad_;
+} gcc_eval_f32_act_epilogue_t;
+int gcc_conv_eval_f32_act(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
+                          const gcc_eval_f32_act_epilogue_t* ep, gcc_stream_t stream);
+int gcc_conv_eval_f32_act_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle);
+/* dst[n][c][h][w] = src[p][off + c] for c < C: the NHWC fp32 image of gcc_conv_eval_f32_act as the NCHW fp32 buffer the metric
+ * kernels read (gcc_psnr_y_sse, gcc_ssim_y_sum).  off + C <= ld.  One launch. */
+int gcc_nhwc_f32_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, gcc_stream_t stream);
 /* dst[p][off + c] = src[n][c][h][w] for c < C and 0 for C <= c < cfill: an NCHW fp32 image as the NHWC fp32 input of
  * gcc_conv_eval_f32 (ld, off, cfill multiples of 4; off + cfill <= ld; dst 16-byte aligned).  One launch. */
 int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, int cfill,
@@ -541,8 +572,10 @@ int gcc_nchw_f32_to_nhwc_f32(const float* src, float* dst, int N, int C, int H, 
 
 /* Image bytes of the reference's util.tensor2im: out[p][k] = (uint8)(((x + 1) * 0.5) * 255) of channel k < 3 of pixel p of an
  * NHWC bf16 tensor (ld, off: multiples of 8), evaluated in fp32 in that order with no contraction, then truncated (values
- * outside [-1, 1] are clamped to 0 / 255).  out: DEVICE uint8 [pixels][3]. */
+ * outside [-1, 1] are clamped to 0 / 255).  out: DEVICE uint8 [pixels][3].
+ * gcc_image_to_u8_f32: the same arithmetic (one kernel text) on an NHWC fp32 image, ld >= off + 3 in floats. */
 int gcc_image_to_u8(const void* x, int ld, int off, size_t pixels, void* out, gcc_stream_t stream);
+int gcc_image_to_u8_f32(const float* x, int ld, int off, size_t pixels, void* out, gcc_stream_t stream);
 
 /* Backward of y = act(gate(bn(x))) [dropout] given up to two upstream gradients:
  *   g  = g1 * act'(y)  +  g2 * act2'(y)     (g2 from the skip/concat path, may be NULL)
