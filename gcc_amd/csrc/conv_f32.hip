@@ -20,6 +20,12 @@
 // gcc_conv_eval_f32_act is the same kernel (EXT) with sides up to 9, PReLU (a device slope) and tanh in the epilogue, and an
 // optional PixelShuffle(2) store: SRResNet at the reference's own precision (engine.SRResNetEngine.infer, precision 'fp32').  With
 // the shuffle a 32-lane store group (32 consecutive channels of one pixel) puts 8 consecutive floats on each of the 4 sub-pixels.
+//
+// gcc_conv_eval_f32_unet is a second kernel with the same tiles, LDS layout, MFMA loop and order of K (conv_f32_unet_kernel; the
+// kernel above keeps its text and its bits): the U-Net generator's k4 s2 p1 layers at the reference's own precision
+// (engine.UnetEngine.infer, precision 'fp32').  Forward it gathers the 16 taps of Conv2d; transposed, blockIdx.z is one of the four
+// output parity phases, each a 2 x 2-tap gather over the input (K = 4 Ci) whose tile is stored at pixel stride 2.  The epilogue
+// writes up to two activated copies of fmaf(acc, scale, shift): none / ReLU / LeakyReLU (a host slope) / tanh.
 #include "common.hpp"
 
 namespace {
@@ -176,6 +182,154 @@ __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
     }
 }
 
+// ---- gcc_conv_eval_f32_unet: Conv2d / ConvTranspose2d (k4, s2, p1) with two activated outputs -------------------------------
+struct ConvF32UnetArgs {
+    const float* x; const float* w; float* y; float* y2;
+    const float* scale; const float* shift;
+    int M, H, W, Hm, Wm, Ci, Cip, Co;              // M = N Hm Wm rows: forward Hm x Wm is the output map, transposed the input map
+    int ldx, xoff, ldy, yoff, ldy2, y2off, Kreal, Kp, act, act2;
+    float slope;
+    FastDiv dWm, dHm, dCip;
+};
+
+__device__ __forceinline__ float cf_unet_act(float v, int act, float slope) {
+    if (act == GCC_EVAL_ACT_RELU) return v < 0.f ? 0.f : v;
+    if (act == GCC_EVAL_ACT_LRELU) return v >= 0.f ? v : __fmul_rn(slope, v);
+    if (act == GCC_EVAL_ACT_TANH) return tanhf(v);
+    return v;
+}
+
+// TR = false: row m is output pixel (n, oh, ow), tap = kh 4 + kw read at (2 oh - 1 + kh, 2 ow - 1 + kw).
+// TR = true: blockIdx.z = 2 ph + pw is the phase, row m is input-map pixel (n, i, j) and output pixel (n, 2 i + ph, 2 j + pw);
+// tap = 2 th + tw reads (i + ph - th, j + pw - tw), which is kernel element (1 - ph + 2 th, 1 - pw + 2 tw) of ConvTranspose2d.
+template <int MI, int NI, int WM, int WN, bool TR>
+__global__ __launch_bounds__(CF_THREADS) void conv_f32_unet_kernel(ConvF32UnetArgs a) {
+    static_assert(WM * WN == 4, "four waves");
+    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
+    constexpr int A_PER = BM * 4 / CF_THREADS, B_PER = (BN * 4 + CF_THREADS - 1) / CF_THREADS;
+    __shared__ __attribute__((aligned(16))) float As[2][BM * CF_LDK];
+    __shared__ __attribute__((aligned(16))) float Bs[2][BN * CF_LDK];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+    const int chunk = t & 3;
+    const int ph = TR ? (int)(blockIdx.z >> 1) : 0, pw = TR ? (int)(blockIdx.z & 1) : 0;
+    const float* wbase = a.w + (TR ? (size_t)blockIdx.z * a.Co * a.Kp : 0);
+
+    int ih0[A_PER], iw0[A_PER], nb[A_PER];
+#pragma unroll
+    for (int i = 0; i < A_PER; i++) {
+        const int m = m0 + ((t + i * CF_THREADS) >> 2);
+        if (m < a.M) {
+            const int q = fdiv(m, a.dWm), c = m - q * a.Wm;
+            const int n = fdiv(q, a.dHm), r = q - n * a.Hm;
+            ih0[i] = TR ? r + ph : 2 * r - 1; iw0[i] = TR ? c + pw : 2 * c - 1; nb[i] = n * a.H * a.W;
+        } else {
+            ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
+        }
+    }
+    const float* wrow[B_PER];
+#pragma unroll
+    for (int i = 0; i < B_PER; i++) {
+        const int idx = t + i * CF_THREADS, co = n0 + (idx >> 2);
+        wrow[i] = (idx < BN * 4 && co < a.Co) ? wbase + (size_t)co * a.Kp + chunk * 4 : nullptr;
+    }
+
+    f32x4 ra[A_PER], rb[B_PER];
+    auto load = [&](int kt) {
+        const int k4 = kt * CF_BK + chunk * 4;
+        const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;
+        const bool kok = k4 < a.Kreal;
+        const int dh = TR ? -(tap >> 1) : (tap >> 2), dw = TR ? -(tap & 1) : (tap & 3);
+#pragma unroll
+        for (int i = 0; i < A_PER; i++) {
+            const int ih = ih0[i] + dh, iw = iw0[i] + dw;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (kok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
+                v = *(const f32x4*)(a.x + (size_t)(nb[i] + ih * a.W + iw) * a.ldx + a.xoff + ci);
+                if (a.Ci == 3) v[3] = 0.f;           // the stem's pad channel: whatever it holds, it is not an input
+            }
+            ra[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < B_PER; i++) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (wrow[i]) v = *(const f32x4*)(wrow[i] + kt * CF_BK);
+            rb[i] = v;
+        }
+    };
+    auto stage = [&](int s) {
+#pragma unroll
+        for (int i = 0; i < A_PER; i++) *(f32x4*)&As[s][((t + i * CF_THREADS) >> 2) * CF_LDK + chunk * 4] = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_PER; i++) {
+            const int idx = t + i * CF_THREADS;
+            if (idx < BN * 4) *(f32x4*)&Bs[s][(idx >> 2) * CF_LDK + chunk * 4] = rb[i];
+        }
+    };
+
+    f32x16 acc[MI][NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+        for (int ni = 0; ni < NI; ni++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[mi][ni][r] = 0.f;
+
+    // the k loop of conv_f32_kernel: the same LDS reads, the same order of MFMAs
+    const int nk = a.Kp / CF_BK;
+    const int arow = (wm * MI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
+    const int brow = (wn * NI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
+    load(0);
+    stage(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; kt++) {
+        const int cur = kt & 1;
+        if (kt + 1 < nk) load(kt + 1);
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            f32x4 af[MI], bf[NI];
+#pragma unroll
+            for (int mi = 0; mi < MI; mi++) af[mi] = *(const f32x4*)&As[cur][arow + mi * 32 * CF_LDK + g * 8];
+#pragma unroll
+            for (int ni = 0; ni < NI; ni++) bf[ni] = *(const f32x4*)&Bs[cur][brow + ni * 32 * CF_LDK + g * 8];
+#pragma unroll
+            for (int e = 0; e < 4; e++)
+#pragma unroll
+                for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+                    for (int ni = 0; ni < NI; ni++)
+                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi][e], bf[ni][e], acc[mi][ni], 0, 0, 0);
+        }
+        if (kt + 1 < nk) stage(cur ^ 1);
+        __syncthreads();
+    }
+
+    // epilogue: z = fmaf(acc, scale, shift); y = act(z) and, with y2, y2 = act2(z); only rows < M and channels < Co are touched
+#pragma unroll
+    for (int ni = 0; ni < NI; ni++) {
+        const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
+        if (co >= a.Co) continue;
+        const float sc = a.scale ? a.scale[co] : 1.f, sh = a.shift ? a.shift[co] : 0.f;
+#pragma unroll
+        for (int mi = 0; mi < MI; mi++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int m = m0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (m >= a.M) continue;
+                size_t p = (size_t)m;
+                if (TR) {                            // row (n, i, j) of the input map -> pixel (n, 2 i + ph, 2 j + pw) of [N][2 H][2 W]
+                    const int q = fdiv(m, a.dWm), c = m - q * a.Wm;            // q = n H + i
+                    p = ((size_t)q * 2 + ph) * ((size_t)a.Wm * 2) + 2 * c + pw;
+                }
+                const float z = fmaf(acc[mi][ni][r], sc, sh);
+                a.y[p * a.ldy + a.yoff + co] = cf_unet_act(z, a.act, a.slope);
+                if (a.y2) a.y2[p * a.ldy2 + a.y2off + co] = cf_unet_act(z, a.act2, a.slope);
+            }
+        }
+    }
+}
+
 // one thread per pixel: C strided reads (consecutive threads read consecutive floats of a plane), cfill / 4 16-byte stores
 __global__ __launch_bounds__(CF_THREADS) void nchw_to_nhwc_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
                                                                        size_t plane, size_t pixels, int ld, int off, int cfill) {
@@ -304,7 +458,91 @@ int cf_launch(const gcc_conv_t* c, int route, int pad_h, int pad_w, const float*
     return GCC_OK;
 }
 
+// gcc_conv_eval_f32_unet: 16 taps forward, 4 per phase transposed
+inline int cf_unet_kp(int Ci, int transposed) { return ((transposed ? 4 : 16) * cf_cip(Ci) + CF_BK - 1) / CF_BK * CF_BK; }
+
+// the rows one launch slice walks: output pixels forward, input pixels (one phase's output pixels) transposed
+inline long long cf_unet_rows(const gcc_conv_t* c, int transposed) {
+    return transposed ? (long long)c->N * c->H * c->W : (long long)c->N * (c->H / 2) * (c->W / 2);
+}
+
+// gcc_conv_eval_f32_unet: the tile of a geometry (cf_tile on the rows of one phase), or the error the call returns for it
+int cf_route_unet(const gcc_conv_t* c, int transposed) {
+    if (!c || (transposed != 0 && transposed != 1)) return GCC_ERR_BAD_ARG;
+    const int bad = cf_common(c, c->pad, c->pad, 1);
+    if (bad) return bad;
+    if (c->pad != 1) return GCC_ERR_BAD_ARG;               // the U-Net's layers have one padding; anything else is a mistake
+    if (c->KH != 4 || c->KW != 4 || c->stride != 2) return GCC_ERR_UNSUPPORTED;
+    if ((c->Ci & 7) && (c->Ci != 3 || transposed)) return GCC_ERR_UNSUPPORTED;
+    if (c->Co & 7) return GCC_ERR_UNSUPPORTED;
+    if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
+    if (!transposed && (c->H < 2 || c->W < 2)) return GCC_ERR_BAD_ARG;         // a map smaller than the kernel's span
+    const long long M = cf_unet_rows(c, transposed), Mout = transposed ? 4 * M : M, Min = (long long)c->N * c->H * c->W;
+    if (Mout >= (1ll << 31) - 256 || Min >= (1ll << 31) || 16ll * cf_cip(c->Ci) >= (1ll << 30)) return GCC_ERR_UNSUPPORTED;
+    return cf_tile(M, c->Co);
+}
+
+// do the windows [0, Co) of two NHWC tensors of `pixels` pixels share a float?  a, b: addresses in floats
+bool cf_windows_overlap(long long a, int lda, long long b, int ldb, long long pixels, int Co) {
+    if (a + (pixels - 1) * lda + Co <= b || b + (pixels - 1) * ldb + Co <= a) return false;
+    if (lda != ldb) return true;                           // interleaved at two strides: not worth telling apart
+    const long long r = ((b - a) % lda + lda) % lda;
+    return r < Co || r > lda - Co;
+}
+
+template <bool TR>
+void cf_launch_unet(const ConvF32UnetArgs& a, int route, hipStream_t st) {
+    const unsigned z = TR ? 4 : 1;
+    if (route == 0)
+        hipLaunchKernelGGL((conv_f32_unet_kernel<2, 2, 2, 2, TR>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128), z), dim3(CF_THREADS), 0, st, a);
+    else if (route == 1)
+        hipLaunchKernelGGL((conv_f32_unet_kernel<1, 1, 2, 2, TR>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64), z), dim3(CF_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((conv_f32_unet_kernel<1, 1, 4, 1, TR>), dim3(cdiv(a.M, 128), 1, z), dim3(CF_THREADS), 0, st, a);
+}
+
 }  // namespace
+
+extern "C" int gcc_conv_eval_f32_unet_kp(int Ci, int transposed) {
+    if (Ci <= 0 || (transposed != 0 && transposed != 1) || 16ll * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
+    return cf_unet_kp(Ci, transposed);
+}
+
+extern "C" int gcc_conv_eval_f32_unet_route(const gcc_conv_t* c, int transposed) { return cf_route_unet(c, transposed); }
+
+extern "C" int gcc_conv_eval_f32_unet(const gcc_conv_t* c, int transposed, const float* x, const float* w, float* y,
+                                      const gcc_eval_f32_unet_epilogue_t* ep, gcc_stream_t stream) {
+    GCC_ENTER();
+    if (!c || !x || !w || !y || !ep) return GCC_ERR_BAD_ARG;
+    auto act_ok = [](int act) {
+        return act == GCC_EVAL_ACT_NONE || act == GCC_EVAL_ACT_RELU || act == GCC_EVAL_ACT_LRELU || act == GCC_EVAL_ACT_TANH;
+    };
+    if (!act_ok(ep->act) || (ep->y2 && !act_ok(ep->act2))) return GCC_ERR_BAD_ARG;
+    const int route = cf_route_unet(c, transposed);
+    if (route < 0) return route;
+    if ((((uintptr_t)x) | ((uintptr_t)w) | ((uintptr_t)y) | ((uintptr_t)ep->y2)) & 15) return GCC_ERR_BAD_ARG;
+    const long long M = cf_unet_rows(c, transposed), Mout = transposed ? 4 * M : M;
+    if (ep->y2) {
+        if (ep->ldy2 <= 0 || ep->y2off < 0 || (ep->ldy2 & 3) || (ep->y2off & 3) || ep->ldy2 < ep->y2off + c->Co) return GCC_ERR_BAD_ARG;
+        if (cf_windows_overlap((long long)((uintptr_t)y / 4) + c->yoff, c->ldy, (long long)((uintptr_t)ep->y2 / 4) + ep->y2off, ep->ldy2,
+                               Mout, c->Co))
+            return GCC_ERR_BAD_ARG;
+    }
+    ConvF32UnetArgs a;
+    a.x = x; a.w = w; a.y = y; a.y2 = ep->y2; a.scale = ep->scale; a.shift = ep->shift;
+    a.M = (int)M; a.H = c->H; a.W = c->W;
+    a.Hm = transposed ? c->H : c->H / 2; a.Wm = transposed ? c->W : c->W / 2;
+    a.Ci = c->Ci; a.Cip = cf_cip(c->Ci); a.Co = c->Co;
+    a.ldx = c->ldx; a.xoff = c->xoff; a.ldy = c->ldy; a.yoff = c->yoff;
+    a.ldy2 = ep->y2 ? ep->ldy2 : 0; a.y2off = ep->y2 ? ep->y2off : 0;
+    a.Kreal = (transposed ? 4 : 16) * a.Cip; a.Kp = cf_unet_kp(c->Ci, transposed);
+    a.act = ep->act; a.act2 = ep->act2; a.slope = ep->slope;
+    a.dWm = make_fastdiv(a.Wm); a.dHm = make_fastdiv(a.Hm); a.dCip = make_fastdiv(a.Cip);
+    if (transposed) cf_launch_unet<true>(a, route, (hipStream_t)stream);
+    else cf_launch_unet<false>(a, route, (hipStream_t)stream);
+    GCC_CHECK_LAUNCH();
+    return GCC_OK;
+}
 
 extern "C" int gcc_conv_eval_f32_kp(int Ci, int KH, int KW) {
     if (Ci <= 0 || KH <= 0 || KW <= 0 || (long long)KH * KW * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;

@@ -618,10 +618,22 @@ class UnetEngine:
         D = self.D
         return [(self.down[d], self.down_bn[d]) for d in range(1, D)] + [(self.up[d], self.up_bn[d]) for d in range(D - 1, 0, -1)]
 
-    def eval_coeffs(self):
+    PRECISIONS = ('bf16', 'fp32')
+
+    def _precision(self, precision, where):
+        if precision not in self.PRECISIONS:
+            raise _lib.GccError('UnetEngine.%s: precision %r; expected one of %s' % (where, precision, ', '.join(self.PRECISIONS)))
+        return precision == 'fp32'
+
+    def eval_coeffs(self, precision='bf16'):
         """scale / shift of every BatchNorm of the generator (conv bias folded in) and the bias of the innermost conv from the
         current parameters and running statistics: ONE launch.  Call after the parameters or running statistics changed,
-        before infer()."""
+        before infer().
+        precision='fp32': the coefficients of the fp32 route (a table of its own, the outermost convs' biases included, every entry
+        zero-padded to 8 channels) and the fp32 packings of all 2 D convolutions, refreshed from the master weights into buffers
+        allocated at the first call."""
+        if self._precision(precision, 'eval_coeffs'):
+            return self._eval_coeffs_f32()
         if getattr(self, '_ev_table', None) is None:
             entries = []
             for conv, bn in self._ev_layers():
@@ -662,8 +674,11 @@ class UnetEngine:
         v.out = view(region[0], 3, 8, H, W)
         return v
 
-    def infer_input(self, N, H, W):
-        """the slab's input view (NHWC bf16, 3 channels): fill it, then infer(it)"""
+    def infer_input(self, N, H, W, precision='bf16'):
+        """the slab's input view (NHWC bf16, 3 channels; precision='fp32': NHWC fp32 in an ld of 4, the fp32 route's own slab):
+        fill it, then infer(it, precision)"""
+        if self._precision(precision, 'infer_input'):
+            return self._infer_bufs_f32(N, H, W).x_in
         return self._infer_bufs(N, H, W).x_in
 
     def _infer(self, x, count_only=False):
@@ -706,21 +721,133 @@ class UnetEngine:
                        bias=u0.bias.data if u0.bias is not None else None, act=ACT_TANH, slope=LRELU, ws_slot=None)
         return v.out
 
-    def infer(self, x):
+    def infer(self, x, precision='bf16'):
         """eval-mode generator forward of an NHWC bf16 batch x [N, 3, H, W] (H, W multiples of 2^D): d0 conv + bias with its
         LeakyReLU and ReLU copies | down convs + BatchNorm, LeakyReLU and a ReLU copy into the concat buffer | innermost conv
         (+ BatchNorm) + ReLU | up convs + BatchNorm + ReLU into the concat buffers | u0 + bias + tanh.  One launch per conv
         (two where K is split; infer_launches() says how many).  Returns the NHWC bf16 image [N, 3, H, W], a view of the slab
-        valid until the next call.  Needs eval_coeffs() of the current parameters and running statistics."""
+        valid until the next call.  Needs eval_coeffs() of the current parameters and running statistics.
+        precision='fp32': x and the image are NHWC fp32 and every layer is ONE gcc_conv_eval_f32_unet launch, 2 D in all (the
+        reference's own arithmetic: fp32 weights, fp32 activations, exact k-ordered sums); needs eval_coeffs('fp32')."""
+        if self._precision(precision, 'infer'):
+            return self._infer_f32(x)
         if getattr(self, '_ev_table', None) is None:
             raise _lib.GccError('UnetEngine.infer: eval_coeffs() first')
         return self._infer(x)
 
-    def infer_launches(self, N, H, W):
+    def infer_launches(self, N, H, W, precision='bf16'):
         """kernel launches infer() makes for an N x H x W batch, from the library's route introspection (launches nothing)"""
+        if self._precision(precision, 'infer_launches'):
+            return self._infer_f32(self.infer_input(N, H, W, 'fp32'), count_only=True)
         if getattr(self, '_ev_table', None) is None:
             raise _lib.GccError('UnetEngine.infer_launches: eval_coeffs() first')
         return self._infer(self.infer_input(N, H, W), count_only=True)
+
+    # ---- the same program at the reference's own precision (gcc_conv_eval_f32_unet) -----------------------------------------
+    # fp32 packings of the master weights, a coefficient table and a slab of its own; every width is carried at the next multiple
+    # of 8 with zero weights, zero scale and zero shift in the pad channels, which therefore stay 0 through every activation.  The
+    # concat buffers keep the bf16 route's layout (skip part padded to 8 | up part padded to 8), so an up conv's packing takes the
+    # two row ranges of its master at uoff.  Layer i of 2 D: down 0 .. D-1, then up D-1 .. 0.
+
+    def _eval_coeffs_f32(self):
+        if getattr(self, '_ev32', None) is None:
+            D, wd, uw, dev = self.D, self.width, self.uwidth, self.device
+            bias = lambda conv: conv.bias.data if conv.bias is not None else None
+            e = type('UnetEval32', (), {})()
+            e.w, e.copies, entries = [], [], []          # copies: (view of a packing, conv, its master's row range or None)
+            for d in range(D):
+                op = self.down[d]
+                w, dst = ops.unet_weights_f32(3 if d == 0 else ops.ceil8(wd[d - 1]), ops.ceil8(wd[d]), False, dev)
+                e.w.append(w)
+                e.copies.append((dst[:op.rows, :, :, :op.cols], op, None, None))
+                entries.append((self.down_bn[d].bn if self.down_bn[d] is not None else None, bias(op), op.rows))
+            for d in range(D - 1, -1, -1):
+                op = self.up[d]
+                inner = d == D - 1
+                w, dst = ops.unet_weights_f32(ops.ceil8(wd[d]) if inner else self.catw[d + 1], ops.ceil8(uw[d]), True, dev)
+                e.w.append(w)
+                for p, v in enumerate(dst):
+                    if inner:
+                        e.copies.append((v[:op.cols, :, :, :op.rows], op, p, (0, op.rows)))
+                    else:
+                        e.copies.append((v[:op.cols, :, :, :wd[d]], op, p, (0, wd[d])))
+                        e.copies.append((v[:op.cols, :, :, self.uoff[d + 1]:self.uoff[d + 1] + uw[d + 1]], op, p, (wd[d], op.rows)))
+                entries.append((self.up_bn[d].bn if self.up_bn[d] is not None else None, bias(op), op.cols))
+            e.table = ops.BNEvalTable(entries, dev, widths=[w.shape[-2] for w in e.w])
+            self._ev32 = e
+        e = self._ev32
+        for dst, op, phase, rows in e.copies:              # strided both ways: no temporary
+            m = op.weight.detach()
+            if phase is None:
+                dst.copy_(m.permute(0, 2, 3, 1))
+            else:
+                dst.copy_(m[rows[0]:rows[1], :, 1 - (phase >> 1)::2, 1 - (phase & 1)::2].permute(1, 2, 3, 0))
+        e.table.run()
+
+    def _infer_bufs_f32(self, N, H, W):
+        """views of the fp32 slab, every one at its full padded width: the input (ld 4), two regions (the down path's LeakyReLU
+        outputs alternate between them; the innermost output and the image, ld 8, reuse them), the concat buffers"""
+        D, wd = self.D, self.width
+        hs = [(H >> (d + 1), W >> (d + 1)) for d in range(D)]
+        P = [N * h * w for h, w in hs]
+        size_x = N * H * W * 4
+        size_r = max([N * H * W * 8] + [P[d] * ops.ceil8(wd[d]) for d in range(D)])
+        cat_off = [0] * D
+        total = size_x + 2 * size_r
+        for d in range(1, D):
+            cat_off[d] = total
+            total += P[d - 1] * self.catw[d]
+        if getattr(self, '_ev32_slab', None) is None or self._ev32_slab.numel() < total:
+            self._ev32_slab = None
+            self._ev32_slab = torch.zeros(total, dtype=torch.float32, device=self.device)
+        slab = self._ev32_slab
+
+        def view(off, Cc, ld, h, w):
+            return slab[off:off + N * h * w * ld].view(N, h, w, ld).permute(0, 3, 1, 2)[:, :Cc]
+        v = type('UnetInferBufs32', (), {})()
+        v.hs = hs
+        v.x_in = view(0, 3, 4, H, W)
+        region = [size_x, size_x + size_r]
+        v.lin = [None] + [view(region[(d + 1) % 2], ops.ceil8(wd[d]), ops.ceil8(wd[d]), *hs[d]) for d in range(D - 1)]
+        v.e_act = view(region[D % 2], ops.ceil8(wd[D - 1]), ops.ceil8(wd[D - 1]), *hs[D - 1])
+        v.rcat = [None] + [view(cat_off[d], self.catw[d], self.catw[d], *hs[d - 1]) for d in range(1, D)]
+        v.out = view(region[0], 8, 8, H, W)
+        return v
+
+    def _infer_f32(self, x, count_only=False):
+        e = getattr(self, '_ev32', None)
+        if e is None:
+            raise _lib.GccError("UnetEngine.infer: eval_coeffs('fp32') first")
+        N, _, H, W = x.shape
+        D, wd, uw = self.D, self.width, self.uwidth
+        if H % (1 << D) or W % (1 << D):
+            raise _lib.GccError('UnetEngine.infer: H, W must be multiples of %d' % (1 << D))
+        v = self._infer_bufs_f32(N, H, W)
+        T, E = e.table, _lib
+        launches = 0
+
+        def ev(i, src, dst, act, y2=None, transposed=False):
+            nonlocal launches
+            has_bn = T.entries[i][0] is not None
+            r = ops.conv_eval_f32_unet(src, e.w[i], e.w[i].shape[-2], dst, transposed=transposed,
+                                       scale=T.scale[i] if has_bn else None, shift=T.shift[i], act=act, y2=y2,
+                                       act2=E.EVAL_ACT_RELU, slope=LRELU, route_only=count_only)
+            if count_only:
+                _lib.check(min(r, 0), 'gcc_conv_eval_f32_unet_route')
+                launches += 1
+        src = x
+        for d in range(D - 1):
+            w8 = ops.ceil8(wd[d])
+            ev(d, src, v.lin[d + 1], E.EVAL_ACT_LRELU, y2=v.rcat[d + 1][:, :w8])
+            src = v.lin[d + 1]
+        # innermost: conv + ReLU, or (a block around Identity) conv + BatchNorm + ReLU
+        ev(D - 1, src, v.e_act, E.EVAL_ACT_RELU)
+        src = v.e_act
+        for d in range(D - 1, 0, -1):
+            ev(2 * D - 1 - d, src, v.rcat[d][:, self.uoff[d]:self.uoff[d] + ops.ceil8(uw[d])], E.EVAL_ACT_RELU, transposed=True)
+            src = v.rcat[d]
+        ev(2 * D - 1, src, v.out, E.EVAL_ACT_TANH, transposed=True)
+        return launches if count_only else v.out[:, :3]
 
     # ---------------------------------------------------------------------------------------
     def backward(self, c, g_feat=None, wgrad=True):

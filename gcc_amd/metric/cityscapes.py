@@ -115,7 +115,10 @@ def _f3(v):
 
 def seg_input(image, out=None):
     """the segmenter's input (NCHW fp32 [N, 3, H, W]) of generated images: an NHWC bf16 activation (the generator's output; the
-    byte of util.tensor2im first) or a uint8 [N, H, W, 3] device tensor (those bytes themselves); gcc_seg_input"""
+    byte of util.tensor2im first) or a uint8 [N, H, W, 3] device tensor (those bytes themselves); gcc_seg_input.  An NHWC fp32
+    activation (the generator's fp32 route) becomes its bytes first (gcc_image_to_u8_f32) and goes on as uint8."""
+    if image.dtype == torch.float32:
+        image = ops.image_to_u8(image)
     if image.dtype == torch.uint8:
         if image.dim() == 3:
             image = image[None]

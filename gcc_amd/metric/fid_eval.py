@@ -61,7 +61,11 @@ def sagan_count(length):
 def fid_input(image, out=None):
     """the network's input (NCHW fp32 [N, 3, H, W] in [0, 1]) through gcc_fid_input: of an NHWC bf16 activation view (a
     generator's output), a uint8 [N, H, W, 3] device tensor, or an NCHW fp32 device tensor in [-1, 1] (a loader's image); the
-    byte of util.tensor2imgs over 255.  ``out``: a contiguous fp32 [N, 3, H, W] device tensor, e.g. a slot of a batch buffer."""
+    byte of util.tensor2imgs over 255.  ``out``: a contiguous fp32 [N, 3, H, W] device tensor, e.g. a slot of a batch buffer.
+    An NHWC fp32 activation view (a generator's fp32 route: channels innermost in a pixel stride of at least 4) becomes its
+    bytes first (gcc_image_to_u8_f32) and goes on as uint8."""
+    if image.dtype == torch.float32 and image.dim() == 4 and image.stride(1) == 1 and image.stride(3) >= 4:
+        image = ops.image_to_u8(image)
     if image.dtype == torch.uint8:
         if image.dim() == 3:
             image = image[None]

@@ -25,7 +25,7 @@ from .. import engine, ops
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from .Pix2Pix import MobileResnetGenerator, _patchgan_tree
+from .Pix2Pix import MobileResnetGenerator, _patchgan_tree, gen_precision
 from ._base import ARCH_SLOTS, GANModelBase, _ChainWgrad
 from ._optim import HipAdam
 
@@ -362,6 +362,7 @@ class MobileCycleGANModel(GANModelBase):
         Returns an NHWC bf16 [N, 3, H, W] view valid until the next call of the same generator."""
         if generator not in ('A', 'B'):
             raise ValueError("generator must be 'A' or 'B'")
+        gen_precision(only_bf16='--model cyclegan')
         if isinstance(real, dict):
             AtoB = self.opt.direction == 'AtoB'
             real = real[('A' if AtoB else 'B') if generator == 'A' else ('B' if AtoB else 'A')]

@@ -242,6 +242,25 @@ def _drain(gen, stream):
             pass
 
 
+GEN_PRECISION_ENV = 'GCC_GEN_PRECISION'
+GEN_PRECISIONS = ('bf16', 'fp32')
+
+
+def gen_precision(only_bf16=None):
+    """the precision of the generator's inference path (Pix2PixModel.infer_nhwc) in gcc_amd.test --model pix2pix and in the
+    per-epoch mIoU and FID evaluations: the environment variable GCC_GEN_PRECISION, 'bf16' (the default) or 'fp32' (the
+    reference's own arithmetic on the f32-input matrix instructions: UnetEngine.infer(x, 'fp32')); any other value raises
+    GccError.  The one place that reads it.  only_bf16: the caller is a generator without an fp32 route and names its backbone or
+    model here -- 'fp32' then raises instead of falling back."""
+    precision = os.environ.get(GEN_PRECISION_ENV) or 'bf16'
+    if precision not in GEN_PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (GEN_PRECISION_ENV, precision, ', '.join(GEN_PRECISIONS)))
+    if precision == 'fp32' and only_bf16:
+        raise GccError('%s=fp32: the fp32 generator route exists for the U-Net only (--model pix2pix --backbone unet), not for %s'
+                       % (GEN_PRECISION_ENV, only_bf16))
+    return precision
+
+
 # ------------------------------------------------------------------------------------------------
 class Pix2PixModel(GANModelBase):
     DISTILL_LOSSES = GANModelBase.DISTILL_LOSSES[:2]             # no 'L1' entry: G_L1 is always logged
@@ -426,30 +445,37 @@ class Pix2PixModel(GANModelBase):
     def infer_nhwc(self, real):
         """the generator in eval mode on `real` (NCHW fp32: the generator's input, real_A; or a dataset batch dict, whose input
         is picked by --direction as set_input does) through the fused inference path (UnetEngine.infer): an NHWC bf16
-        [N, 3, H, W] view valid until the next call.  Refreshes the eval-mode coefficients (one launch) when the parameters or
-        running statistics changed since the last call.  --backbone resnet: MobileResnetEngine.infer."""
+        [N, 3, H, W] view valid until the next call -- an NHWC fp32 one with GCC_GEN_PRECISION=fp32 (gen_precision).  Refreshes
+        the eval-mode coefficients of that precision (one launch; fp32: and the fp32 weight packings) when the parameters or
+        running statistics changed since its last call.  --backbone resnet: MobileResnetEngine.infer, bf16 only."""
         if isinstance(real, dict):
             real = real['A' if self.opt.direction == 'AtoB' else 'B']
         real = real.to(self.device, torch.float32).contiguous()
         N, _, H, W = real.shape
         if self.resnet:
+            gen_precision(only_bf16='--backbone resnet')
             # InstanceNorm without running statistics: nothing to refresh (MobileResnetEngine.infer)
             self.finish_G_update()
             x = self.G.infer_input(N, H, W)
             ops.nchw_to_nhwc(real, x, cfill=8)
             return self.G.infer(x)
+        precision = gen_precision()
         self.finish_G_update()
-        if getattr(self, '_ev_generation', None) != self._g_generation:
-            self.G.eval_coeffs()
-            self._ev_generation = self._g_generation
-        x = self.G.infer_input(N, H, W)
+        done = self.__dict__.setdefault('_ev_generation', {})
+        if done.get(precision) != self._g_generation:
+            self.G.eval_coeffs(precision)
+            done[precision] = self._g_generation
+        x = self.G.infer_input(N, H, W, precision)
+        if precision == 'fp32':
+            return self.G.infer(ops.nchw_to_nhwc_f32(real, x), 'fp32')
         ops.nchw_to_nhwc(real, x, cfill=8)
         return self.G.infer(x)
 
     def infer(self, real):
         """fake_B = G(real) in eval mode as NCHW fp32 (see infer_nhwc), whatever mode the model is in; forward() in eval mode
         keeps its own route."""
-        return ops.nhwc_to_nchw(self.infer_nhwc(real), 3)
+        image = self.infer_nhwc(real)
+        return ops.nhwc_to_nchw_f32(image, Cc=3) if image.dtype is torch.float32 else ops.nhwc_to_nchw(image, 3)
 
     @property
     def fake_B(self):

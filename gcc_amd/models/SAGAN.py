@@ -28,6 +28,7 @@ from .. import engine, ops
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
+from .Pix2Pix import gen_precision
 from ._base import GANModelBase, _ChainWgrad
 from ._optim import HipAdam
 
@@ -246,6 +247,7 @@ class SAGANModel(GANModelBase):
         (SaganGeneratorEngine.infer): an NHWC bf16 [N, 3, 64, 64] view valid until the next call.  z: [N, z_dim] (or
         [N, z_dim, 1, 1]) on the host or the device, or a dataset batch dict.  Like an eval forward() it advances the
         generator's power iterations (u, v); it touches no training buffer.  forward() keeps its own route."""
+        gen_precision(only_bf16='--model sagan')
         if isinstance(z, dict):
             z = z['z']
         N = z.shape[0]

@@ -770,6 +770,55 @@ def conv_eval_f32_act(x, w, Co, kernel, pad, out, stride=1, dilation=1, scale=No
     return out
 
 
+def unet_weights_f32(Ci, Co, transposed, device):
+    """(w, dst) for gcc_conv_eval_f32_unet: the zero-filled packed buffer of a k4 s2 p1 layer of Ci -> Co channels (each a multiple
+    of 8, or Ci == 3 forward) and the strided view(s) of it that dst.copy_(src) fills from the master weights --
+    forward: w [Co][Kp], one view [Co, 4, 4, Ci] to fill from weight.permute(0, 2, 3, 1) of Conv2d's [Co, Ci, 4, 4];
+    transposed: w [4][Co][Kp], per phase 2 ph + pw one view [Co, 2, 2, Ci] (taps th, tw) to fill from
+    weight[:, :, 1 - ph::2, 1 - pw::2].permute(1, 2, 3, 0) of ConvTranspose2d's [Ci, Co, 4, 4] (include/gcc_hip.h).
+    Views of fewer channels (dst[..., :ci], dst[:co]) leave the pad channels zero."""
+    kp = lib().gcc_conv_eval_f32_unet_kp(Ci, 1 if transposed else 0)
+    check(min(kp, 0), 'gcc_conv_eval_f32_unet_kp')
+    cip = 4 if Ci == 3 else Ci
+    if not transposed:
+        w = torch.zeros((Co, kp), dtype=torch.float32, device=device)
+        return w, w[:, :16 * cip].view(Co, 4, 4, cip)[..., :Ci]
+    w = torch.zeros((4, Co, kp), dtype=torch.float32, device=device)
+    return w, [w[p, :, :4 * Ci].view(Co, 2, 2, Ci) for p in range(4)]
+
+
+def pack_weights_f32_unet(master, transposed):
+    """the packing gcc_conv_eval_f32_unet reads, from Conv2d's [Co, Ci, 4, 4] or (transposed) ConvTranspose2d's [Ci, Co, 4, 4]"""
+    m = master.detach().float()
+    if not transposed:
+        w, dst = unet_weights_f32(m.shape[1], m.shape[0], False, m.device)
+        dst.copy_(m.permute(0, 2, 3, 1))
+        return w
+    w, dst = unet_weights_f32(m.shape[0], m.shape[1], True, m.device)
+    for p, d in enumerate(dst):
+        d.copy_(m[:, :, 1 - (p >> 1)::2, 1 - (p & 1)::2].permute(1, 2, 3, 0))
+    return w
+
+
+def conv_eval_f32_unet(x, w, Co, out, transposed=False, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, y2=None,
+                       act2=_lib.EVAL_ACT_NONE, slope=0.2, route_only=False):
+    """the U-Net's k4 s2 p1 layer in fp32 (gcc_conv_eval_f32_unet): z = scale[c] conv(x, w) + shift[c]; out = act(z), y2 = act2(z).
+    x [N, Ci, H, W], out / y2 [N, Co, H / 2, W / 2] or (transposed) [N, Co, 2 H, 2 W]: NHWC fp32 views; w from unet_weights_f32.
+    One launch, no workspace.  route_only: the tile the library takes (>= 0) or its error for the geometry, nothing launched."""
+    xp, N, Ci, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    d = conv_desc(N, H, W, Ci, Co, 4, 2, 1, ldx, ldy)
+    tr = 1 if transposed else 0
+    if route_only:
+        return lib().gcc_conv_eval_f32_unet_route(C.byref(d), tr)
+    ep = _lib.eval_f32_unet_epilogue_t(_p(scale), _p(shift), None, 0, 0, act, act2, slope, 0)
+    if y2 is not None:
+        y2p, _, _, _, _, ldy2 = geom_f32(y2)
+        ep.y2, ep.ldy2 = y2p, ldy2
+    check(lib().gcc_conv_eval_f32_unet(C.byref(d), tr, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_f32_unet')
+    return out
+
+
 def nhwc_to_nchw_f32(src, out=None, Cc=None):
     """contiguous NCHW fp32 [N, Cc, H, W] of the first Cc channels of an NHWC fp32 view (gcc_nhwc_f32_to_nchw_f32)"""
     sp, N, C0, H, W, ld = geom_f32(src)

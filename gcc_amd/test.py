@@ -2,7 +2,8 @@
 over the test split, write PNGs under <checkpoints_dir>/<name>/test_results with the names of the reference's util.save_images.
 
 Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
-  pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer (fused eval path);
+  pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer_nhwc (fused eval path)
+            at the precision GCC_GEN_PRECISION names (bf16, the default, or fp32: the reference's own; U-Net only);
             on a Cityscapes root with table.txt and a segmenter at --drn_path (the reference's .pth or TorchScript): prints the mIoU afterwards
   pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
             --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written)
@@ -99,13 +100,15 @@ class _Writer:
         self.pending = []
 
     def write(self, visuals, img_path):
-        """visuals: label -> NHWC device view, bf16 or fp32 (generated), or NCHW fp32 tensor (input)"""
+        """visuals: label -> NHWC device view, bf16 or fp32, or its uint8 [N, H, W, 3] bytes (generated), or NCHW fp32 tensor
+        (input)"""
         from . import ops
         names = result_names(list(visuals), img_path, self.direction)
         # generated: NHWC bf16, or an NHWC fp32 view (channels innermost in a pixel stride of a multiple of 4: ops.geom_f32)
-        generated = lambda t: t.dtype == torch.bfloat16 or (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1
-                                                           and t.stride(3) % 4 == 0)
-        dev = [ops.image_to_u8(visuals[label])[0] for label, _ in names if generated(visuals[label])]
+        generated = lambda t: t.dtype in (torch.bfloat16, torch.uint8) or (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1
+                                                                          and t.stride(3) % 4 == 0)
+        u8 = lambda t: t if t.dtype == torch.uint8 else ops.image_to_u8(t)
+        dev = [u8(visuals[label])[0] for label, _ in names if generated(visuals[label])]
         host = iter(torch.stack(dev).cpu().numpy() if dev else [])        # one device-to-host copy per batch
         for label, rel in names:
             im = next(host) if generated(visuals[label]) else tensor2im_host(visuals[label])
@@ -170,6 +173,9 @@ def run(opt, model):
             print('no FID evaluation: %s' % why)
         else:
             fid = fid_eval.fid_evaluator(inception).scorer(model, topt)
+    if opt.model == 'pix2pix':
+        from .models.Pix2Pix import gen_precision
+        print('generator precision: %s' % gen_precision(only_bf16='--backbone resnet' if model.resnet else None))
     dataset = create_dataset(topt, model.device)
     if scorer is not None and getattr(dataset, 'paths', None) is not None:
         scorer.prefetch(dataset.paths)
@@ -178,7 +184,11 @@ def run(opt, model):
             break
         model.set_input(data)
         if opt.model == 'pix2pix':
-            visuals = {'real_A': model.real_A, 'fake_B': model.infer_nhwc(model.real_A)}
+            fake = model.infer_nhwc(model.real_A)
+            if fake.dtype == torch.float32:      # the fp32 route: tensor2im's bytes once, for the PNG and both scorers
+                from . import ops
+                fake = ops.image_to_u8(fake)
+            visuals = {'real_A': model.real_A, 'fake_B': fake}
             if scorer is not None:
                 scorer.add(data['A_paths'][0], visuals['fake_B'])
             if fid is not None:

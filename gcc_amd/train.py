@@ -112,6 +112,18 @@ def run_evaluation(model, opt, logger, epoch, best, evaluate, ckpt_dir):
     return [v for v, _ in scores]
 
 
+def _generator_note(opt):
+    """what an evaluation's announcement says about the generator whose images it scores: nothing on the default bf16 inference
+    route, its precision once GCC_GEN_PRECISION selects another (models/Pix2Pix.py gen_precision; a generator without an fp32
+    route raises here, before the first epoch)"""
+    from .models.Pix2Pix import gen_precision
+    if opt.model == 'pix2pix':
+        precision = gen_precision(only_bf16='--backbone resnet' if opt.backbone == 'resnet' else None)
+    else:
+        precision = gen_precision(only_bf16='--model %s' % opt.model)
+    return '' if precision == 'bf16' else '; generator images in %s' % precision
+
+
 def builtin_evaluator(opt, logger):
     """the evaluation a run gets without an explicit evaluate=: SRGAN's PSNR / SSIM on the reference's test sets found under
     <dataroot>/test (train.py:37-56); Pix2Pix's mIoU on a Cityscapes root that holds table.txt when --drn_path is the reference's
@@ -125,8 +137,8 @@ def builtin_evaluator(opt, logger):
             logger.info('no Cityscapes mIoU evaluation: %s' % why)
             return None
         precision = getattr(segmenter, 'precision', None)          # the native engine's; a TorchScript archive has none
-        logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s%s'
-                    % (opt.save_epoch_freq, opt.drn_path, ' (native, %s)' % precision if precision else ''))
+        logger.info('Cityscapes mIoU evaluation every %d epochs with the segmenter %s%s%s'
+                    % (opt.save_epoch_freq, opt.drn_path, ' (native, %s)' % precision if precision else '', _generator_note(opt)))
         return cityscapes_evaluator(segmenter, logger)
     if str(opt.dataroot).startswith('synthetic'):
         return None
@@ -136,8 +148,8 @@ def builtin_evaluator(opt, logger):
         if inception is None:
             logger.info('no FID evaluation: %s' % why)
             return None
-        logger.info('FID evaluation every %d epochs with the Inception network %s%s'
-                    % (opt.save_epoch_freq, os.environ[ENV], network_label(inception)))
+        logger.info('FID evaluation every %d epochs with the Inception network %s%s%s'
+                    % (opt.save_epoch_freq, os.environ[ENV], network_label(inception), _generator_note(opt)))
         return fid_evaluator(inception, logger)
     if opt.model != 'srgan':
         return None

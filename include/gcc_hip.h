@@ -562,6 +562,47 @@ typedef struct {
 int gcc_conv_eval_f32_act(const gcc_conv_t* c, int pad_h, int pad_w, const float* x, const float* w, float* y,
                           const gcc_eval_f32_act_epilogue_t* ep, gcc_stream_t stream);
 int gcc_conv_eval_f32_act_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle);
+/* gcc_conv_eval_f32_unet: the U-Net generator's layers at the reference's own precision (engine.UnetEngine.infer, precision
+ * 'fp32'; models/Pix2Pix.py:40-118): Conv2d(k4, s2, p1) and ConvTranspose2d(k4, s2, p1) in fp32 with up to two activated outputs.
+ * A kernel of its own with gcc_conv_eval_f32's tiles, matrix instruction and ONE order of K (walked in steps of 16, every product
+ * an fmaf onto the running sum; no split-K, no atomics, no workspace): an output element does not depend on its batch, its tile
+ * or the tile shape.  One launch.  Added without a GCC_HIP_ABI bump (additions only); the three entries above keep their text and
+ * their bits.  With z = fmaf(acc, scale[c], shift[c]):
+ *     y [p][c] = act (z)   at (c->ldy, c->yoff)
+ *     y2[p][c] = act2(z)   at (ldy2, y2off)          (y2 NULL: no second store, act2 not read)
+ *   act / act2: GCC_EVAL_ACT_NONE | _RELU | _LRELU | _TANH.  _LRELU is z >= 0 ? z : slope z with the host `slope`, one rounded
+ *   multiply; tanh is the device library's tanhf.  There is no residual.
+ * The descriptor is the LAYER's in both directions (unlike gcc_conv_eval_ex, which reads a transposed call as a data gradient):
+ *   c->H, c->W, c->Ci, c->ldx, c->xoff describe the input x; c->Co, c->ldy, c->yoff the output y.
+ *   transposed = 0: y is [N][H / 2][W / 2] (H, W >= 2, odd sizes round down), taps at ih = 2 oh - 1 + kh.
+ *   transposed = 1: y is [N][2 H][2 W] (H, W >= 1).  Each of the four output parity phases (oh & 1, ow & 1) is a 2 x 2-tap gather
+ *     over x with K = 4 Ci, stored at pixel stride 2: an even oh takes kh = 1 from ih = oh / 2 and kh = 3 from ih = oh / 2 - 1, an
+ *     odd oh takes kh = 0 from ih = (oh + 1) / 2 and kh = 2 from ih = (oh - 1) / 2; ow alike.  Nothing is zero-stuffed.
+ * Geometry: KH == KW == 4, stride 2, dilation 1; Ci a multiple of 8 (forward also 3, read as 4 with the fourth channel ignored);
+ *   Co a multiple of 8; any N: GCC_ERR_UNSUPPORTED otherwise.  c->pad other than 1 is GCC_ERR_BAD_ARG.  The plan is not read.
+ * Layout: ldx / xoff / ldy / yoff / ldy2 / y2off in floats, multiples of 4; pointers 16-byte aligned; a window must fit its ld;
+ *   y2's window must not share a float with y's; an unknown act (act2 with y2), a null pointer, transposed other than 0 / 1:
+ *   GCC_ERR_BAD_ARG.  Only channels [yoff, yoff + Co) of y and [y2off, y2off + Co) of y2 are written.
+ * Weights, transposed = 0: gcc_conv_eval_f32's packing, fp32 [Co][Kp] with k = (kh 4 + kw) Cip + ci from Conv2d's [Co][Ci][4][4].
+ *   transposed = 1: fp32 [4][Co][Kp], phase 2 (oh & 1) + (ow & 1) first; row co of phase (ph, pw) holds k = (2 th + tw) Ci + ci with
+ *   th, tw in {0, 1}, the element [ci][co][1 - ph + 2 th][1 - pw + 2 tw] of ConvTranspose2d's [Ci][Co][4][4] (tap (th, tw) reads
+ *   x at (ih, iw) = ((oh >> 1) + ph - th, (ow >> 1) + pw - tw)).
+ *   Kp = gcc_conv_eval_f32_unet_kp(Ci, transposed): 16 Cip or 4 Ci rounded up to 16, zero-filled beyond.
+ * Every refusal happens before anything is launched.  gcc_conv_eval_f32_unet_route: the tile (0 / 1 / 2 as above, chosen by the
+ *   rows of one launch slice: N (H / 2) (W / 2) forward, N H W per phase transposed) or the geometry's error; launches nothing. */
+typedef struct {
+    const float* scale;     /* [Co] or NULL (1): folded BatchNorm */
+    const float* shift;     /* [Co] or NULL (0): BatchNorm shift or the conv's bias */
+    float* y2;              /* NULL, or NHWC fp32 with the output's geometry: the second activated copy */
+    int ldy2, y2off;
+    int act, act2;          /* GCC_EVAL_ACT_NONE | _RELU | _LRELU | _TANH */
+    float slope;            /* negative-side slope of GCC_EVAL_ACT_LRELU (both outputs) */
+    int pad_;
+} gcc_eval_f32_unet_epilogue_t;
+int gcc_conv_eval_f32_unet(const gcc_conv_t* c, int transposed, const float* x, const float* w, float* y,
+                           const gcc_eval_f32_unet_epilogue_t* ep, gcc_stream_t stream);
+int gcc_conv_eval_f32_unet_route(const gcc_conv_t* c, int transposed);
+int gcc_conv_eval_f32_unet_kp(int Ci, int transposed);
 /* dst[n][c][h][w] = src[p][off + c] for c < C: the NHWC fp32 image of gcc_conv_eval_f32_act as the NCHW fp32 buffer the metric
  * kernels read (gcc_psnr_y_sse, gcc_ssim_y_sum).  off + C <= ld.  One launch. */
 int gcc_nhwc_f32_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, gcc_stream_t stream);
