@@ -100,6 +100,12 @@ class eval_f32_unet_epilogue_t(C.Structure):
                 ('act', C.c_int), ('act2', C.c_int), ('slope', C.c_float), ('pad_', C.c_int)]
 
 
+class eval_f32_resnet_epilogue_t(C.Structure):
+    """include/gcc_hip.h gcc_eval_f32_resnet_epilogue_t: the epilogue of gcc_conv_eval_f32_resnet (none / ReLU / tanh)"""
+    _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('act', C.c_int), ('pad_', C.c_int)]
+
+
+F32_RESNET_REFLECT, F32_RESNET_TRANSPOSED3 = 0, 1           # include/gcc_hip.h GCC_F32_RESNET_*
 FID_IN_BF16, FID_IN_U8, FID_IN_F32 = 0, 1, 2               # include/gcc_hip.h GCC_FID_IN_*
 POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2     # include/gcc_hip.h GCC_POOL3_*
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
@@ -248,6 +254,13 @@ PROTOTYPES = {
     'gcc_conv_eval_f32_unet': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(eval_f32_unet_epilogue_t), _P]),
     'gcc_conv_eval_f32_unet_route': (_I, [C.POINTER(conv_t), _I]),
     'gcc_conv_eval_f32_unet_kp': (_I, [_I, _I]),
+    'gcc_conv_eval_f32_resnet': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(eval_f32_resnet_epilogue_t), _P]),
+    'gcc_conv_eval_f32_resnet_route': (_I, [C.POINTER(conv_t), _I]),
+    'gcc_conv_eval_f32_resnet_kp': (_I, [_I, _I, _I]),
+    'gcc_dwconv3x3_reflect_f32': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    'gcc_inorm_f32_workspace': (_Z, [_I, _I, C.c_longlong]),
+    'gcc_inorm_stats_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    'gcc_inorm_apply_f32': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
     'gcc_nhwc_f32_to_nchw_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_nchw_f32_to_nhwc_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_image_to_u8': (_I, [_P, _I, _I, _Z, _P, _P]),

@@ -1398,8 +1398,26 @@ class MobileResnetEngine:
             self._ev_views, self._ev_key = v, key
         return self._ev_views
 
-    def infer_input(self, N, H, W):
-        """the slab's input view (NHWC bf16, in_nc channels): fill it, then infer(it)"""
+    PRECISIONS = ('bf16', 'fp32')
+
+    def _precision(self, precision, where):
+        if precision not in self.PRECISIONS:
+            raise _lib.GccError('MobileResnetEngine.%s: precision %r; expected one of %s' % (where, precision, ', '.join(self.PRECISIONS)))
+        return precision == 'fp32'
+
+    def eval_coeffs(self, precision='bf16'):
+        """what infer() reads, from the current parameters.  precision='bf16': the packings of repack().  precision='fp32': the
+        fp32 packings of all convolutions, depthwise ones included, and their biases, refreshed from the master weights into
+        buffers allocated at the first call (widths zero-padded to 8)."""
+        if self._precision(precision, 'eval_coeffs'):
+            return self._eval_coeffs_f32()
+        self.repack()
+
+    def infer_input(self, N, H, W, precision='bf16'):
+        """the slab's input view (NHWC bf16, in_nc channels; precision='fp32': NHWC fp32, the fp32 route's own slab): fill it, then
+        infer(it, precision)"""
+        if self._precision(precision, 'infer_input'):
+            return self._infer_bufs_f32(N, H, W).x_in
         return self._infer_bufs(N, H, W).x_in
 
     def _dw_in(self, slot, mode, dw, x, y, r=None, u_out=None, count_only=False):
@@ -1504,16 +1522,193 @@ class MobileResnetEngine:
         launches += conv(self.last, v.ypad, v.out, act=ACT_TANH)
         return launches if count_only else v.out
 
-    def infer(self, x):
+    def infer(self, x, precision='bf16'):
         """eval-mode generator forward of an NHWC bf16 batch x [N, in_nc, H, W] (H, W multiples of 4) with the packed weights of
         the last repack(): 4B + 14 launches for B residual blocks (infer_launches() says how many).  Returns the NHWC bf16 image
-        [N, out_nc, H, W], a view of the slab valid until the next call."""
+        [N, out_nc, H, W], a view of the slab valid until the next call.
+        precision='fp32': x and the image are NHWC fp32 and the program is the reference's own arithmetic -- fp32 weights and
+        activations, exact k-ordered sums, InstanceNorm statistics folded in double -- in 10B + 16 launches; needs
+        eval_coeffs('fp32')."""
+        if self._precision(precision, 'infer'):
+            return self._infer_f32(x)
         return self._infer(x)
 
-    def infer_launches(self, N, H, W):
+    def infer_launches(self, N, H, W, precision='bf16'):
         """kernel launches infer() makes for an N x H x W batch, from the library's route introspection (launches nothing and
         writes nothing: an image an earlier infer() returned stays valid)"""
+        if self._precision(precision, 'infer_launches'):
+            return self._infer_f32(self.infer_input(N, H, W, 'fp32'), count_only=True)
         return self._infer(self.infer_input(N, H, W), count_only=True)
+
+    # ---- the same network at the reference's own precision ----------------------------------------------------------------------
+    # fp32 packings of the master weights, biases and a slab of their own; every width is carried at the next multiple of 8 with
+    # zero weights and zero biases in the pad channels, which InstanceNorm, the activations and the depthwise convs keep at 0.
+    # Program: stem 3 x [conv, stats, apply + ReLU] | per block dw (+ its statistics), apply, pw1, stats, apply + ReLU, dw (+ its
+    # statistics), apply, pw2, stats, apply + residual | 2 x [transposed conv, stats, apply + ReLU] | reflect conv + bias + tanh:
+    # 10B + 16 launches.  The reflect and transposed convs are gcc_conv_eval_f32_resnet, the k3 s2 and 1 x 1 ones
+    # gcc_conv_eval_f32_act.  Nothing of self.ctx, self.gbuf or the bf16 slab is read or written.
+
+    def _eval_coeffs_f32(self):
+        L, E, dev = ops.ceil8, _lib, self.device
+        if getattr(self, '_ev32', None) is None:
+            if self.in_nc != 3 and self.in_nc % 8:
+                raise _lib.GccError('MobileResnetEngine: the fp32 route takes 3 input channels or a multiple of 8, not %d' % self.in_nc)
+            e = type('ResnetEval32', (), {})()
+            e.copies = []                                # (view of a packing, its parameter, how the parameter is viewed)
+            convs = self.stem + [c for b in self.blocks for c in (b.pw1, b.pw2)] + self.ups + [self.last]
+            e.bias = torch.zeros(sum(L(op.cols if op.transposed else op.rows) for op in convs), dtype=torch.float32, device=dev)
+            taken = [0]
+
+            def shift(op):
+                C8 = L(op.cols if op.transposed else op.rows)
+                v = e.bias[taken[0]:taken[0] + C8]
+                taken[0] += C8
+                if op.bias is not None:
+                    e.copies.append((v[:op.cols if op.transposed else op.rows], op.bias, lambda p: p))
+                return v
+
+            def plain(op):                               # gcc_conv_eval_f32's packing at padded widths
+                Ci8, Co8, k = L(op.cols), L(op.rows), op.k
+                kp = ops.lib().gcc_conv_eval_f32_kp(Ci8, k, k)
+                _lib.check(min(kp, 0), 'gcc_conv_eval_f32_kp')
+                w = torch.zeros((Co8, kp), dtype=torch.float32, device=dev)
+                e.copies.append((w[:, :k * k * Ci8].view(Co8, k, k, Ci8)[:op.rows, :, :, :op.cols], op.weight,
+                                 lambda p: p.permute(0, 2, 3, 1)))
+                return w, shift(op)
+
+            def reflect(op, Ci):
+                w, dst = ops.resnet_weights_f32(Ci, L(op.rows), E.F32_RESNET_REFLECT, op.k, dev)
+                e.copies.append((dst[:op.rows, :, :, :op.cols], op.weight, lambda p: p.permute(0, 2, 3, 1)))
+                return w, shift(op)
+
+            def transposed(op):
+                w, dst = ops.resnet_weights_f32(L(op.rows), L(op.cols), E.F32_RESNET_TRANSPOSED3, 3, dev)
+                for ph, d in enumerate(dst):
+                    for th, tw, kh, kw in ops.resnet_phase_taps(ph):
+                        e.copies.append((d[:op.cols, th, tw, :op.rows], op.weight, lambda p, kh=kh, kw=kw: p[:, :, kh, kw].t()))
+                return w, shift(op)
+
+            def depthwise(dw):
+                w, b = ops.pack_dw_f32(dw.weight, dw.bias, L(dw.C))
+                e.copies.append((w[:, :dw.C], dw.weight, lambda p: p.reshape(p.shape[0], 9).t()))
+                if dw.bias is not None:
+                    e.copies.append((b[:dw.C], dw.bias, lambda p: p))
+                return w, b
+
+            e.stem = [reflect(self.stem[0], 3 if self.in_nc == 3 else L(self.in_nc)), plain(self.stem[1]), plain(self.stem[2])]
+            e.blocks = [(depthwise(b.dw1), plain(b.pw1), depthwise(b.dw2), plain(b.pw2)) for b in self.blocks]
+            e.ups = [transposed(op) for op in self.ups]
+            e.last = reflect(self.last, L(self.last.cols))
+            self._ev32 = e
+        for dst, param, view in self._ev32.copies:       # strided both ways: no temporary
+            dst.copy_(view(param.detach()))
+
+    def _infer_bufs_f32(self, N, H, W):
+        """views of the fp32 slab for an N x H x W input, every one at its full padded width, and the InstanceNorm partials"""
+        L = ops.ceil8
+        h, w = H // 4, W // 4
+        tw = L(max([self.stem[2].rows] + [c for b in self.blocks for c in (b.dw1.C, b.pw2.rows)]))          # trunk width
+        mw = L(max([8] + [b.pw1.rows for b in self.blocks]))
+        cin = 4 if self.in_nc == 3 else L(self.in_nc)
+        shapes = [('x_in', cin, H, W)]
+        shapes += [('s_raw%d' % i, L(self.stem[i].rows), H >> i, W >> i) for i in range(3)]
+        shapes += [('s_act%d' % i, L(self.stem[i].rows), H >> i, W >> i) for i in range(2)]
+        shapes += [('u0', tw, h, w), ('u1', tw, h, w), ('d', max(tw, mw), h, w), ('n', max(tw, mw), h, w), ('p1', mw, h, w),
+                   ('r1', mw, h, w), ('p2', tw, h, w)]
+        shapes += [('t_raw%d' % i, L(self.ups[i].cols), H >> (1 - i), W >> (1 - i)) for i in range(2)]
+        shapes += [('t_act%d' % i, L(self.ups[i].cols), H >> (1 - i), W >> (1 - i)) for i in range(2)]
+        shapes += [('out', L(self.out_nc), H, W)]
+        total = sum(N * hh * ww * Cc for _, Cc, hh, ww in shapes)
+        if getattr(self, '_ev32_slab', None) is None or self._ev32_slab.numel() < total:
+            self._ev32_slab = self._ev32_views = None
+            self._ev32_slab = torch.zeros(total, dtype=torch.float32, device=self.device)
+        normed = [(Cc, hh * ww) for name, Cc, hh, ww in shapes if name[:5] in ('s_raw', 't_raw')] + [(max(tw, mw), h * w)]
+        ws_need = max(ops.inorm_f32_workspace_bytes(N, Cc, hw) for Cc, hw in normed) // 8
+        if getattr(self, '_ev32_ws', None) is None or self._ev32_ws.numel() < ws_need:
+            self._ev32_ws = None
+            self._ev32_ws = torch.empty(ws_need, dtype=torch.float64, device=self.device)
+        key = (N, H, W)
+        if getattr(self, '_ev32_views', None) is None or self._ev32_views.key != key:
+            v = type('ResnetInferBufs32', (), {})()
+            off = 0
+            for name, Cc, hh, ww in shapes:
+                setattr(v, name, self._ev32_slab[off:off + N * hh * ww * Cc].view(N, hh, ww, Cc).permute(0, 3, 1, 2))
+                off += N * hh * ww * Cc
+            v.x_in = v.x_in[:, :self.in_nc]
+            v.key = key
+            self._ev32_views = v
+        return self._ev32_views
+
+    def _infer_f32(self, x, count_only=False):
+        e = getattr(self, '_ev32', None)
+        if e is None:
+            raise _lib.GccError("MobileResnetEngine.infer: eval_coeffs('fp32') first")
+        N, _, H, W = x.shape
+        if H % 4 or W % 4:
+            raise _lib.GccError('MobileResnetEngine.infer: H, W must be multiples of 4')
+        v = self._infer_bufs_f32(N, H, W)
+        E, L, ws = _lib, ops.ceil8, self._ev32_ws
+        launches = 0
+
+        def count(n):
+            nonlocal launches
+            launches += n
+
+        def routed(r, name):
+            if count_only:
+                _lib.check(min(r, 0), name)
+            count(1)
+
+        def resnet(pack, kind, k, src, dst, act=E.EVAL_ACT_NONE):
+            routed(ops.conv_eval_f32_resnet(src, pack[0], dst.shape[1], kind, k, dst, shift=pack[1], act=act, route_only=count_only),
+                   'gcc_conv_eval_f32_resnet_route')
+
+        def plain(pack, k, stride, src, dst):
+            routed(ops.conv_eval_f32_act(src, pack[0], dst.shape[1], (k, k), (k // 2, k // 2), dst, stride=stride, shift=pack[1],
+                                         route_only=count_only), 'gcc_conv_eval_f32_act_route')
+
+        def depthwise(pack, src, dst):
+            if not count_only:
+                ops.dwconv_reflect_f32(src, pack[0], pack[1], dst, stats=ws)
+            count(1)
+
+        def inorm(src, dst, act=E.EVAL_ACT_NONE, residual=None, stats=True):
+            if not count_only:
+                if stats:
+                    ops.inorm_stats_f32(src, ws)
+                ops.inorm_apply_f32(src, dst, ws, act=act, residual=residual)
+            count(2 if stats else 1)
+
+        src = x
+        for i in range(3):
+            raw = getattr(v, 's_raw%d' % i)
+            if i == 0:
+                resnet(e.stem[0], E.F32_RESNET_REFLECT, 7, src, raw)
+            else:
+                plain(e.stem[i], 3, 2, src, raw)
+            dst = getattr(v, 's_act%d' % i) if i < 2 else v.u0[:, :L(self.stem[2].rows)]
+            inorm(raw, dst, act=E.EVAL_ACT_RELU)
+            src = dst
+        u, unext = v.u0, v.u1
+        for b, (dw1, pw1, dw2, pw2) in zip(self.blocks, e.blocks):
+            cin, cmid, cout = L(b.dw1.C), L(b.pw1.rows), L(b.pw2.rows)
+            depthwise(dw1, src[:, :cin], v.d[:, :cin])
+            inorm(v.d[:, :cin], v.n[:, :cin], stats=False)
+            plain(pw1, 1, 1, v.n[:, :cin], v.p1[:, :cmid])
+            inorm(v.p1[:, :cmid], v.r1[:, :cmid], act=E.EVAL_ACT_RELU)
+            depthwise(dw2, v.r1[:, :cmid], v.d[:, :cmid])
+            inorm(v.d[:, :cmid], v.n[:, :cmid], stats=False)
+            plain(pw2, 1, 1, v.n[:, :cmid], v.p2[:, :cout])
+            inorm(v.p2[:, :cout], unext[:, :cout], residual=src[:, :cout])
+            src = unext[:, :cout]
+            u, unext = unext, u
+        for i in range(2):
+            raw, dst = getattr(v, 't_raw%d' % i), getattr(v, 't_act%d' % i)
+            resnet(e.ups[i], E.F32_RESNET_TRANSPOSED3, 3, src, raw)
+            inorm(raw, dst, act=E.EVAL_ACT_RELU)
+            src = dst
+        resnet(e.last, E.F32_RESNET_REFLECT, 7, src, v.out, act=E.EVAL_ACT_TANH)
+        return launches if count_only else v.out[:, :self.out_nc]
 
     # ---------------------------------------------------------------------------------------
     def backward(self, c, g_feat=None, wgrad=True, need_dx=False):

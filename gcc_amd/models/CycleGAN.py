@@ -25,7 +25,7 @@ from .. import engine, ops
 from .._lib import GccError
 from ..utils import util
 from .DifferentiableOp import DifferentiableOP
-from .Pix2Pix import MobileResnetGenerator, _patchgan_tree, gen_precision
+from .Pix2Pix import MobileResnetGenerator, _patchgan_tree, gen_precision, resnet_infer_nhwc
 from ._base import ARCH_SLOTS, GANModelBase, _ChainWgrad
 from ._optim import HipAdam
 
@@ -359,7 +359,8 @@ class MobileCycleGANModel(GANModelBase):
         """one generator in eval mode on `real` through the fused inference path (MobileResnetEngine.infer): 'A' = netG_A
         (A -> B), 'B' = netG_B (B -> A).  real: NCHW fp32, or a dataset batch dict -- the generator's own domain is picked the
         way set_input picks real_A / real_B.  Uses the weights of the last finished optimizer step; touches no training buffer.
-        Returns an NHWC bf16 [N, 3, H, W] view valid until the next call of the same generator."""
+        Returns an NHWC bf16 [N, 3, H, W] view valid until the next call of the same generator -- an NHWC fp32 one with
+        GCC_RESNET_PRECISION=fp32 (Pix2Pix.resnet_precision; its packings are refreshed when the weights moved)."""
         if generator not in ('A', 'B'):
             raise ValueError("generator must be 'A' or 'B'")
         gen_precision(only_bf16='--model cyclegan')
@@ -367,15 +368,16 @@ class MobileCycleGANModel(GANModelBase):
             AtoB = self.opt.direction == 'AtoB'
             real = real[('A' if AtoB else 'B') if generator == 'A' else ('B' if AtoB else 'A')]
         real = real.to(self.device, torch.float32).contiguous()
-        N, _, H, W = real.shape
-        G = self.G[generator]
-        x = G.infer_input(N, H, W)
-        ops.nchw_to_nhwc(real, x, cfill=8)
-        return G.infer(x)
+        return resnet_infer_nhwc(self, self.G[generator], real)
 
     def infer(self, real, generator='A'):
         """infer_nhwc as NCHW fp32"""
-        return ops.nhwc_to_nchw(self.infer_nhwc(real, generator), 3)
+        image = self.infer_nhwc(real, generator)
+        return ops.nhwc_to_nchw_f32(image, Cc=3) if image.dtype is torch.float32 else ops.nhwc_to_nchw(image, 3)
+
+    def refresh_weights(self):
+        self._g_generation = getattr(self, '_g_generation', 0) + 1
+        super().refresh_weights()
 
     fake_A = property(lambda self: self._image('fake_A'))
     fake_B = property(lambda self: self._image('fake_B'))
@@ -503,6 +505,7 @@ class MobileCycleGANModel(GANModelBase):
         self.backward_G(ts)
         self._allreduce(self.optimizer_G)
         self.optimizer_G.step()          # L1_sparsity() (:548-569) is fused into the Adam kernel, per-tensor weights
+        self._g_generation = getattr(self, '_g_generation', 0) + 1
         for w in 'AB':
             self.G[w].repack()
             for t in self.T[w]:

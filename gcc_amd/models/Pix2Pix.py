@@ -261,6 +261,38 @@ def gen_precision(only_bf16=None):
     return precision
 
 
+RESNET_PRECISION_ENV = 'GCC_RESNET_PRECISION'
+
+
+def resnet_precision():
+    """the precision of a MobileResnet generator's inference path (Pix2PixModel.infer_nhwc with --backbone resnet,
+    MobileCycleGANModel.infer_nhwc) in gcc_amd.test and in the per-epoch mIoU and FID evaluations: the environment variable
+    GCC_RESNET_PRECISION, 'bf16' (the default) or 'fp32' (the reference's own arithmetic: MobileResnetEngine.infer(x, 'fp32'));
+    any other value raises GccError.  The one place that reads it, and only where a MobileResnet generator infers: U-Net, SAGAN
+    and SRGAN runs never look at it."""
+    precision = os.environ.get(RESNET_PRECISION_ENV) or 'bf16'
+    if precision not in GEN_PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (RESNET_PRECISION_ENV, precision, ', '.join(GEN_PRECISIONS)))
+    return precision
+
+
+def resnet_infer_nhwc(owner, G, real):
+    """G (a MobileResnetEngine) in eval mode on the NCHW fp32 batch `real` at resnet_precision(): the NHWC bf16 image, or the
+    NHWC fp32 one.  The fp32 packings are refreshed when owner._g_generation moved since this generator's last fp32 call."""
+    N, _, H, W = real.shape
+    precision = resnet_precision()
+    if precision == 'fp32':
+        done = owner.__dict__.setdefault('_ev_resnet_generation', {})
+        generation = getattr(owner, '_g_generation', 0)
+        if done.get(id(G)) != generation:
+            G.eval_coeffs('fp32')
+            done[id(G)] = generation
+        return G.infer(ops.nchw_to_nhwc_f32(real, G.infer_input(N, H, W, 'fp32')), 'fp32')
+    x = G.infer_input(N, H, W)
+    ops.nchw_to_nhwc(real, x, cfill=8)
+    return G.infer(x)
+
+
 # ------------------------------------------------------------------------------------------------
 class Pix2PixModel(GANModelBase):
     DISTILL_LOSSES = GANModelBase.DISTILL_LOSSES[:2]             # no 'L1' entry: G_L1 is always logged
@@ -447,18 +479,17 @@ class Pix2PixModel(GANModelBase):
         is picked by --direction as set_input does) through the fused inference path (UnetEngine.infer): an NHWC bf16
         [N, 3, H, W] view valid until the next call -- an NHWC fp32 one with GCC_GEN_PRECISION=fp32 (gen_precision).  Refreshes
         the eval-mode coefficients of that precision (one launch; fp32: and the fp32 weight packings) when the parameters or
-        running statistics changed since its last call.  --backbone resnet: MobileResnetEngine.infer, bf16 only."""
+        running statistics changed since its last call.  --backbone resnet: MobileResnetEngine.infer at the precision
+        GCC_RESNET_PRECISION names (resnet_precision); GCC_GEN_PRECISION=fp32 is refused there as before."""
         if isinstance(real, dict):
             real = real['A' if self.opt.direction == 'AtoB' else 'B']
         real = real.to(self.device, torch.float32).contiguous()
         N, _, H, W = real.shape
         if self.resnet:
             gen_precision(only_bf16='--backbone resnet')
-            # InstanceNorm without running statistics: nothing to refresh (MobileResnetEngine.infer)
+            # InstanceNorm without running statistics: the bf16 route has nothing to refresh (MobileResnetEngine.infer)
             self.finish_G_update()
-            x = self.G.infer_input(N, H, W)
-            ops.nchw_to_nhwc(real, x, cfill=8)
-            return self.G.infer(x)
+            return resnet_infer_nhwc(self, self.G, real)
         precision = gen_precision()
         self.finish_G_update()
         done = self.__dict__.setdefault('_ev_generation', {})

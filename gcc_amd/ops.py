@@ -819,6 +819,118 @@ def conv_eval_f32_unet(x, w, Co, out, transposed=False, scale=None, shift=None, 
     return out
 
 
+def resnet_weights_f32(Ci, Co, kind, k, device):
+    """(w, dst) for gcc_conv_eval_f32_resnet: the zero-filled packed buffer of a layer of Ci -> Co channels (each a multiple of 8, or
+    Ci == 3 for REFLECT) and the strided view(s) of it that dst.copy_(src) fills from the master weights --
+    F32_RESNET_REFLECT: w [Co][Kp], one view [Co, k, k, Ci] to fill from weight.permute(0, 2, 3, 1) of Conv2d's [Co, Ci, k, k];
+    F32_RESNET_TRANSPOSED3: w [4][Co][Kp], per phase p = 2 ph + pw one view [Co, 1 + ph, 1 + pw, Ci] (taps th, tw) to fill from
+    weight[:, :, kh, kw].t() of ConvTranspose2d's [Ci, Co, 3, 3], tap by tap (resnet_phase_taps; include/gcc_hip.h).
+    Views of fewer channels (dst[..., :ci], dst[:co]) leave the pad channels zero."""
+    kp = lib().gcc_conv_eval_f32_resnet_kp(Ci, kind, k)
+    check(min(kp, 0), 'gcc_conv_eval_f32_resnet_kp')
+    cip = 4 if Ci == 3 else Ci
+    if kind == _lib.F32_RESNET_REFLECT:
+        w = torch.zeros((Co, kp), dtype=torch.float32, device=device)
+        return w, w[:, :k * k * cip].view(Co, k, k, cip)[..., :Ci]
+    w = torch.zeros((4, Co, kp), dtype=torch.float32, device=device)
+    return w, [w[p, :, :(1 + (p >> 1)) * (1 + (p & 1)) * Ci].view(Co, 1 + (p >> 1), 1 + (p & 1), Ci) for p in range(4)]
+
+
+def resnet_phase_taps(p):
+    """(th, tw, kh, kw) of the taps of output parity phase p = 2 ph + pw of ConvTranspose2d(k3, s2, p1, output_padding 1), in the
+    phase's tap order: an even coordinate takes kernel element 1, an odd one elements 2 then 0"""
+    ks = lambda odd: (2, 0) if odd else (1,)
+    return [(th, tw, kh, kw) for th, kh in enumerate(ks(p >> 1)) for tw, kw in enumerate(ks(p & 1))]
+
+
+def pack_weights_f32_resnet(master, kind):
+    """the packing gcc_conv_eval_f32_resnet reads, from Conv2d's [Co, Ci, k, k] or ConvTranspose2d's [Ci, Co, 3, 3]"""
+    m = master.detach().float()
+    if kind == _lib.F32_RESNET_REFLECT:
+        w, dst = resnet_weights_f32(m.shape[1], m.shape[0], kind, m.shape[2], m.device)
+        dst.copy_(m.permute(0, 2, 3, 1))
+        return w
+    w, dst = resnet_weights_f32(m.shape[0], m.shape[1], kind, 3, m.device)
+    for p, d in enumerate(dst):
+        for th, tw, kh, kw in resnet_phase_taps(p):
+            d[:, th, tw, :].copy_(m[:, :, kh, kw].t())
+    return w
+
+
+def conv_eval_f32_resnet(x, w, Co, kind, k, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, route_only=False):
+    """a MobileResnet layer in fp32 (gcc_conv_eval_f32_resnet): out = act(scale[c] conv(x, w) + shift[c]), act none / ReLU / tanh.
+    kind F32_RESNET_REFLECT: Conv2d(k) behind ReflectionPad2d(k // 2), out [N, Co, H, W]; F32_RESNET_TRANSPOSED3:
+    ConvTranspose2d(k3, s2, p1, output_padding 1), out [N, Co, 2 H, 2 W].  NHWC fp32 views; w from resnet_weights_f32.  One launch,
+    no workspace.  route_only: the tile the library takes (>= 0) or its error for the geometry, nothing launched."""
+    xp, N, Ci, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    tr = kind == _lib.F32_RESNET_TRANSPOSED3
+    d = conv_desc(N, H, W, Ci, Co, k, 2 if tr else 1, 1 if tr else 0, ldx, ldy)
+    if route_only:
+        return lib().gcc_conv_eval_f32_resnet_route(C.byref(d), kind)
+    ep = _lib.eval_f32_resnet_epilogue_t(_p(scale), _p(shift), act, 0)
+    check(lib().gcc_conv_eval_f32_resnet(C.byref(d), kind, xp, w.data_ptr(), yp, C.byref(ep), stream()), 'gcc_conv_eval_f32_resnet')
+    return out
+
+
+def pack_dw_f32(weight, bias, C8=None, out=None):
+    """(w [9][C8], b [C8]) fp32 of a depthwise Conv2d(C, C, 3, groups=C)'s weight [C, 1, 3, 3] and bias [C] or None, tap-major and
+    zero-padded to C8 channels: what gcc_dwconv3x3_reflect_f32 reads.  out: the (w, b) of an earlier call, refilled in place."""
+    Cc = weight.shape[0]
+    C8 = C8 or (Cc + 3) // 4 * 4
+    if out is None:
+        out = (torch.zeros((9, C8), dtype=torch.float32, device=weight.device), torch.zeros(C8, dtype=torch.float32, device=weight.device))
+    out[0][:, :Cc].copy_(weight.detach().reshape(Cc, 9).t())
+    if bias is not None:
+        out[1][:Cc].copy_(bias.detach())
+    return out
+
+
+def inorm_f32_workspace_bytes(N, Cc, HW):
+    """bytes of InstanceNorm partials for [N, Cc, HW] (gcc_inorm_f32_workspace)"""
+    return lib().gcc_inorm_f32_workspace(N, Cc, HW)
+
+
+def _inorm_f32_ws(ws, N, Cc, HW, device):
+    if ws is None:
+        ws = workspace(inorm_f32_workspace_bytes(N, Cc, HW), device, 'inorm_f32')
+    return ws, ws.numel() * ws.element_size()
+
+
+def dwconv_reflect_f32(x, w, b, out, stats=None):
+    """out = depthwise 3 x 3 conv of ReflectionPad2d(1)(x) + b (gcc_dwconv3x3_reflect_f32): NHWC fp32 views of C channels (a multiple
+    of 4), (w, b) from pack_dw_f32.  stats: None, or the workspace tensor that receives the InstanceNorm partials of out in the same
+    launch (inorm_apply_f32 can follow).  One launch."""
+    xp, N, Cc, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    sb = stats.numel() * stats.element_size() if stats is not None else 0
+    check(lib().gcc_dwconv3x3_reflect_f32(xp, ldx, yp, ldy, w.data_ptr(), b.data_ptr(), N, H, W, Cc, _p(stats), sb, stream()),
+          'gcc_dwconv3x3_reflect_f32')
+    return out
+
+
+def inorm_stats_f32(x, ws=None):
+    """the InstanceNorm partials of an NHWC fp32 view x (gcc_inorm_stats_f32) into ws (None: the device's shared workspace);
+    returns ws.  One launch."""
+    xp, N, Cc, H, W, ldx = geom_f32(x)
+    ws, nbytes = _inorm_f32_ws(ws, N, Cc, H * W, x.device)
+    check(lib().gcc_inorm_stats_f32(xp, ldx, N, H, W, Cc, ws.data_ptr(), nbytes, stream()), 'gcc_inorm_stats_f32')
+    return ws
+
+
+def inorm_apply_f32(x, out, ws, act=_lib.EVAL_ACT_NONE, residual=None, eps=1e-5):
+    """out = act(InstanceNorm(x)) + residual from the partials in ws (gcc_inorm_apply_f32): act none / ReLU, the residual added
+    after the activation.  NHWC fp32 views; out may be x.  One launch."""
+    xp, N, Cc, H, W, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(out)
+    rp, ldr = None, 0
+    if residual is not None:
+        rp, _, _, _, _, ldr = geom_f32(residual)
+    check(lib().gcc_inorm_apply_f32(xp, ldx, yp, ldy, rp, ldr, N, H, W, Cc, act, eps, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                    stream()), 'gcc_inorm_apply_f32')
+    return out
+
+
 def nhwc_to_nchw_f32(src, out=None, Cc=None):
     """contiguous NCHW fp32 [N, Cc, H, W] of the first Cc channels of an NHWC fp32 view (gcc_nhwc_f32_to_nchw_f32)"""
     sp, N, C0, H, W, ld = geom_f32(src)

@@ -4,6 +4,7 @@ over the test split, write PNGs under <checkpoints_dir>/<name>/test_results with
 Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
   pix2pix   phase val, batch 1, serial, no flip, load_size 256; the generator through Pix2PixModel.infer_nhwc (fused eval path)
             at the precision GCC_GEN_PRECISION names (bf16, the default, or fp32: the reference's own; U-Net only);
+            --backbone resnet and cyclegan: MobileResnetEngine.infer at the precision GCC_RESNET_PRECISION names;
             on a Cityscapes root with table.txt and a segmenter at --drn_path (the reference's .pth or TorchScript): prints the mIoU afterwards
   pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
             --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written)
@@ -174,8 +175,13 @@ def run(opt, model):
         else:
             fid = fid_eval.fid_evaluator(inception).scorer(model, topt)
     if opt.model == 'pix2pix':
-        from .models.Pix2Pix import gen_precision
-        print('generator precision: %s' % gen_precision(only_bf16='--backbone resnet' if model.resnet else None))
+        from .models.Pix2Pix import gen_precision, resnet_precision
+        precision = gen_precision(only_bf16='--backbone resnet' if model.resnet else None)
+        print('generator precision: %s' % (resnet_precision() if model.resnet else precision))
+    elif opt.model == 'cyclegan':
+        from .models.Pix2Pix import resnet_precision
+        if resnet_precision() != 'bf16':         # the default run's lines stay as they were
+            print('generator precision: %s' % resnet_precision())
     dataset = create_dataset(topt, model.device)
     if scorer is not None and getattr(dataset, 'paths', None) is not None:
         scorer.prefetch(dataset.paths)

@@ -603,6 +603,70 @@ int gcc_conv_eval_f32_unet(const gcc_conv_t* c, int transposed, const float* x, 
                            const gcc_eval_f32_unet_epilogue_t* ep, gcc_stream_t stream);
 int gcc_conv_eval_f32_unet_route(const gcc_conv_t* c, int transposed);
 int gcc_conv_eval_f32_unet_kp(int Ci, int transposed);
+/* gcc_conv_eval_f32_resnet: the MobileResnet generator's reflection-padded and transposed convolutions at the reference's own
+ * precision (engine.MobileResnetEngine.infer, precision 'fp32'; models/Pix2Pix.py:132-265, models/CycleGAN.py:77-138;
+ * gcc_amd/csrc/resnet_f32.hip).  A kernel of its own with gcc_conv_eval_f32's tiles, matrix instruction and ONE order of K (walked
+ * in steps of 16, every product an fmaf onto the running sum; no split-K, no atomics, no workspace): an output element depends on
+ * neither its batch nor its tile.  One launch.  Added without a GCC_HIP_ABI bump (additions only); the four entries above keep
+ * their text and their bits.  The generator's other convolutions (k3 s2 p1, 1 x 1) run on gcc_conv_eval_f32_act.
+ *     y[p][c] = act(fmaf(acc, scale[c], shift[c]))      act: GCC_EVAL_ACT_NONE | _RELU | _TANH (the device library's tanhf)
+ * The descriptor is the LAYER's: c->H, c->W, c->Ci, c->ldx, c->xoff describe the input x; c->Co, c->ldy, c->yoff the output y.
+ * kind = GCC_F32_RESNET_REFLECT: Conv2d(k, stride 1, padding 0) behind ReflectionPad2d(k / 2), y is [N][H][W].  The padding is
+ *   index arithmetic in the gather: a tap at ih = oh - k / 2 + kh < 0 reads row -ih, one at ih >= H reads row 2 (H - 1) - ih; iw
+ *   alike.  No padded copy of the map exists.  KH == KW in {7, 3}, stride 1, Ci == 3 (read as 4 with the fourth channel ignored)
+ *   or a multiple of 8: GCC_ERR_UNSUPPORTED otherwise.  c->pad other than 0 (the conv has none of its own), H or W <= k / 2:
+ *   GCC_ERR_BAD_ARG.  Weights: gcc_conv_eval_f32's packing, fp32 [Co][Kp] with k = (kh KW + kw) Cip + ci.
+ * kind = GCC_F32_RESNET_TRANSPOSED3: ConvTranspose2d(k3, s2, p1, output_padding 1), y is [N][2 H][2 W] (H, W >= 1).  Each of the
+ *   four output parity phases (ph, pw) = (oh & 1, ow & 1) is a gather over x stored at pixel stride 2; nothing is zero-stuffed.
+ *   An even oh takes kh = 1 from ih = oh / 2; an odd oh takes kh = 2 from ih = (oh - 1) / 2 and kh = 0 from ih = (oh + 1) / 2
+ *   when that is < H; ow alike.  The phases have 1, 2, 2 and 4 taps and each walks only its own K = (1 + ph) (1 + pw) Ci, rounded
+ *   up to 16.  KH == KW == 3, stride 2, Ci a multiple of 8: GCC_ERR_UNSUPPORTED otherwise; c->pad other than 1: GCC_ERR_BAD_ARG.
+ *   Weights: fp32 [4][Co][Kp], phase 2 ph + pw first, Kp = 4 Ci rounded up to 16 for every phase; row co of phase (ph, pw) holds
+ *   k = (th (1 + pw) + tw) Ci + ci for th <= ph, tw <= pw: the element [ci][co][ph ? 2 - 2 th : 1][pw ? 2 - 2 tw : 1] of
+ *   ConvTranspose2d's [Ci][Co][3][3] (tap (th, tw) reads x at ((oh >> 1) + th, (ow >> 1) + tw)); zeros from the phase's K to Kp.
+ * Both kinds: Co a multiple of 8 (GCC_ERR_UNSUPPORTED).  Layout: ldx / xoff / ldy / yoff in floats, multiples of 4; pointers
+ *   16-byte aligned; a window must fit its ld; an unknown kind or act, a null pointer: GCC_ERR_BAD_ARG.  Only channels
+ *   [yoff, yoff + Co) of y are written.  Every refusal happens before anything is launched.
+ * gcc_conv_eval_f32_resnet_route: the tile (0 / 1 / 2 as above, chosen by N H W rows) or the geometry's error; launches nothing.
+ * gcc_conv_eval_f32_resnet_kp(Ci, kind, k): Kp of the packing (k: 7 or 3 for REFLECT, 3 for TRANSPOSED3). */
+enum { GCC_F32_RESNET_REFLECT = 0, GCC_F32_RESNET_TRANSPOSED3 = 1 };
+typedef struct {
+    const float* scale;     /* [Co] or NULL (1) */
+    const float* shift;     /* [Co] or NULL (0): the conv's bias */
+    int act;                /* GCC_EVAL_ACT_NONE | _RELU | _TANH */
+    int pad_;
+} gcc_eval_f32_resnet_epilogue_t;
+int gcc_conv_eval_f32_resnet(const gcc_conv_t* c, int kind, const float* x, const float* w, float* y,
+                             const gcc_eval_f32_resnet_epilogue_t* ep, gcc_stream_t stream);
+int gcc_conv_eval_f32_resnet_route(const gcc_conv_t* c, int kind);
+int gcc_conv_eval_f32_resnet_kp(int Ci, int kind, int k);
+/* gcc_dwconv3x3_reflect_f32: depthwise 3 x 3 convolution behind ReflectionPad2d(1) with bias, NHWC fp32 (x, y: pointers to the
+ * first channel of the window, ldx / ldy >= C in floats, multiples of 4, 16-byte aligned; C a multiple of 4; H, W >= 2).
+ *     y[p][c] = fmaf chain: acc = bias[c]; acc = fmaf(x[mirror(oh - 1 + kh, ow - 1 + kw)][c], w[kh 3 + kw][c], acc), kh, kw ascending
+ * w: fp32 [9][C] (tap-major), bias: fp32 [C], both packed by the host.  One thread's outputs are 4 channels of a pixel.
+ * stats: NULL, or gcc_inorm_f32_workspace(N, C, H W) bytes that receive the InstanceNorm partials of y in gcc_inorm_stats_f32's
+ *   format from this same launch (a workgroup owns whole chunks of one image's pixels), so that gcc_inorm_apply_f32 can follow
+ *   at once.  One launch.  GCC_ERR_WORKSPACE: stats_bytes too small.  Every refusal happens before anything is launched. */
+int gcc_dwconv3x3_reflect_f32(const float* x, int ldx, float* y, int ldy, const float* w, const float* bias, int N, int H, int W,
+                              int C, void* stats, size_t stats_bytes, gcc_stream_t stream);
+/* InstanceNorm2d(affine = False) on NHWC fp32 in two launches, with no launch waiting for a workgroup of its own grid.
+ * gcc_inorm_stats_f32: a plane of H W pixels is cut into chunks of consecutive pixels whose size depends on H W alone (not on N or
+ *   on the grid); per (image, chunk, channel) it writes the chunk's mean and M2 = sum (x - mean)^2 as doubles, [N][chunks][2][C],
+ *   formed from sums about a pivot (the chunk's first pixel) -- never E[x^2] - E[x]^2 of the raw values.  The workspace is the
+ *   caller's, gcc_inorm_f32_workspace(N, C, H W) bytes, 16-byte aligned; there is NO zero-fill contract: every partial the apply
+ *   launch reads was written by the stats launch before it.
+ * gcc_inorm_apply_f32: every workgroup folds the partials of its channels in chunk order, in double (mean = sum n_k mean_k / HW,
+ *   M2 = sum M2_k + n_k (mean_k - mean)^2), forms rstd = 1 / sqrt(M2 / HW + eps) (biased variance) and writes
+ *       y = act((x - mean) rstd) + residual        act: GCC_EVAL_ACT_NONE | _RELU; the residual (NULL: none) is added AFTER the
+ *   activation, as gcc_inorm_fwd does.  The difference and the product are formed in double and rounded once.  y may be x.
+ *   An all-zero channel (a pad channel) comes out as zeros.  There is no finalize launch between the two.
+ * x, y, residual: pointers to the first channel of the window, ld >= C in floats, multiples of 4, 16-byte aligned; C a multiple of
+ *   4 (GCC_ERR_UNSUPPORTED).  GCC_ERR_WORKSPACE: workspace_bytes too small.  Every refusal happens before anything is launched. */
+size_t gcc_inorm_f32_workspace(int N, int C, long long HW);
+int gcc_inorm_stats_f32(const float* x, int ldx, int N, int H, int W, int C, void* workspace, size_t workspace_bytes,
+                        gcc_stream_t stream);
+int gcc_inorm_apply_f32(const float* x, int ldx, float* y, int ldy, const float* residual, int ld_residual, int N, int H, int W,
+                        int C, int act, float eps, const void* workspace, size_t workspace_bytes, gcc_stream_t stream);
 /* dst[n][c][h][w] = src[p][off + c] for c < C: the NHWC fp32 image of gcc_conv_eval_f32_act as the NCHW fp32 buffer the metric
  * kernels read (gcc_psnr_y_sse, gcc_ssim_y_sum).  off + C <= ld.  One launch. */
 int gcc_nhwc_f32_to_nchw_f32(const float* src, float* dst, int N, int C, int H, int W, int ld, int off, gcc_stream_t stream);
