@@ -15,7 +15,7 @@ mkdir -p build
 # GCC_BUILD_FORCE=1 (set by __graft_entry__.build()): recompile every source, whatever the timestamps of shipped objects say
 if [ "${GCC_BUILD_FORCE:-0}" = "1" ]; then rm -f build/*.o $OUT $OUT_DIAG; fi
 stale() {   # object, source
-  [ ! -f $1 ] || [ $2 -nt $1 ] || [ common.hpp -nt $1 ] || [ igemm_common.hpp -nt $1 ] || [ igemm_kernel_body.inc -nt $1 ] || [ ../../include/gcc_hip.h -nt $1 ]
+  [ ! -f $1 ] || [ $2 -nt $1 ] || [ common.hpp -nt $1 ] || [ igemm_common.hpp -nt $1 ] || [ igemm_kernel_body.inc -nt $1 ] || [ conv_f32_tile.hpp -nt $1 ] || [ conv_f32_tile_body.inc -nt $1 ] || [ ../../include/gcc_hip.h -nt $1 ]
 }
 pids=()
 for f in $SRCS; do

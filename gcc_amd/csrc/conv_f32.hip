@@ -1,37 +1,24 @@
-// Inference convolution in fp32 on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain,
-// at 1/16 of the bf16 MFMA rate): gcc_conv_eval_f32, the evaluator networks at the reference's own precision
-// (gcc_amd/metric/drn_seg.py, precision 'fp32'), and gcc_conv_eval_f32_ex, the same kernel with KH, KW and the two paddings
-// independent (gcc_amd/metric/inception_fid.py, precision 'fp32': 5 x 5, (1, 7) / (7, 1), padding 0).
+// Inference convolution in fp32 on the f32-input matrix instruction: five entries, one tile (conv_f32_tile.hpp: the implicit GEMM,
+// its LDS layout, its k loop and the single order of K).  A kernel here is its gather and its store, as macros, around the one
+// body text (conv_f32_tile_body.inc).
 //
-// Implicit GEMM: M = N Ho Wo output pixels, N = Co, K = KH KW Cip (Cip = Ci, or 4 for the 3-channel stem).  A workgroup of four
-// waves owns one BM x BN output tile and walks ALL of K in steps of 16: no split-K, no atomics, no inter-workgroup state.
-//   A tile  gathered from NHWC fp32, 16 bytes (4 channels of one tap) per load; taps outside the image, rows beyond M and k
-//           beyond KH KW Cip are zeros; stride and dilation are index arithmetic
-//   B tile  rows of the packed weights [Co][Kp] (k contiguous, zero-filled to Kp = ceil16(K)); rows beyond Co are zeros
-//   LDS     As[row][16 + 4], Bs[col][16 + 4] floats, two stages (40 KB for the largest tile).  A lane reads its row's k-half
-//           (4 floats at 8 g + 4 (lane >> 5)) with one ds_read_b128; the row stride of 20 dwords puts the 16 lanes of every
-//           ds_read_b128 lane group on 16 distinct 4-bank spans of the 64 banks
-//   MFMA    32x32x2: lane l supplies A[row l & 31][k half l >> 5] and B[k half l >> 5][col l & 31], so instruction e of half-step
-//           g multiplies k = 8 g + e and 8 g + 4 + e.  The order of K is the same for every tile shape, every pixel, every batch.
-//   C       col = lane & 31 (a channel: 32 lanes store 128 contiguous bytes), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-// The next step's global loads are issued into registers before the current step's MFMAs and stored to the other LDS stage behind
-// them: one barrier per step.
-//
-// gcc_conv_eval_f32_act is the same kernel (EXT) with sides up to 9, PReLU (a device slope) and tanh in the epilogue, and an
-// optional PixelShuffle(2) store: SRResNet at the reference's own precision (engine.SRResNetEngine.infer, precision 'fp32').  With
-// the shuffle a 32-lane store group (32 consecutive channels of one pixel) puts 8 consecutive floats on each of the 4 sub-pixels.
-//
-// gcc_conv_eval_f32_unet is a second kernel with the same tiles, LDS layout, MFMA loop and order of K (conv_f32_unet_kernel; the
-// kernel above keeps its text and its bits): the U-Net generator's k4 s2 p1 layers at the reference's own precision
-// (engine.UnetEngine.infer, precision 'fp32').  Forward it gathers the 16 taps of Conv2d; transposed, blockIdx.z is one of the four
-// output parity phases, each a 2 x 2-tap gather over the input (K = 4 Ci) whose tile is stored at pixel stride 2.  The epilogue
-// writes up to two activated copies of fmaf(acc, scale, shift): none / ReLU / LeakyReLU (a host slope) / tanh.
-#include "common.hpp"
+// conv_f32_kernel   Conv2d with zero padding; stride and dilation are index arithmetic, taps outside the image are zeros
+//   gcc_conv_eval_f32      square 1 / 3 / 7 kernels with "same" padding, residual and ReLU: the evaluator networks at the
+//                          reference's own precision (gcc_amd/metric/drn_seg.py, precision 'fp32')
+//   gcc_conv_eval_f32_ex   KH, KW and the two paddings independent (gcc_amd/metric/inception_fid.py, precision 'fp32': 5 x 5,
+//                          (1, 7) / (7, 1), padding 0)
+//   gcc_conv_eval_f32_act  (EXT) sides up to 9, PReLU (a device slope) and tanh in the epilogue, and an optional PixelShuffle(2)
+//                          store: SRResNet at the reference's own precision (engine.SRResNetEngine.infer, precision 'fp32').  With
+//                          the shuffle a 32-lane store group (32 consecutive channels of one pixel) puts 8 consecutive floats on
+//                          each of the 4 sub-pixels.
+// conv_f32_unet_kernel   gcc_conv_eval_f32_unet: the U-Net generator's k4 s2 p1 layers at the reference's own precision
+//   (engine.UnetEngine.infer, precision 'fp32').  Forward it gathers the 16 taps of Conv2d; transposed, blockIdx.z is one of the
+//   four output parity phases, each a 2 x 2-tap gather over the input (K = 4 Ci) whose tile is stored at pixel stride 2.  The store
+//   writes up to two activated copies of fmaf(acc, scale, shift): none / ReLU / LeakyReLU (a host slope) / tanh.
+// The fifth entry, gcc_conv_eval_f32_resnet, is in resnet_f32.hip.
+#include "conv_f32_tile.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-constexpr int CF_BK = 16, CF_LDK = CF_BK + 4, CF_THREADS = 256;
 
 struct ConvF32Args {
     const float* x; const float* w; float* y;
@@ -42,145 +29,60 @@ struct ConvF32Args {
     const float* slope; int act, shuffle;           // EXT only (gcc_conv_eval_f32_act)
 };
 
-// EXT = false is the kernel of gcc_conv_eval_f32 / _ex as it was; EXT = true has the epilogue of gcc_conv_eval_f32_act
+// row m is output pixel (n, oh, ow); tap = kh KW + kw reads (oh stride - pad_h + kh dil, ow stride - pad_w + kw dil), zeros outside the
+// map.  The store is act(z + residual); EXT = false is that of gcc_conv_eval_f32 / _ex, EXT = true that of gcc_conv_eval_f32_act.
+// a: the kernel's ConvF32Args in each of them.
+#define CF_ROW(m, ih0, iw0, nb)                                                                        \
+    const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;                                                   \
+    const int n = fdiv(q, a.dHo), oh = q - n * a.Ho;                                                   \
+    ih0 = oh * a.stride - a.pad_h; iw0 = ow * a.stride - a.pad_w; nb = n * a.H * a.W
+#define CF_TAP(k4)                                                                                     \
+    const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;                                           \
+    const int kh = fdiv(tap, a.dKW), kw = tap - kh * a.KW;                                             \
+    const bool kok = k4 < a.Kreal;                                                                     \
+    const int dh = kh * a.dil, dw = kw * a.dil
+// the fetch of a zero-padded map (the U-Net's too); the stem's pad channel, whatever it holds, is not an input
+#define CF_FETCH_PADDED(v, ih0, iw0, nb)                                                               \
+    const int ih = ih0 + dh, iw = iw0 + dw;                                                            \
+    if (kok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {                         \
+        v = *(const f32x4*)(a.x + (size_t)(nb + ih * a.W + iw) * a.ldx + a.xoff + ci);                 \
+        if (a.Ci == 3) v[3] = 0.f;                                                                     \
+    }
+// PReLU's slope: one device load per thread
+#define CF_STORE_SETUP                                                                                 \
+    float slope = 0.f;                                                                                 \
+    if (EXT && a.act == GCC_EVAL_ACT_PRELU) slope = *a.slope
+// nn.PixelShuffle(2): channel co of pixel (n, oh, ow) is channel co >> 2 of pixel (2 oh + bit 1, 2 ow + bit 0); q = n Ho + oh
+#define CF_STORE(m, co, z)                                                                             \
+    float v = z;                                                                                       \
+    if (a.res) v += a.res[(size_t)m * a.ldr + a.roff + co];                                            \
+    if (!EXT) {                                                                                        \
+        if (a.relu) v = v < 0.f ? 0.f : v;                                                             \
+        a.y[(size_t)m * a.ldy + a.yoff + co] = v;                                                      \
+    } else {                                                                                           \
+        if (a.act == GCC_EVAL_ACT_RELU) v = v < 0.f ? 0.f : v;                                         \
+        else if (a.act == GCC_EVAL_ACT_PRELU) v = v >= 0.f ? v : __fmul_rn(slope, v);                  \
+        else if (a.act == GCC_EVAL_ACT_TANH) v = tanhf(v);                                             \
+        if (!a.shuffle) {                                                                              \
+            a.y[(size_t)m * a.ldy + a.yoff + co] = v;                                                  \
+        } else {                                                                                       \
+            const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;                                           \
+            const size_t p = ((size_t)q * 2 + ((co >> 1) & 1)) * ((size_t)a.Wo * 2) + 2 * ow + (co & 1); \
+            a.y[p * a.ldy + a.yoff + (co >> 2)] = v;                                                   \
+        }                                                                                              \
+    }
 template <int MI, int NI, int WM, int WN, bool EXT>
 __global__ __launch_bounds__(CF_THREADS) void conv_f32_kernel(ConvF32Args a) {
-    static_assert(WM * WN == 4, "four waves");
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    constexpr int A_PER = BM * 4 / CF_THREADS, B_PER = (BN * 4 + CF_THREADS - 1) / CF_THREADS;
-    __shared__ __attribute__((aligned(16))) float As[2][BM * CF_LDK];
-    __shared__ __attribute__((aligned(16))) float Bs[2][BN * CF_LDK];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int chunk = t & 3;                        // the thread's 4 floats of a 16-float k step, for its A rows and its B rows
-
-    // the thread's A rows: output pixel -> (image base, first tap's input row / column); a row beyond M never passes the range test
-    int ih0[A_PER], iw0[A_PER], nb[A_PER];
-#pragma unroll
-    for (int i = 0; i < A_PER; i++) {
-        const int m = m0 + ((t + i * CF_THREADS) >> 2);
-        if (m < a.M) {
-            const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;
-            const int n = fdiv(q, a.dHo), oh = q - n * a.Ho;
-            ih0[i] = oh * a.stride - a.pad_h; iw0[i] = ow * a.stride - a.pad_w; nb[i] = n * a.H * a.W;
-        } else {
-            ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
-        }
-    }
-    const float* wrow[B_PER];
-#pragma unroll
-    for (int i = 0; i < B_PER; i++) {
-        const int idx = t + i * CF_THREADS, co = n0 + (idx >> 2);
-        wrow[i] = (idx < BN * 4 && co < a.Co) ? a.w + (size_t)co * a.Kp + chunk * 4 : nullptr;
-    }
-
-    f32x4 ra[A_PER], rb[B_PER];
-    auto load = [&](int kt) {
-        const int k4 = kt * CF_BK + chunk * 4;
-        const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;
-        const int kh = fdiv(tap, a.dKW), kw = tap - kh * a.KW;
-        const bool kok = k4 < a.Kreal;
-        const int dh = kh * a.dil, dw = kw * a.dil;
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) {
-            const int ih = ih0[i] + dh, iw = iw0[i] + dw;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (kok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-                v = *(const f32x4*)(a.x + (size_t)(nb[i] + ih * a.W + iw) * a.ldx + a.xoff + ci);
-                if (a.Ci == 3) v[3] = 0.f;           // the stem's pad channel: whatever it holds, it is not an input
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (wrow[i]) v = *(const f32x4*)(wrow[i] + kt * CF_BK);
-            rb[i] = v;
-        }
-    };
-    auto stage = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) *(f32x4*)&As[s][((t + i * CF_THREADS) >> 2) * CF_LDK + chunk * 4] = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            const int idx = t + i * CF_THREADS;
-            if (idx < BN * 4) *(f32x4*)&Bs[s][(idx >> 2) * CF_LDK + chunk * 4] = rb[i];
-        }
-    };
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[mi][ni][r] = 0.f;
-
-    const int nk = a.Kp / CF_BK;
-    const int arow = (wm * MI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
-    const int brow = (wn * NI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) load(kt + 1);
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            f32x4 af[MI], bf[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; mi++) af[mi] = *(const f32x4*)&As[cur][arow + mi * 32 * CF_LDK + g * 8];
-#pragma unroll
-            for (int ni = 0; ni < NI; ni++) bf[ni] = *(const f32x4*)&Bs[cur][brow + ni * 32 * CF_LDK + g * 8];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-#pragma unroll
-                for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ni++)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi][e], bf[ni][e], acc[mi][ni], 0, 0, 0);
-        }
-        if (kt + 1 < nk) stage(cur ^ 1);
-        __syncthreads();
-    }
-
-    // epilogue: act(scale acc + shift + residual); only pixels < M and channels < Co are touched
-    float slope = 0.f;
-    if (EXT && a.act == GCC_EVAL_ACT_PRELU) slope = *a.slope;
-#pragma unroll
-    for (int ni = 0; ni < NI; ni++) {
-        const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
-        if (co >= a.Co) continue;
-        const float sc = a.scale ? a.scale[co] : 1.f, sh = a.shift ? a.shift[co] : 0.f;
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= a.M) continue;
-                float v = fmaf(acc[mi][ni][r], sc, sh);
-                if (a.res) v += a.res[(size_t)m * a.ldr + a.roff + co];
-                if (!EXT) {
-                    if (a.relu) v = v < 0.f ? 0.f : v;
-                    a.y[(size_t)m * a.ldy + a.yoff + co] = v;
-                } else {
-                    if (a.act == GCC_EVAL_ACT_RELU) v = v < 0.f ? 0.f : v;
-                    else if (a.act == GCC_EVAL_ACT_PRELU) v = v >= 0.f ? v : __fmul_rn(slope, v);
-                    else if (a.act == GCC_EVAL_ACT_TANH) v = tanhf(v);
-                    if (!a.shuffle) {
-                        a.y[(size_t)m * a.ldy + a.yoff + co] = v;
-                    } else {
-                        // nn.PixelShuffle(2): channel co of pixel (n, oh, ow) is channel co >> 2 of pixel (2 oh + bit 1, 2 ow + bit 0)
-                        const int q = fdiv(m, a.dWo), ow = m - q * a.Wo;           // q = n Ho + oh
-                        const size_t p = ((size_t)q * 2 + ((co >> 1) & 1)) * ((size_t)a.Wo * 2) + 2 * ow + (co & 1);
-                        a.y[p * a.ldy + a.yoff + (co >> 2)] = v;
-                    }
-                }
-            }
-        }
-    }
+#define CF_SETUP const float* wbase = a.w
+#define CF_FETCH CF_FETCH_PADDED
+#define CF_NK (a.Kp / CF_BK)
+#include "conv_f32_tile_body.inc"
 }
+#undef CF_SETUP
+#undef CF_ROW
+#undef CF_TAP
+#undef CF_STORE_SETUP
+#undef CF_STORE
 
 // ---- gcc_conv_eval_f32_unet: Conv2d / ConvTranspose2d (k4, s2, p1) with two activated outputs -------------------------------
 struct ConvF32UnetArgs {
@@ -200,135 +102,43 @@ __device__ __forceinline__ float cf_unet_act(float v, int act, float slope) {
 }
 
 // TR = false: row m is output pixel (n, oh, ow), tap = kh 4 + kw read at (2 oh - 1 + kh, 2 ow - 1 + kw).
-// TR = true: blockIdx.z = 2 ph + pw is the phase, row m is input-map pixel (n, i, j) and output pixel (n, 2 i + ph, 2 j + pw);
-// tap = 2 th + tw reads (i + ph - th, j + pw - tw), which is kernel element (1 - ph + 2 th, 1 - pw + 2 tw) of ConvTranspose2d.
+// TR = true: blockIdx.z = 2 ph + pw is the phase (each has its own packed weights), row m is input-map pixel (n, i, j) and output
+// pixel (n, 2 i + ph, 2 j + pw) of [N][2 H][2 W]; tap = 2 th + tw reads (i + ph - th, j + pw - tw), which is kernel element
+// (1 - ph + 2 th, 1 - pw + 2 tw) of ConvTranspose2d.  The store is y = act(z) and, with y2, y2 = act2(z); q = n H + i there.
+// a: the kernel's ConvF32UnetArgs in each of them.
+#define CF_ROW(m, ih0, iw0, nb)                                                                        \
+    const int q = fdiv(m, a.dWm), c = m - q * a.Wm;                                                    \
+    const int n = fdiv(q, a.dHm), r = q - n * a.Hm;                                                    \
+    ih0 = TR ? r + ph : 2 * r - 1; iw0 = TR ? c + pw : 2 * c - 1; nb = n * a.H * a.W
+#define CF_TAP(k4)                                                                                     \
+    const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;                                           \
+    const bool kok = k4 < a.Kreal;                                                                     \
+    const int dh = TR ? -(tap >> 1) : (tap >> 2), dw = TR ? -(tap & 1) : (tap & 3)
+#define CF_STORE_SETUP
+#define CF_STORE(m, co, Z)                                                                             \
+    size_t p = (size_t)m;                                                                              \
+    if (TR) {                                                                                          \
+        const int q = fdiv(m, a.dWm), c = m - q * a.Wm;                                                \
+        p = ((size_t)q * 2 + ph) * ((size_t)a.Wm * 2) + 2 * c + pw;                                    \
+    }                                                                                                  \
+    const float z = Z;                                                                                 \
+    a.y[p * a.ldy + a.yoff + co] = cf_unet_act(z, a.act, a.slope);                                     \
+    if (a.y2) a.y2[p * a.ldy2 + a.y2off + co] = cf_unet_act(z, a.act2, a.slope)
 template <int MI, int NI, int WM, int WN, bool TR>
 __global__ __launch_bounds__(CF_THREADS) void conv_f32_unet_kernel(ConvF32UnetArgs a) {
-    static_assert(WM * WN == 4, "four waves");
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    constexpr int A_PER = BM * 4 / CF_THREADS, B_PER = (BN * 4 + CF_THREADS - 1) / CF_THREADS;
-    __shared__ __attribute__((aligned(16))) float As[2][BM * CF_LDK];
-    __shared__ __attribute__((aligned(16))) float Bs[2][BN * CF_LDK];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int chunk = t & 3;
-    const int ph = TR ? (int)(blockIdx.z >> 1) : 0, pw = TR ? (int)(blockIdx.z & 1) : 0;
-    const float* wbase = a.w + (TR ? (size_t)blockIdx.z * a.Co * a.Kp : 0);
-
-    int ih0[A_PER], iw0[A_PER], nb[A_PER];
-#pragma unroll
-    for (int i = 0; i < A_PER; i++) {
-        const int m = m0 + ((t + i * CF_THREADS) >> 2);
-        if (m < a.M) {
-            const int q = fdiv(m, a.dWm), c = m - q * a.Wm;
-            const int n = fdiv(q, a.dHm), r = q - n * a.Hm;
-            ih0[i] = TR ? r + ph : 2 * r - 1; iw0[i] = TR ? c + pw : 2 * c - 1; nb[i] = n * a.H * a.W;
-        } else {
-            ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
-        }
-    }
-    const float* wrow[B_PER];
-#pragma unroll
-    for (int i = 0; i < B_PER; i++) {
-        const int idx = t + i * CF_THREADS, co = n0 + (idx >> 2);
-        wrow[i] = (idx < BN * 4 && co < a.Co) ? wbase + (size_t)co * a.Kp + chunk * 4 : nullptr;
-    }
-
-    f32x4 ra[A_PER], rb[B_PER];
-    auto load = [&](int kt) {
-        const int k4 = kt * CF_BK + chunk * 4;
-        const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;
-        const bool kok = k4 < a.Kreal;
-        const int dh = TR ? -(tap >> 1) : (tap >> 2), dw = TR ? -(tap & 1) : (tap & 3);
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) {
-            const int ih = ih0[i] + dh, iw = iw0[i] + dw;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (kok && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W) {
-                v = *(const f32x4*)(a.x + (size_t)(nb[i] + ih * a.W + iw) * a.ldx + a.xoff + ci);
-                if (a.Ci == 3) v[3] = 0.f;           // the stem's pad channel: whatever it holds, it is not an input
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (wrow[i]) v = *(const f32x4*)(wrow[i] + kt * CF_BK);
-            rb[i] = v;
-        }
-    };
-    auto stage = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) *(f32x4*)&As[s][((t + i * CF_THREADS) >> 2) * CF_LDK + chunk * 4] = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            const int idx = t + i * CF_THREADS;
-            if (idx < BN * 4) *(f32x4*)&Bs[s][(idx >> 2) * CF_LDK + chunk * 4] = rb[i];
-        }
-    };
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[mi][ni][r] = 0.f;
-
-    // the k loop of conv_f32_kernel: the same LDS reads, the same order of MFMAs
-    const int nk = a.Kp / CF_BK;
-    const int arow = (wm * MI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
-    const int brow = (wn * NI * 32 + (lane & 31)) * CF_LDK + (lane >> 5) * 4;
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) load(kt + 1);
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            f32x4 af[MI], bf[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; mi++) af[mi] = *(const f32x4*)&As[cur][arow + mi * 32 * CF_LDK + g * 8];
-#pragma unroll
-            for (int ni = 0; ni < NI; ni++) bf[ni] = *(const f32x4*)&Bs[cur][brow + ni * 32 * CF_LDK + g * 8];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-#pragma unroll
-                for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ni++)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi][e], bf[ni][e], acc[mi][ni], 0, 0, 0);
-        }
-        if (kt + 1 < nk) stage(cur ^ 1);
-        __syncthreads();
-    }
-
-    // epilogue: z = fmaf(acc, scale, shift); y = act(z) and, with y2, y2 = act2(z); only rows < M and channels < Co are touched
-#pragma unroll
-    for (int ni = 0; ni < NI; ni++) {
-        const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
-        if (co >= a.Co) continue;
-        const float sc = a.scale ? a.scale[co] : 1.f, sh = a.shift ? a.shift[co] : 0.f;
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= a.M) continue;
-                size_t p = (size_t)m;
-                if (TR) {                            // row (n, i, j) of the input map -> pixel (n, 2 i + ph, 2 j + pw) of [N][2 H][2 W]
-                    const int q = fdiv(m, a.dWm), c = m - q * a.Wm;            // q = n H + i
-                    p = ((size_t)q * 2 + ph) * ((size_t)a.Wm * 2) + 2 * c + pw;
-                }
-                const float z = fmaf(acc[mi][ni][r], sc, sh);
-                a.y[p * a.ldy + a.yoff + co] = cf_unet_act(z, a.act, a.slope);
-                if (a.y2) a.y2[p * a.ldy2 + a.y2off + co] = cf_unet_act(z, a.act2, a.slope);
-            }
-        }
-    }
+#define CF_SETUP                                                                                       \
+    const int ph = TR ? (int)(blockIdx.z >> 1) : 0, pw = TR ? (int)(blockIdx.z & 1) : 0;               \
+    const float* wbase = a.w + (TR ? (size_t)blockIdx.z * a.Co * a.Kp : 0)
+#include "conv_f32_tile_body.inc"
 }
+#undef CF_SETUP
+#undef CF_ROW
+#undef CF_TAP
+#undef CF_FETCH
+#undef CF_FETCH_PADDED
+#undef CF_NK
+#undef CF_STORE_SETUP
+#undef CF_STORE
 
 // one thread per pixel: C strided reads (consecutive threads read consecutive floats of a plane), cfill / 4 16-byte stores
 __global__ __launch_bounds__(CF_THREADS) void nchw_to_nhwc_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
@@ -355,26 +165,6 @@ __global__ __launch_bounds__(CF_THREADS) void nhwc_to_nchw_f32_kernel(const floa
         float* d = dst + n * C * plane + q;
         for (int c = 0; c < C; c++) d[(size_t)c * plane] = s[c];
     }
-}
-
-inline int cf_cip(int Ci) { return Ci == 3 ? 4 : Ci; }
-inline int cf_kp(int Ci, int KH, int KW) { return (KH * KW * cf_cip(Ci) + CF_BK - 1) / CF_BK * CF_BK; }
-
-// the tile of M pixels x Co channels (0: 128 x 128, 1: 64 x 64, 2: 128 x 32)
-inline int cf_tile(long long M, int Co) {
-    if (Co <= 32) return 2;
-    const long long big = ((M + 127) / 128) * ((Co + 127) / 128);
-    return (Co >= 128 && big >= 256) ? 0 : 1;              // 128 x 128 tiles once they fill the chip, else 64 x 64
-}
-
-// what both entries refuse alike, the kernel's shape aside; 0 when there is nothing to refuse
-int cf_common(const gcc_conv_t* c, int pad_h, int pad_w, int dilation) {
-    if (!c || c->N <= 0 || c->H <= 0 || c->W <= 0 || c->Ci <= 0 || c->Co <= 0 || c->KH <= 0 || c->KW <= 0 || c->stride <= 0 ||
-        pad_h < 0 || pad_w < 0 || dilation < 1)
-        return GCC_ERR_BAD_ARG;
-    if (c->ldx <= 0 || c->ldy <= 0 || c->xoff < 0 || c->yoff < 0 || (c->ldx & 3) || (c->xoff & 3) || (c->ldy & 3) || (c->yoff & 3))
-        return GCC_ERR_BAD_ARG;
-    return 0;
 }
 
 // the tile of a geometry whose kernel and paddings have passed, or the error the call returns for it
@@ -443,23 +233,17 @@ int cf_launch(const gcc_conv_t* c, int route, int pad_h, int pad_w, const float*
     a.dil = ep->dilation;
     a.ldx = c->ldx; a.xoff = c->xoff; a.ldy = c->ldy; a.yoff = c->yoff;
     a.ldr = ep->residual ? ep->ld_residual : 0; a.roff = ep->residual ? ep->residual_off : 0;
-    a.Kreal = c->KH * c->KW * a.Cip; a.Kp = cf_kp(c->Ci, c->KH, c->KW);
+    a.Kreal = c->KH * c->KW * a.Cip; a.Kp = cf_kp(c->Ci, c->KH * c->KW);
     a.relu = ep->act == GCC_EVAL_ACT_RELU;
     a.slope = slope; a.act = ep->act; a.shuffle = shuffle;
     a.dWo = make_fastdiv(a.Wo); a.dHo = make_fastdiv(a.Ho); a.dCip = make_fastdiv(a.Cip); a.dKW = make_fastdiv(a.KW);
-    const hipStream_t st = (hipStream_t)stream;
-    if (route == 0)
-        hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2, EXT>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128)), dim3(CF_THREADS), 0, st, a);
-    else if (route == 1)
-        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 2, 2, EXT>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64)), dim3(CF_THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_f32_kernel<1, 1, 4, 1, EXT>), dim3(cdiv(a.M, 128), 1), dim3(CF_THREADS), 0, st, a);
+    CF_LAUNCH_TILE(conv_f32_kernel, EXT, a, 1, route, (hipStream_t)stream);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
 
 // gcc_conv_eval_f32_unet: 16 taps forward, 4 per phase transposed
-inline int cf_unet_kp(int Ci, int transposed) { return ((transposed ? 4 : 16) * cf_cip(Ci) + CF_BK - 1) / CF_BK * CF_BK; }
+inline int cf_unet_kp(int Ci, int transposed) { return cf_kp(Ci, transposed ? 4 : 16); }
 
 // the rows one launch slice walks: output pixels forward, input pixels (one phase's output pixels) transposed
 inline long long cf_unet_rows(const gcc_conv_t* c, int transposed) {
@@ -488,17 +272,6 @@ bool cf_windows_overlap(long long a, int lda, long long b, int ldb, long long pi
     if (lda != ldb) return true;                           // interleaved at two strides: not worth telling apart
     const long long r = ((b - a) % lda + lda) % lda;
     return r < Co || r > lda - Co;
-}
-
-template <bool TR>
-void cf_launch_unet(const ConvF32UnetArgs& a, int route, hipStream_t st) {
-    const unsigned z = TR ? 4 : 1;
-    if (route == 0)
-        hipLaunchKernelGGL((conv_f32_unet_kernel<2, 2, 2, 2, TR>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128), z), dim3(CF_THREADS), 0, st, a);
-    else if (route == 1)
-        hipLaunchKernelGGL((conv_f32_unet_kernel<1, 1, 2, 2, TR>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64), z), dim3(CF_THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_f32_unet_kernel<1, 1, 4, 1, TR>), dim3(cdiv(a.M, 128), 1, z), dim3(CF_THREADS), 0, st, a);
 }
 
 }  // namespace
@@ -538,15 +311,15 @@ extern "C" int gcc_conv_eval_f32_unet(const gcc_conv_t* c, int transposed, const
     a.Kreal = (transposed ? 4 : 16) * a.Cip; a.Kp = cf_unet_kp(c->Ci, transposed);
     a.act = ep->act; a.act2 = ep->act2; a.slope = ep->slope;
     a.dWm = make_fastdiv(a.Wm); a.dHm = make_fastdiv(a.Hm); a.dCip = make_fastdiv(a.Cip);
-    if (transposed) cf_launch_unet<true>(a, route, (hipStream_t)stream);
-    else cf_launch_unet<false>(a, route, (hipStream_t)stream);
+    if (transposed) CF_LAUNCH_TILE(conv_f32_unet_kernel, true, a, 4, route, (hipStream_t)stream);
+    else CF_LAUNCH_TILE(conv_f32_unet_kernel, false, a, 1, route, (hipStream_t)stream);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
 
 extern "C" int gcc_conv_eval_f32_kp(int Ci, int KH, int KW) {
     if (Ci <= 0 || KH <= 0 || KW <= 0 || (long long)KH * KW * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
-    return cf_kp(Ci, KH, KW);
+    return cf_kp(Ci, (long long)KH * KW);
 }
 
 extern "C" int gcc_conv_eval_f32_route(const gcc_conv_t* c, int dilation) { return cf_route(c, dilation); }

@@ -1,25 +1,23 @@
 // The MobileResnet generator at the reference's own precision (engine.MobileResnetEngine.infer, precision 'fp32'): what its fp32
 // program needs beyond gcc_conv_eval_f32_act (the k3 s2 p1 and 1 x 1 convolutions).  All tensors are NHWC fp32.
 //
-// gcc_conv_eval_f32_resnet   conv_f32_kernel's tiles, LDS layout, MFMA loop (v_mfma_f32_32x32x2_f32) and single order of K in a
-//                            kernel of its own (conv_f32.hip keeps its text and its bits), with two gathers:
+// gcc_conv_eval_f32_resnet   the fifth entry on the fp32 tile (conv_f32_tile.hpp: the implicit GEMM, its k loop and the single
+//                            order of K, the body text conv_f32_tile_body.inc; conv_f32.hip has the other four), with two gathers:
 //     REFLECT      Conv2d(k, s1, p0) behind ReflectionPad2d(k / 2): a tap outside the map reads its mirror pixel (ih < 0 -> -ih,
 //                  ih >= H -> 2 (H - 1) - ih); no padded copy of the map exists
 //     TRANSPOSED3  ConvTranspose2d(k3, s2, p1, output_padding 1): blockIdx.z is one of the four output parity phases, a gather of
 //                  1 / 2 / 2 / 4 taps over the input stored at pixel stride 2; each phase walks only its own K
-//   No split-K, no atomics, nothing shared between workgroups.
 // gcc_dwconv3x3_reflect_f32  depthwise 3 x 3 behind ReflectionPad2d(1): bias and nine products as one fmaf chain per output; with a
 //                            statistics pointer the launch also writes the InstanceNorm partials of its own output.
 // gcc_inorm_stats_f32 / gcc_inorm_apply_f32   InstanceNorm2d(affine=False) in two launches.  A plane is cut into chunks whose
 //   size depends on H W alone; per (image, chunk, channel) the stats launch writes the chunk's mean and M2 (the sum of squared
 //   deviations from that mean) as doubles, from sums about a pivot (the chunk's first pixel).  The apply launch folds the chunks
 //   of its channels in chunk order, in double, and normalises.  No workgroup waits for another; no atomics; no zero-fill contract.
-#include "common.hpp"
+#include "conv_f32_tile.hpp"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-constexpr int RF_BK = 16, RF_LDK = RF_BK + 4, RF_THREADS = 256;
+constexpr int RF_THREADS = 256;                    // the depthwise and InstanceNorm kernels' workgroup
 
 struct ConvF32ResnetArgs {
     const float* x; const float* w; float* y;
@@ -32,163 +30,67 @@ struct ConvF32ResnetArgs {
 __device__ __forceinline__ int rf_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }
 
 // TR = false: row m is output pixel (n, oh, ow); tap = kh KW + kw reads the mirror of (oh - pad + kh, ow - pad + kw).
-// TR = true: blockIdx.z = 2 ph + pw is the phase, row m is input pixel (n, i, j) and output pixel (n, 2 i + ph, 2 j + pw).  The
-// phase has (1 + ph) (1 + pw) taps, tap = th (1 + pw) + tw reading (i + th, j + tw) -- zeros beyond the map -- which is kernel
-// element (ph ? 2 - 2 th : 1, pw ? 2 - 2 tw : 1) of ConvTranspose2d.
+// TR = true: blockIdx.z = 2 ph + pw is the phase (its own packed weights, its own K), row m is input pixel (n, i, j) and output
+// pixel (n, 2 i + ph, 2 j + pw) of [N][2 H][2 W].  The phase has (1 + ph) (1 + pw) taps, tap = th (1 + pw) + tw reading
+// (i + th, j + tw) -- zeros beyond the map -- which is kernel element (ph ? 2 - 2 th : 1, pw ? 2 - 2 tw : 1) of ConvTranspose2d.
+// A row beyond M (the tile's sentinel) has no mirror either.  The store is y = act(z); q = n H + i there.
+// a: the kernel's ConvF32ResnetArgs in each of them.
+#define CF_ROW(m, ih0, iw0, nb)                                                                        \
+    const int q = fdiv(m, a.dW), c = m - q * a.W;                                                      \
+    const int n = fdiv(q, a.dH), r = q - n * a.H;                                                      \
+    ih0 = TR ? r : r - a.pad; iw0 = TR ? c : c - a.pad; nb = n * a.H * a.W
+#define CF_TAP(k4)                                                                                     \
+    const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;                                           \
+    const bool kok = k4 < kreal;                                                                       \
+    int dh, dw;                                                                                        \
+    if (TR) { dh = pw ? tap >> 1 : tap; dw = pw ? tap & 1 : 0; }                                       \
+    else { dh = fdiv(tap, a.dKW); dw = tap - dh * a.KW; }
+#define CF_FETCH(v, ih0, iw0, nb)                                                                      \
+    int ih = ih0 + dh, iw = iw0 + dw;                                                                  \
+    bool ok = kok && ih0 > -(1 << 27);                                                                 \
+    if (TR) ok = ok && ih < a.H && iw < a.W;                                                           \
+    else { ih = rf_reflect(ih, a.H); iw = rf_reflect(iw, a.W); }                                       \
+    if (ok) {                                                                                          \
+        v = *(const f32x4*)(a.x + (size_t)(nb + ih * a.W + iw) * a.ldx + a.xoff + ci);                 \
+        if (a.Ci == 3) v[3] = 0.f;                                                                     \
+    }
+#define CF_NK nk
+#define CF_STORE_SETUP
+#define CF_STORE(m, co, z)                                                                             \
+    size_t p = (size_t)m;                                                                              \
+    if (TR) {                                                                                          \
+        const int q = fdiv(m, a.dW), c = m - q * a.W;                                                  \
+        p = ((size_t)q * 2 + ph) * ((size_t)a.W * 2) + 2 * c + pw;                                     \
+    }                                                                                                  \
+    float v = z;                                                                                       \
+    if (a.act == GCC_EVAL_ACT_RELU) v = v < 0.f ? 0.f : v;                                             \
+    else if (a.act == GCC_EVAL_ACT_TANH) v = tanhf(v);                                                 \
+    a.y[p * a.ldy + a.yoff + co] = v
 template <int MI, int NI, int WM, int WN, bool TR>
-__global__ __launch_bounds__(RF_THREADS) void conv_f32_resnet_kernel(ConvF32ResnetArgs a) {
-    static_assert(WM * WN == 4, "four waves");
-    constexpr int BM = WM * MI * 32, BN = WN * NI * 32;
-    constexpr int A_PER = BM * 4 / RF_THREADS, B_PER = (BN * 4 + RF_THREADS - 1) / RF_THREADS;
-    __shared__ __attribute__((aligned(16))) float As[2][BM * RF_LDK];
-    __shared__ __attribute__((aligned(16))) float Bs[2][BN * RF_LDK];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-    const int chunk = t & 3;
-    const int ph = TR ? (int)(blockIdx.z >> 1) : 0, pw = TR ? (int)(blockIdx.z & 1) : 0;
-    const float* wbase = a.w + (TR ? (size_t)blockIdx.z * a.Co * a.Kp : 0);
-    const int kreal = TR ? (1 + ph) * (1 + pw) * a.Ci : a.Kreal;
-    const int nk = TR ? (kreal + RF_BK - 1) / RF_BK : a.Kp / RF_BK;
-
-    int ih0[A_PER], iw0[A_PER], nb[A_PER];
-#pragma unroll
-    for (int i = 0; i < A_PER; i++) {
-        const int m = m0 + ((t + i * RF_THREADS) >> 2);
-        if (m < a.M) {
-            const int q = fdiv(m, a.dW), c = m - q * a.W;
-            const int n = fdiv(q, a.dH), r = q - n * a.H;
-            ih0[i] = TR ? r : r - a.pad; iw0[i] = TR ? c : c - a.pad; nb[i] = n * a.H * a.W;
-        } else {
-            ih0[i] = -(1 << 28); iw0[i] = 0; nb[i] = 0;
-        }
-    }
-    const float* wrow[B_PER];
-#pragma unroll
-    for (int i = 0; i < B_PER; i++) {
-        const int idx = t + i * RF_THREADS, co = n0 + (idx >> 2);
-        wrow[i] = (idx < BN * 4 && co < a.Co) ? wbase + (size_t)co * a.Kp + chunk * 4 : nullptr;
-    }
-
-    f32x4 ra[A_PER], rb[B_PER];
-    auto load = [&](int kt) {
-        const int k4 = kt * RF_BK + chunk * 4;
-        const int tap = fdiv(k4, a.dCip), ci = k4 - tap * a.Cip;
-        const bool kok = k4 < kreal;
-        int dh, dw;
-        if (TR) { dh = pw ? tap >> 1 : tap; dw = pw ? tap & 1 : 0; }
-        else { dh = fdiv(tap, a.dKW); dw = tap - dh * a.KW; }
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) {
-            int ih = ih0[i] + dh, iw = iw0[i] + dw;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            bool ok = kok && ih0[i] > -(1 << 27);
-            if (TR) ok = ok && ih < a.H && iw < a.W;
-            else { ih = rf_reflect(ih, a.H); iw = rf_reflect(iw, a.W); }
-            if (ok) {
-                v = *(const f32x4*)(a.x + (size_t)(nb[i] + ih * a.W + iw) * a.ldx + a.xoff + ci);
-                if (a.Ci == 3) v[3] = 0.f;           // the stem's pad channel: whatever it holds, it is not an input
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (wrow[i]) v = *(const f32x4*)(wrow[i] + kt * RF_BK);
-            rb[i] = v;
-        }
-    };
-    auto stage = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < A_PER; i++) *(f32x4*)&As[s][((t + i * RF_THREADS) >> 2) * RF_LDK + chunk * 4] = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_PER; i++) {
-            const int idx = t + i * RF_THREADS;
-            if (idx < BN * 4) *(f32x4*)&Bs[s][(idx >> 2) * RF_LDK + chunk * 4] = rb[i];
-        }
-    };
-
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-        for (int ni = 0; ni < NI; ni++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[mi][ni][r] = 0.f;
-
-    // the k loop of conv_f32_kernel: the same LDS reads, the same order of MFMAs
-    const int arow = (wm * MI * 32 + (lane & 31)) * RF_LDK + (lane >> 5) * 4;
-    const int brow = (wn * NI * 32 + (lane & 31)) * RF_LDK + (lane >> 5) * 4;
-    load(0);
-    stage(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) load(kt + 1);
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            f32x4 af[MI], bf[NI];
-#pragma unroll
-            for (int mi = 0; mi < MI; mi++) af[mi] = *(const f32x4*)&As[cur][arow + mi * 32 * RF_LDK + g * 8];
-#pragma unroll
-            for (int ni = 0; ni < NI; ni++) bf[ni] = *(const f32x4*)&Bs[cur][brow + ni * 32 * RF_LDK + g * 8];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-#pragma unroll
-                for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-                    for (int ni = 0; ni < NI; ni++)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mi][e], bf[ni][e], acc[mi][ni], 0, 0, 0);
-        }
-        if (kt + 1 < nk) stage(cur ^ 1);
-        __syncthreads();
-    }
-
-    // epilogue: y = act(fmaf(acc, scale, shift)); only rows < M and channels < Co are touched
-#pragma unroll
-    for (int ni = 0; ni < NI; ni++) {
-        const int co = n0 + (wn * NI + ni) * 32 + (lane & 31);
-        if (co >= a.Co) continue;
-        const float sc = a.scale ? a.scale[co] : 1.f, sh = a.shift ? a.shift[co] : 0.f;
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int m = m0 + (wm * MI + mi) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (m >= a.M) continue;
-                size_t p = (size_t)m;
-                if (TR) {                            // row (n, i, j) of the input map -> pixel (n, 2 i + ph, 2 j + pw) of [N][2 H][2 W]
-                    const int q = fdiv(m, a.dW), c = m - q * a.W;              // q = n H + i
-                    p = ((size_t)q * 2 + ph) * ((size_t)a.W * 2) + 2 * c + pw;
-                }
-                float v = fmaf(acc[mi][ni][r], sc, sh);
-                if (a.act == GCC_EVAL_ACT_RELU) v = v < 0.f ? 0.f : v;
-                else if (a.act == GCC_EVAL_ACT_TANH) v = tanhf(v);
-                a.y[p * a.ldy + a.yoff + co] = v;
-            }
-        }
-    }
+__global__ __launch_bounds__(CF_THREADS) void conv_f32_resnet_kernel(ConvF32ResnetArgs a) {
+#define CF_SETUP                                                                                       \
+    const int ph = TR ? (int)(blockIdx.z >> 1) : 0, pw = TR ? (int)(blockIdx.z & 1) : 0;               \
+    const float* wbase = a.w + (TR ? (size_t)blockIdx.z * a.Co * a.Kp : 0);                            \
+    const int kreal = TR ? (1 + ph) * (1 + pw) * a.Ci : a.Kreal;                                       \
+    const int nk = TR ? (kreal + CF_BK - 1) / CF_BK : a.Kp / CF_BK
+#include "conv_f32_tile_body.inc"
 }
+#undef CF_SETUP
+#undef CF_ROW
+#undef CF_TAP
+#undef CF_FETCH
+#undef CF_NK
+#undef CF_STORE_SETUP
+#undef CF_STORE
 
-inline int rf_cip(int Ci) { return Ci == 3 ? 4 : Ci; }
-inline int rf_ceil16(long long v) { return (int)((v + RF_BK - 1) / RF_BK * RF_BK); }
 // REFLECT: gcc_conv_eval_f32's packing; TRANSPOSED3: the row stride of all four phases, the four-tap phase's K
-inline int rf_kp(int Ci, int kind, int k) { return kind == GCC_F32_RESNET_REFLECT ? rf_ceil16((long long)k * k * rf_cip(Ci)) : rf_ceil16(4ll * Ci); }
-
-// conv_f32.hip's choice of tile for M rows x Co channels (0: 128 x 128, 1: 64 x 64, 2: 128 x 32)
-inline int rf_tile(long long M, int Co) {
-    if (Co <= 32) return 2;
-    const long long big = ((M + 127) / 128) * ((Co + 127) / 128);
-    return (Co >= 128 && big >= 256) ? 0 : 1;
-}
+inline int rf_kp(int Ci, int kind, int k) { return cf_kp(Ci, kind == GCC_F32_RESNET_REFLECT ? (long long)k * k : 4); }
 
 // the tile of a geometry, or the error the call returns for it
 int rf_route(const gcc_conv_t* c, int kind) {
     if (!c || (kind != GCC_F32_RESNET_REFLECT && kind != GCC_F32_RESNET_TRANSPOSED3)) return GCC_ERR_BAD_ARG;
-    if (c->N <= 0 || c->H <= 0 || c->W <= 0 || c->Ci <= 0 || c->Co <= 0 || c->KH <= 0 || c->KW <= 0 || c->stride <= 0 || c->pad < 0)
-        return GCC_ERR_BAD_ARG;
-    if (c->ldx <= 0 || c->ldy <= 0 || c->xoff < 0 || c->yoff < 0 || (c->ldx & 3) || (c->xoff & 3) || (c->ldy & 3) || (c->yoff & 3))
-        return GCC_ERR_BAD_ARG;
+    const int bad = cf_common(c, c->pad, c->pad, 1);
+    if (bad) return bad;
     const bool tr = kind == GCC_F32_RESNET_TRANSPOSED3;
     if (tr) {
         if (c->KH != 3 || c->KW != 3 || c->stride != 2) return GCC_ERR_UNSUPPORTED;
@@ -201,21 +103,10 @@ int rf_route(const gcc_conv_t* c, int kind) {
         if (c->H <= c->KH / 2 || c->W <= c->KH / 2) return GCC_ERR_BAD_ARG;   // ReflectionPad2d needs the pad below the size
     }
     if (c->Co & 7) return GCC_ERR_UNSUPPORTED;
-    if (c->ldx < c->xoff + rf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
+    if (c->ldx < c->xoff + cf_cip(c->Ci) || c->ldy < c->yoff + c->Co) return GCC_ERR_BAD_ARG;
     const long long M = (long long)c->N * c->H * c->W, Mout = tr ? 4 * M : M;
-    if (Mout >= (1ll << 31) - 256 || (long long)c->KH * c->KW * rf_cip(c->Ci) >= (1ll << 30)) return GCC_ERR_UNSUPPORTED;
-    return rf_tile(M, c->Co);
-}
-
-template <bool TR>
-void rf_launch(const ConvF32ResnetArgs& a, int route, hipStream_t st) {
-    const unsigned z = TR ? 4 : 1;
-    if (route == 0)
-        hipLaunchKernelGGL((conv_f32_resnet_kernel<2, 2, 2, 2, TR>), dim3(cdiv(a.M, 128), cdiv(a.Co, 128), z), dim3(RF_THREADS), 0, st, a);
-    else if (route == 1)
-        hipLaunchKernelGGL((conv_f32_resnet_kernel<1, 1, 2, 2, TR>), dim3(cdiv(a.M, 64), cdiv(a.Co, 64), z), dim3(RF_THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_f32_resnet_kernel<1, 1, 4, 1, TR>), dim3(cdiv(a.M, 128), 1, z), dim3(RF_THREADS), 0, st, a);
+    if (Mout >= (1ll << 31) - 256 || (long long)c->KH * c->KW * cf_cip(c->Ci) >= (1ll << 30)) return GCC_ERR_UNSUPPORTED;
+    return cf_tile(M, c->Co);
 }
 
 // ---- InstanceNorm partials ------------------------------------------------------------------------------------------------
@@ -445,7 +336,7 @@ int in_common(const void* x, int ldx, const void* y, int ldy, int N, long long H
 extern "C" int gcc_conv_eval_f32_resnet_kp(int Ci, int kind, int k) {
     if (Ci <= 0 || (kind != GCC_F32_RESNET_REFLECT && kind != GCC_F32_RESNET_TRANSPOSED3)) return GCC_ERR_BAD_ARG;
     if (kind == GCC_F32_RESNET_TRANSPOSED3 ? k != 3 : (k != 3 && k != 7)) return GCC_ERR_BAD_ARG;
-    if ((long long)k * k * rf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
+    if ((long long)k * k * cf_cip(Ci) >= (1ll << 30)) return GCC_ERR_BAD_ARG;
     return rf_kp(Ci, kind, k);
 }
 
@@ -463,13 +354,13 @@ extern "C" int gcc_conv_eval_f32_resnet(const gcc_conv_t* c, int kind, const flo
     ConvF32ResnetArgs a;
     a.x = x; a.w = w; a.y = y; a.scale = ep->scale; a.shift = ep->shift;
     a.M = c->N * c->H * c->W; a.H = c->H; a.W = c->W;
-    a.Ci = c->Ci; a.Cip = rf_cip(c->Ci); a.Co = c->Co; a.KW = c->KW; a.pad = c->KH / 2;
+    a.Ci = c->Ci; a.Cip = cf_cip(c->Ci); a.Co = c->Co; a.KW = c->KW; a.pad = c->KH / 2;
     a.ldx = c->ldx; a.xoff = c->xoff; a.ldy = c->ldy; a.yoff = c->yoff;
     a.Kreal = c->KH * c->KW * a.Cip; a.Kp = rf_kp(c->Ci, kind, c->KH);
     a.act = ep->act;
     a.dW = make_fastdiv(a.W); a.dH = make_fastdiv(a.H); a.dCip = make_fastdiv(a.Cip); a.dKW = make_fastdiv(a.KW);
-    if (tr) rf_launch<true>(a, route, (hipStream_t)stream);
-    else rf_launch<false>(a, route, (hipStream_t)stream);
+    if (tr) CF_LAUNCH_TILE(conv_f32_resnet_kernel, true, a, 4, route, (hipStream_t)stream);
+    else CF_LAUNCH_TILE(conv_f32_resnet_kernel, false, a, 1, route, (hipStream_t)stream);
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }

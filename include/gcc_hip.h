@@ -564,10 +564,10 @@ int gcc_conv_eval_f32_act(const gcc_conv_t* c, int pad_h, int pad_w, const float
 int gcc_conv_eval_f32_act_route(const gcc_conv_t* c, int pad_h, int pad_w, int dilation, int shuffle);
 /* gcc_conv_eval_f32_unet: the U-Net generator's layers at the reference's own precision (engine.UnetEngine.infer, precision
  * 'fp32'; models/Pix2Pix.py:40-118): Conv2d(k4, s2, p1) and ConvTranspose2d(k4, s2, p1) in fp32 with up to two activated outputs.
- * A kernel of its own with gcc_conv_eval_f32's tiles, matrix instruction and ONE order of K (walked in steps of 16, every product
- * an fmaf onto the running sum; no split-K, no atomics, no workspace): an output element does not depend on its batch, its tile
- * or the tile shape.  One launch.  Added without a GCC_HIP_ABI bump (additions only); the three entries above keep their text and
- * their bits.  With z = fmaf(acc, scale[c], shift[c]):
+ * A gather and a store of its own on gcc_conv_eval_f32's tile: its tile shapes, matrix instruction and ONE order of K (walked in
+ * steps of 16, every product an fmaf onto the running sum; no split-K, no atomics, no workspace): an output element does not
+ * depend on its batch, its tile or the tile shape.  One launch.  Added without a GCC_HIP_ABI bump (additions only); the three
+ * entries above keep their bits.  With z = fmaf(acc, scale[c], shift[c]):
  *     y [p][c] = act (z)   at (c->ldy, c->yoff)
  *     y2[p][c] = act2(z)   at (ldy2, y2off)          (y2 NULL: no second store, act2 not read)
  *   act / act2: GCC_EVAL_ACT_NONE | _RELU | _LRELU | _TANH.  _LRELU is z >= 0 ? z : slope z with the host `slope`, one rounded
@@ -605,10 +605,11 @@ int gcc_conv_eval_f32_unet_route(const gcc_conv_t* c, int transposed);
 int gcc_conv_eval_f32_unet_kp(int Ci, int transposed);
 /* gcc_conv_eval_f32_resnet: the MobileResnet generator's reflection-padded and transposed convolutions at the reference's own
  * precision (engine.MobileResnetEngine.infer, precision 'fp32'; models/Pix2Pix.py:132-265, models/CycleGAN.py:77-138;
- * gcc_amd/csrc/resnet_f32.hip).  A kernel of its own with gcc_conv_eval_f32's tiles, matrix instruction and ONE order of K (walked
- * in steps of 16, every product an fmaf onto the running sum; no split-K, no atomics, no workspace): an output element depends on
- * neither its batch nor its tile.  One launch.  Added without a GCC_HIP_ABI bump (additions only); the four entries above keep
- * their text and their bits.  The generator's other convolutions (k3 s2 p1, 1 x 1) run on gcc_conv_eval_f32_act.
+ * gcc_amd/csrc/resnet_f32.hip).  Two gathers and a store of its own on gcc_conv_eval_f32's tile: its tile shapes, matrix
+ * instruction and ONE order of K (walked in steps of 16, every product an fmaf onto the running sum; no split-K, no atomics, no
+ * workspace): an output element depends on neither its batch nor its tile.  One launch.  Added without a GCC_HIP_ABI bump
+ * (additions only); the four entries above keep their bits.  The generator's other convolutions (k3 s2 p1, 1 x 1) run on
+ * gcc_conv_eval_f32_act.
  *     y[p][c] = act(fmaf(acc, scale[c], shift[c]))      act: GCC_EVAL_ACT_NONE | _RELU | _TANH (the device library's tanhf)
  * The descriptor is the LAYER's: c->H, c->W, c->Ci, c->ldx, c->xoff describe the input x; c->Co, c->ldy, c->yoff the output y.
  * kind = GCC_F32_RESNET_REFLECT: Conv2d(k, stride 1, padding 0) behind ReflectionPad2d(k / 2), y is [N][H][W].  The padding is

@@ -1,7 +1,7 @@
 """gcc_conv_eval_f32_unet (Conv2d / ConvTranspose2d k4 s2 p1 in fp32 with two activated outputs) against torch-CPU float64 at the
 U-Net's geometries, by the method of tests/test_conv_f32_act_gpu.py: an exact layout check on integer data (a wrong phase-to-tap
 mapping or strided store shows as a wrong integer), a derived per-element bound on seeded normal data, batch invariance bit for
-bit, the refusals, and the three older fp32 entries' bits pinned to what the library gave before this entry existed."""
+bit, the refusals, and the bits of all five fp32 entries pinned to what the library gave before their kernel bodies were merged."""
 import ctypes as C
 import functools
 import hashlib
@@ -310,11 +310,12 @@ def test_refusals_happen_before_any_launch():
     assert (v[:, :16] == 0).all() and (v[:, 48:] == 0).all() and (v[2 * 4 * 6:, 16:48] == SENTINEL).all()
 
 
-# ---- 5. the older entries keep their bits --------------------------------------------------------------------------------------
-# gcc_conv_eval_f32, _ex and _act compile from the text they had; what they compute for these seeded inputs was recorded with
-# the library built from the commit before gcc_conv_eval_f32_unet existed (selected with GCC_HIP_LIB=) and must not move.
-# No geometry goes through both an older entry and the new one (k4 against odd sides), so there is nothing to compare directly.
-OLD_ENTRY_SHA256 = {
+# ---- 5. the five entries keep their bits ----------------------------------------------------------------------------------------
+# All five fp32 entries run one tile (gcc_amd/csrc/conv_f32_tile.hpp).  What they compute for these seeded inputs was recorded
+# with the library built from the parent of the change that merged the kernel bodies (selected with GCC_HIP_LIB=) and must not
+# move: the merge kept the order of every fmaf, so equality is the bar.  The first eight were first recorded with the library
+# from before gcc_conv_eval_f32_unet existed, and have not moved since.
+ENTRY_SHA256 = {
     'f32_k3_s1_co40': '12202ac55194abac',
     'f32_k7_s2_stem': '79bb3e4b9d28c654',
     'f32_k3_d2_co136_big': '586c167c015a1854',
@@ -323,17 +324,32 @@ OLD_ENTRY_SHA256 = {
     'act_k9_prelu': 'dff694b56f72f959',
     'act_k3_shuffle_co64': '04b5a2fd6fc3a83f',
     'act_k3_tanh_res': '6bb64ef3667d6c25',
+    'unet_fwd_stem': '72820a78bc9aec8f',
+    'unet_fwd_co72_y2': '44e8d69ac1d6d237',
+    'unet_tr_ci72': 'f0167f97ad316794',
+    'unet_tr_co136_big': 'ec0be4220eb21fb9',
+    'resnet_rf7_stem': '2422d3c0bb840ac6',
+    'resnet_rf7_co72_tanh': 'ec675fc3088e1f21',
+    'resnet_rf3': 'ff07ccaf4c00aa4d',
+    'resnet_tr_ci72': '680dd2d3c7422a6a',
+    'resnet_tr_1x1': 'c9918623b1438e0e',
+    'resnet_tr_co136_big': '33615ad6db33630c',
 }
 
 
-def old_entry_outputs(L):
-    """name -> sha256 of the output bytes of the three older entries of the library handle L, on fixed seeded inputs that take
-    all three tile shapes, a residual, a dilation, rectangular kernels, PReLU, tanh and the shuffled store"""
+def entry_outputs(L):
+    """name -> sha256 of the output bytes of the five entries of the library handle L, on fixed seeded inputs that take all three
+    tile shapes of each kernel, a residual, a dilation, rectangular kernels, PReLU, tanh, the shuffled store, the U-Net's two
+    outputs and both of its directions, the reflection at k 7 and k 3 and the four phases of the k3 transposed convolution"""
     from gcc_amd import _lib, ops
     P = C.c_void_p
     L.gcc_conv_eval_f32.argtypes = [C.POINTER(_lib.conv_t), P, P, P, C.POINTER(_lib.eval_f32_epilogue_t), P]
     L.gcc_conv_eval_f32_ex.argtypes = [C.POINTER(_lib.conv_t), C.c_int, C.c_int, P, P, P, C.POINTER(_lib.eval_f32_epilogue_t), P]
     L.gcc_conv_eval_f32_act.argtypes = [C.POINTER(_lib.conv_t), C.c_int, C.c_int, P, P, P, C.POINTER(_lib.eval_f32_act_epilogue_t), P]
+    L.gcc_conv_eval_f32_unet.argtypes = [C.POINTER(_lib.conv_t), C.c_int, P, P, P, C.POINTER(_lib.eval_f32_unet_epilogue_t), P]
+    L.gcc_conv_eval_f32_unet_route.argtypes = [C.POINTER(_lib.conv_t), C.c_int]
+    L.gcc_conv_eval_f32_resnet.argtypes = [C.POINTER(_lib.conv_t), C.c_int, P, P, P, C.POINTER(_lib.eval_f32_resnet_epilogue_t), P]
+    L.gcc_conv_eval_f32_resnet_route.argtypes = [C.POINTER(_lib.conv_t), C.c_int]
     out = {}
 
     def one(name, entry, N, H, W, Ci, Co, kh, kw, stride, ph, pw, dil=1, act=NONE, res=False, shuffle=0, slope=False):
@@ -372,11 +388,60 @@ def old_entry_outputs(L):
     one('act_k9_prelu', 'act', 1, 6, 7, 3, 8, 9, 9, 1, 4, 4, act=1, slope=True)
     one('act_k3_shuffle_co64', 'act', 2, 9, 11, 8, 64, 3, 3, 1, 1, 1, act=1, slope=True, shuffle=2)
     one('act_k3_tanh_res', 'act', 2, 9, 11, 24, 72, 3, 3, 1, 1, 1, act=TANH, res=True)
+
+    def seeded(name, N, H, W, Ci, Co, wshape):
+        g = torch.Generator().manual_seed(sum(map(ord, name)))
+        x = _nhwc(torch.randn((N, Ci, H, W), generator=g), (Ci + 3) // 4 * 4, 0, 0.0)
+        w = (torch.randn(wshape, generator=g) * 0.1).to(DEV)
+        return x, w, (torch.rand(Co, generator=g) + 0.5).to(DEV), torch.randn(Co, generator=g).to(DEV)
+
+    def done(name, rc, tile, want_tile, *ys):
+        assert rc == 0 and tile == want_tile, (name, rc, tile)
+        h = hashlib.sha256()
+        for y in ys:
+            host = y.cpu()
+            assert float(host.abs().max()) > 0
+            h.update(host.numpy().tobytes())
+        out[name] = h.hexdigest()[:16]
+
+    def unet(name, tr, N, H, W, Ci, Co, tile, act=NONE, act2=None):
+        x, w, sc, sh = seeded(name, N, H, W, Ci, Co, (Ci, Co, 4, 4) if tr else (Co, Ci, 4, 4))
+        wp = ops.pack_weights_f32_unet(w, bool(tr))
+        Ho, Wo = (2 * H, 2 * W) if tr else (H // 2, W // 2)
+        y = torch.zeros((N, Ho, Wo, Co), dtype=torch.float32, device=DEV)
+        y2 = torch.zeros_like(y) if act2 is not None else None
+        d = ops.conv_desc(N, H, W, Ci, Co, 4, 2, 1, x.shape[-1], Co)
+        ep = _lib.eval_f32_unet_epilogue_t(sc.data_ptr(), sh.data_ptr(), y2.data_ptr() if y2 is not None else None,
+                                           Co if y2 is not None else 0, 0, act, act2 or 0, 0.2, 0)
+        rc = L.gcc_conv_eval_f32_unet(C.byref(d), tr, x.data_ptr(), wp.data_ptr(), y.data_ptr(), C.byref(ep), None)
+        done(name, rc, L.gcc_conv_eval_f32_unet_route(C.byref(d), tr), tile, *([y] if y2 is None else [y, y2]))
+
+    def resnet(name, kind, N, H, W, Ci, Co, k, tile, act=NONE):
+        tr = kind == _lib.F32_RESNET_TRANSPOSED3
+        x, w, sc, sh = seeded(name, N, H, W, Ci, Co, (Ci, Co, 3, 3) if tr else (Co, Ci, k, k))
+        wp = ops.pack_weights_f32_resnet(w, kind)
+        y = torch.zeros((N, 2 * H, 2 * W, Co) if tr else (N, H, W, Co), dtype=torch.float32, device=DEV)
+        d = ops.conv_desc(N, H, W, Ci, Co, k, 2 if tr else 1, 1 if tr else 0, x.shape[-1], Co)
+        ep = _lib.eval_f32_resnet_epilogue_t(sc.data_ptr(), sh.data_ptr(), act, 0)
+        rc = L.gcc_conv_eval_f32_resnet(C.byref(d), kind, x.data_ptr(), wp.data_ptr(), y.data_ptr(), C.byref(ep), None)
+        done(name, rc, L.gcc_conv_eval_f32_resnet_route(C.byref(d), kind), tile, y)
+
+    unet('unet_fwd_stem', 0, 2, 10, 12, 3, 16, 2, act=LRELU)
+    unet('unet_fwd_co72_y2', 0, 3, 4, 4, 8, 72, 1, act=LRELU, act2=RELU)
+    unet('unet_tr_ci72', 1, 3, 2, 2, 72, 16, 2, act=RELU)
+    unet('unet_tr_co136_big', 1, 1, 128, 128, 8, 136, 0, act=TANH)
+    RF, T3 = _lib.F32_RESNET_REFLECT, _lib.F32_RESNET_TRANSPOSED3
+    resnet('resnet_rf7_stem', RF, 1, 4, 4, 3, 8, 7, 2, act=RELU)
+    resnet('resnet_rf7_co72_tanh', RF, 3, 8, 8, 16, 72, 7, 1, act=TANH)
+    resnet('resnet_rf3', RF, 2, 9, 13, 8, 24, 3, 2)
+    resnet('resnet_tr_ci72', T3, 3, 2, 2, 72, 16, 3, 2, act=RELU)
+    resnet('resnet_tr_1x1', T3, 1, 1, 1, 72, 16, 3, 2)
+    resnet('resnet_tr_co136_big', T3, 1, 128, 128, 8, 136, 3, 0, act=RELU)
     return out
 
 
-def test_the_older_entries_keep_their_bits():
+def test_the_entries_keep_their_bits():
     from gcc_amd import ops
-    got = old_entry_outputs(ops.lib())
+    got = entry_outputs(ops.lib())
     print(got)
-    assert got == OLD_ENTRY_SHA256
+    assert got == ENTRY_SHA256
