@@ -187,6 +187,7 @@ PROTOTYPES = {
     'gcc_options_default': (_I, []),
     'gcc_conv_tile': (_I, [C.POINTER(conv_t), _I]),
     'gcc_conv_stat_tiles': (_I, [C.POINTER(conv_t), _I]),
+    'gcc_conv_halo_mode': (_I, [C.POINTER(conv_t), _I, _I]),
     'gcc_conv_route': (_I, [C.POINTER(conv_t), _I, C.POINTER(epilogue_t)]),
     'gcc_conv_y2_supported': (_I, [C.POINTER(conv_t), _I, C.POINTER(epilogue_t)]),
     'gcc_conv_workspace': (_Z, [C.POINTER(conv_t), _I]),

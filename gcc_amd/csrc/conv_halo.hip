@@ -452,8 +452,17 @@ HaloPlan halo_plan(const gcc_conv_t* c, int dgrad) {
     return h;
 }
 
+bool halo_fits(const gcc_conv_t* c, int dgrad) {
+    const size_t Ho = gcc_conv_out(c->H, c->KH, c->stride, 1), Wo = gcc_conv_out(c->W, c->KW, c->stride, 1);
+    const size_t xb = (size_t)c->N * c->H * c->W * c->ldx * 2, yb = (size_t)c->N * Ho * Wo * c->ldy * 2;
+    const size_t wb = (size_t)c->Ci * c->KH * c->KW * c->Co * 2;          // Cout x taps x Ct either way
+    const size_t sb = dgrad ? yb : xb, db = dgrad ? xb : yb;
+    return sb < OOB && wb < OOB && db < (size_t)1 << 32;
+}
+
 int launch_halo(const gcc_conv_t* c, int dgrad, const HaloPlan& h, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep,
                 const TailFin* fin, hipStream_t st) {
+    if (!halo_fits(c, dgrad)) return -1;
     HaloParams p;
     p.fin = fin ? *fin : TailFin{};
     const int Ho = gcc_conv_out(c->H, c->KH, c->stride, 1), Wo = gcc_conv_out(c->W, c->KW, c->stride, 1);
@@ -469,10 +478,7 @@ int launch_halo(const gcc_conv_t* c, int dgrad, const HaloPlan& h, const void* s
         p.Ct = c->Co; p.Cout = c->Ci;
     }
     p.ldw = c->KH * c->KW * p.Ct;
-    const size_t sb = (size_t)p.N * p.Hs * p.Ws * p.lds_ * 2, wb = (size_t)p.Cout * p.ldw * 2;
-    const size_t db = (size_t)p.N * p.Hd * p.Wd * p.ldd * 2;
-    if (sb >= OOB || wb >= OOB || db >= (size_t)1 << 32) return -1;
-    p.src_bytes = (uint32_t)sb; p.wgt_bytes = (uint32_t)wb;
+    p.src_bytes = (uint32_t)((size_t)p.N * p.Hs * p.Ws * p.lds_ * 2); p.wgt_bytes = (uint32_t)((size_t)p.Cout * p.ldw * 2);      // (halo_fits: both below OOB)
     p.TR = h.TR; p.TW = h.TW; p.lgTW = h.lgTW; p.HR = h.HR; p.HW = h.HW; p.HWp = h.HWp; p.npieces = h.npieces;
     p.tiles_x = h.tiles_x; p.tiles_y = h.tiles_y; p.ntiles = h.ntiles; p.nchunks = p.Ct / BK;
     p.PH = h.mode == 3 ? Ho : h.tiles_y * h.TR; p.PW = h.mode == 3 ? Wo : h.tiles_x * h.TW;

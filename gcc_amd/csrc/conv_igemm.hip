@@ -1647,6 +1647,26 @@ extern "C" int gcc_conv_tile(const gcc_conv_t* c, int dgrad) {
     return tp.BP * 1000 + tp.BC;
 }
 
+// gcc_conv_route says 0 for igemm_kernel and for igemm_halo_kernel alike: this tells them apart, with the predicates of the
+// dispatch in gcc_internal_igemm -- the routes in front of the halo branch (gcc_conv_route), select_tile's BP for the statistics
+// form (halo_routed), the launcher's size limits (halo_fits).  (The dispatch's "kernel smaller than the stride" rejection of a
+// data gradient cannot meet a geometry halo_plan accepts: k is 3 or 4, the stride 1 or 2.)  The epilogue it assumes is a plain
+// one: bias / activation, statistic rows or none -- no ep->bn without statistics and no ep->y2, which move a call between the
+// routes in front of the halo branch.
+extern "C" int gcc_conv_halo_mode(const gcc_conv_t* c, int dgrad, int with_stats) {
+    GCC_ENTER();
+    if (check_conv(c)) return 0;
+    gcc_epilogue_t ep = {};
+    float marker = 0.f;
+    if (with_stats) ep.stats_partial = &marker;       // the route predicates only test it against NULL
+    if (gcc_conv_route(c, dgrad, &ep) != 0) return 0;
+    const int phases = dgrad ? c->stride * c->stride : 1;
+    const TilePlan tp = select_tile(c->plan, conv_max_rows(c, dgrad), dgrad ? c->Ci : c->Co, phases, conv_nk(c, dgrad), 1);
+    const HaloPlan h = halo_plan(c, dgrad);
+    if (!halo_routed(c->plan, h, dgrad, with_stats != 0, tp.BP) || !halo_fits(c, dgrad)) return 0;
+    return 1 + h.mode;
+}
+
 extern "C" int gcc_conv_stat_tiles(const gcc_conv_t* c, int dgrad) {
     GCC_ENTER();
     if (check_conv(c)) return 0;

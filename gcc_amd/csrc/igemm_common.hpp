@@ -201,6 +201,9 @@ constexpr int BK = 64;   // k per step
 // conv_halo.hip: k4 s2 p1 convolutions with the tile's input neighbourhood resident in LDS
 struct HaloPlan { int ok, mode, TR, TW, lgTW, HR, HW, HWp, npieces, tiles_x, tiles_y, ntiles, phases, hc; size_t lds; long wgs; };
 HaloPlan halo_plan(const gcc_conv_t* c, int dgrad);
+// launch_halo's own size limits (32-bit buffer ranges of source and weights, 32-bit offsets into the destination): a geometry
+// halo_plan accepts but this refuses falls through to igemm_kernel.  Shared by the launcher and gcc_conv_halo_mode.
+bool halo_fits(const gcc_conv_t* c, int dgrad);
 struct TailFin;
 int launch_halo(const gcc_conv_t* c, int dgrad, const HaloPlan& h, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep,
                 const TailFin* fin, hipStream_t st);

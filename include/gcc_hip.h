@@ -196,6 +196,13 @@ int gcc_conv_y2_supported(const gcc_conv_t* c, int dgrad, const gcc_epilogue_t* 
 /* tile the current plan picks for a geometry on the igemm_kernel route: BP * 1000 + BC (e.g. 256256 = 256 pixels x
  * 256 channels); 0 for an invalid geometry.  Introspection for tests and profilers. */
 int gcc_conv_tile(const gcc_conv_t* c, int dgrad);
+/* gcc_conv_route's 0 covers igemm_kernel and the LDS-resident-neighbourhood kernel of conv_halo.hip: 1 + the halo kernel's mode
+ * (1: k4 s2 forward, 2: k4 s2 data gradient per phase, 3: the 128-channel data gradient with both px phases, 4 / 5: stride-1
+ * forward / data gradient, k4 or k3) when a call with this geometry, plan and options runs on it; 0 when it runs on anything
+ * else.  The call is taken to have a plain epilogue: bias / activation, and statistic rows when with_stats != 0 -- not
+ * gcc_epilogue_t.bn without statistic rows and not gcc_epilogue_t.y2, which send a call to other routes and are not modelled
+ * here.  Introspection for tests. */
+int gcc_conv_halo_mode(const gcc_conv_t* c, int dgrad, int with_stats);
 
 /* y = conv(x, W) (+bias, act).  Replaces aten::convolution at models/Pix2Pix.py:31-32, 280-300,
  * 320-343, 407-409 (F.conv2d / nn.Conv2d.forward).  x: [N,H,W,ldx]  w: W packing  y: [N,Ho,Wo,ldy] */

@@ -12,8 +12,11 @@ replay and event entry points; the depthwise / reflection-pad kernels of dwconv.
 and the training kernels of attention.hip, at pruned channel counts, small planes, strides, slices and
 loop edges, per element against float64, in tests/test_dwconv_kernels_gpu.py and
 tests/test_sagan_kernels_gpu.py; the norm and activation kernels of norm_act.hip, per element against float64 on every
-backward route, in channel windows and in eval mode, in tests/test_norm_kernels_gpu.py.  The one-shape tests of those kernels
-below stay as they are."""
+backward route, in channel windows and in eval mode, in tests/test_norm_kernels_gpu.py; the bf16 training convolutions
+(igemm_kernel's tile families, split K and the pair combine, the thin, head, thin-output, ring-walk and halo routes, every
+weight-gradient form) bit for bit on integer data, per element against float64 and with exact statistic rows, each test
+asserting the route it ran on, in tests/test_conv_bf16_exact_gpu.py (its checks examined in tests/test_conv_bounds_cpu.py).
+The one-shape tests of those kernels below stay as they are."""
 import math
 import os
 
@@ -1794,6 +1797,7 @@ def test_stream_helpers_order_work(public_api):
 HALO_CASES = [  # N, H, W, Ci, Co, stride: the PatchGAN layers conv_halo.hip serves at the bench's batch, and a smaller grid of each form
     (16, 128, 128, 128, 256, 2), (16, 64, 64, 256, 512, 2), (16, 32, 32, 512, 1024, 1), (8, 64, 64, 128, 256, 2),
     (4, 64, 64, 64, 512, 1)]
+from tests._conv_exact import HALO_LEGS      # which launch of which case below is a halo launch (asserted on the IGEMM_HALO = 2 leg)
 
 
 @pytest.mark.parametrize('hc', [0, 128])
@@ -1819,6 +1823,12 @@ def test_halo_conv_3x3(N, H, W, Ci, Co, hc):
     try:
         for halo in (0, 3):
             lib.gcc_set_option(_lib.OPT_IGEMM_HALO, halo)
+            # the leg really runs where it says (gcc_conv_route is 0 for both kernels): forward on the halo kernel with and without
+            # statistic rows; the data gradient only where its output width tiles by 128 (the other two cases' dgrad is igemm_kernel
+            # on both legs)
+            d = ops.conv_desc(N, H, W, Ci, Co, 3, 1, 1, (Ci + 7) & ~7, (Co + 7) & ~7)
+            legs = tuple(int(lib.gcc_conv_halo_mode(C.byref(d), dg, st_)) for dg, st_ in ((0, 0), (0, 1), (1, 0)))
+            assert legs == ((4, 4, 5 if Ci % 128 == 0 else 0) if halo else (0, 0, 0)), legs
             lib.gcc_launch_count(1)
             y = ops.conv_fprop(to_dev(x), w, Co, 3, 1, 1, bias=b.to(DEV), act=ops.ACT_RELU)
             raw, st = ops.conv_fprop(to_dev(x), w, Co, 3, 1, 1, want_stats=True)
@@ -1866,6 +1876,9 @@ def test_halo_conv_vs_torch_and_gather_kernel(N, H, W, Ci, Co, stride, hc):
     try:
         for halo in (0, 2):
             lib.gcc_set_option(_lib.OPT_IGEMM_HALO, halo)
+            d = ops.conv_desc(N, H, W, Ci, Co, k, stride, p, (Ci + 7) & ~7, (Co + 7) & ~7)
+            legs = (int(lib.gcc_conv_halo_mode(C.byref(d), 0, 1)), int(lib.gcc_conv_halo_mode(C.byref(d), 1, 0)))
+            assert legs == (HALO_LEGS[(N, H, W, Ci, Co, stride)][hc == 128] if halo else (0, 0)), legs
             y, st = ops.conv_fprop(to_dev(x), w, Co, k, stride, p, want_stats=True)
             dx = ops.conv_dgrad(to_dev(dy), wt, Ci, H, W, k, stride, p)
             res[halo] = (to_cpu(y), to_cpu(dx), st.double().sum(0).cpu())
