@@ -7,7 +7,11 @@ exact in fp32 in ANY order -- every tile shape, K split, pair combine, slab fold
 round-to-nearest-even.  So on 'int' data a forward / data-gradient output has ONE right value, exact.float().bfloat16(), and a
 weight gradient (fp32) is the exact integer; every route must produce those bits.
 
-Tensors here are NCHW float64 on the CPU; a geometry is g = (N, H, W, Ci, Co, k, stride, pad)."""
+Tensors here are NCHW float64 on the CPU; a geometry is g = (N, H, W, Ci, Co, k, stride, pad).
+
+The second half of the module does the same for the eval-mode (inference) convolutions gcc_conv_fprop_eval and gcc_conv_eval_ex
+(tests/test_conv_eval_exact_gpu.py): data that stays exact behind the affine epilogue, references, bound_eval, an emulation of the
+two epilogues with named defects, the case table and the host-side route queries."""
 import contextlib
 import ctypes as C
 
@@ -499,3 +503,414 @@ def wgrad_counts(case):
     if Co == 1 and ceil8(Ci) >= 256:
         return N * H * W, max(1, cdiv(N * H * W, 64) // 8)
     return N * Ho * Wo, N * cdiv(W, 64) * max(1, H // (2 * k))
+
+
+# ==================================================================================================================================
+# The eval-mode (inference) convolutions: gcc_conv_fprop_eval and gcc_conv_eval_ex -- igemm_epilogue with EPI == 1,
+# igemm_epilogue_ex, the ring-walk's EV branch (conv_ring3.hip), and the two fold kernels splitk_epilogue_kernel<true> and
+# splitk_eval_ex_kernel.  Shared by tests/test_conv_eval_exact_gpu.py and tests/test_conv_bounds_cpu.py.
+#
+# An eval geometry is g = (N, H, W, Ci, Co, kh, kw, stride, pad, transposed): H, W, Ci describe the call's INPUT, Co its output
+# (transposed: the ConvTranspose2d forward, weight [Ci, Co, kh, kw]; the output is (H - 1) stride - 2 pad + kh high).
+#
+# Why the exact method still holds behind an affine epilogue: on 'int' data the accumulator is an integer, scale is +-0.5, +-1
+# or +-2, shift and residual are integers, the slope is 0.25 or -0.5 -- every intermediate (scale acc, + shift, * slope,
+# + residual) is a multiple of 2^-3.  While max |scale| mag + |shift| + |residual| < 2^20 each of them is below 2^20 and so
+# has at most 23 bits in front of its last (2^-3) one: it is an fp32 number.  The value in front of the store is therefore
+# exact in any summation order, with the multiply and the add fused or not, and the bf16 output has ONE right value.
+EV_NONE, EV_PRELU, EV_TANH, EV_RELU, EV_LRELU = 0, 1, 2, 3, 4       # include/gcc_hip.h GCC_EVAL_ACT_*
+EVAL_LIMIT = 2.0 ** 20
+INT_SCALES = (-2.0, -1.0, -0.5, 0.5, 1.0, 2.0)
+INT_SLOPES = (0.25, -0.5)
+NORMAL_SLOPES = (0.2, -0.3)
+
+
+def f32(v):
+    """the fp32 number a kernel reads for a Python float, as a float"""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def eval_out_hw(g):
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    if tr:
+        return (H - 1) * s - 2 * p + kh, (W - 1) * s - 2 * p + kw
+    return (H + 2 * p - kh) // s + 1, (W + 2 * p - kw) // s + 1
+
+
+def eval_k(g):
+    """products per output element: Ci kh kw forward; Ci ceil(kh / s) ceil(kw / s) transposed (the fullest stride phase)"""
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    return Ci * cdiv(kh, s) * cdiv(kw, s) if tr else Ci * kh * kw
+
+
+def make_eval_data(kind, g, seed):
+    """x [N,Ci,H,W], w ([Co,Ci,kh,kw]; transposed [Ci,Co,kh,kw]), scale [Co], shift [Co], residual [N,Co,Ho,Wo] (float64; x, w
+    and residual bf16-representable, scale and shift fp32-representable).
+    'int': x integers in [-3, 3]; w = ((idx * 7919) % m) - m // 2 with m the widest of 509 / 127 / 31 / 7 for which
+    2 (K 3 (m // 2)) + 8 + 64 < 2^20 with the case's OWN K = eval_k(g) (the worst case of max |scale| mag + |shift| + |residual|,
+    so the exactness condition holds by construction); scale drawn from +-0.5, +-1, +-2; shift integers in [-8, 8]; residual
+    integers in [-64, 64].
+    'normal': as make_data, with scale = +-U[0.25, 1.75], shift = 0.3 N(0, 1), a bf16-rounded residual ~ N(0, 1)."""
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    Ho, Wo = eval_out_hw(g)
+    gen = torch.Generator().manual_seed(seed)
+    K = eval_k(g)
+    wshape = (Ci, Co, kh, kw) if tr else (Co, Ci, kh, kw)
+    if kind == 'int':
+        m = next(m for m in (509, 127, 31, 7) if 2 * K * 3 * (m // 2) + 8 + 64 < EVAL_LIMIT)
+        idx = torch.arange(Co * Ci * kh * kw, dtype=torch.int64).view(wshape)
+        w = (((idx * 7919) % m) - m // 2).double()
+        ri = lambda lo, hi, *sh: torch.randint(lo, hi + 1, sh, generator=gen).double()
+        scale = torch.tensor(INT_SCALES, dtype=torch.float64)[torch.randint(0, len(INT_SCALES), (Co,), generator=gen)]
+        return dict(x=ri(-3, 3, N, Ci, H, W), w=w, scale=scale, shift=ri(-8, 8, Co), residual=ri(-64, 64, N, Co, Ho, Wo))
+    assert kind == 'normal'
+    rn = lambda *sh: torch.randn(*sh, generator=gen)
+    sign = torch.where(torch.rand(Co, generator=gen) < 0.5, -1.0, 1.0)
+    scale = (sign * (0.25 + 1.5 * torch.rand(Co, generator=gen))).float().double()
+    return dict(x=rb64(rn(N, Ci, H, W)), w=rb64(rn(*wshape) / K ** 0.5), scale=scale, shift=(0.3 * rn(Co)).float().double(),
+                residual=rb64(rn(N, Co, Ho, Wo)))
+
+
+def eval_act_fn(v, act, slope):
+    """a GCC_EVAL_ACT_* id on float64 (slope: the PReLU / LeakyReLU negative-side factor)"""
+    if act == EV_TANH:
+        return torch.tanh(v)
+    neg = slope if act in (EV_PRELU, EV_LRELU) else (0.0 if act == EV_RELU else 1.0)
+    return torch.where(v > 0, v, v * neg)
+
+
+def eval_conv(d, g):
+    """(acc, mag): the convolution (transposed: ref_dgrad's formulation) of x and w, and of |x| and |w|, float64"""
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    if not tr:
+        return F.conv2d(d['x'], d['w'], None, stride=s, padding=p), F.conv2d(d['x'].abs(), d['w'].abs(), None, stride=s, padding=p)
+    Ho, Wo = eval_out_hw(g)
+    size = (N, Co, Ho, Wo)
+    return (torch.nn.grad.conv2d_input(size, d['w'], d['x'], stride=s, padding=p),
+            torch.nn.grad.conv2d_input(size, d['w'].abs(), d['x'].abs(), stride=s, padding=p))
+
+
+def eval_z(d, conv, scale=True, shift=True):
+    """(z, mag_z): z = scale[c] acc + shift[c] (a NULL scale is 1, a NULL shift 0) and |scale| mag + |shift|"""
+    acc, mag = conv
+    z, mz = acc, mag
+    if scale:
+        z, mz = z * d['scale'][None, :, None, None], mz * d['scale'].abs()[None, :, None, None]
+    if shift:
+        z, mz = z + d['shift'][None, :, None, None], mz + d['shift'].abs()[None, :, None, None]
+    return z, mz
+
+
+def ref_eval(d, g, act, residual, slope=0.25, scale=True, shift=True, conv=None):
+    """gcc_conv_fprop_eval in float64: (y, z, mag) with y = act(z) + residual -- the residual is added AFTER the activation --
+    and mag = |scale| conv(|x|, |w|) + |shift| (the residual's magnitude is the caller's to add).  conv: eval_conv(d, g) when the
+    caller already has it."""
+    z, mz = eval_z(d, conv if conv is not None else eval_conv(d, g), scale, shift)
+    y = eval_act_fn(z, act, slope)
+    if residual:
+        y = y + d['residual']
+    return y, z, mz
+
+
+def ref_eval_ex(d, g, act, act2, slope=0.25, scale=True, shift=True, conv=None):
+    """gcc_conv_eval_ex in float64: (y, y2, z, mag) with y = act(z), y2 = act2(z) (None without a second output) -- both from z"""
+    z, mz = eval_z(d, conv if conv is not None else eval_conv(d, g), scale, shift)
+    return eval_act_fn(z, act, slope), (eval_act_fn(z, act2, slope) if act2 is not None else None), z, mz
+
+
+def assert_eval_exact_condition(d, conv, what, residual=True):
+    """max |scale| mag + |shift| (+ |residual|) < 2^20 on the reference alone, before anything from the GPU is looked at (it
+    covers every variant: a NULL scale is 1 <= max |scale|, a NULL shift or residual only lowers the left side)"""
+    top = max(1.0, float(d['scale'].abs().max())) * conv[1] + d['shift'].abs()[None, :, None, None]
+    if residual:
+        top = top + d['residual'].abs()
+    assert float(top.max()) < EVAL_LIMIT, '%s: max |scale| mag + |shift| + |residual| = %.4g is not below 2^20' % (what, float(top.max()))
+    return float(top.max())
+
+
+def assert_eval_data_conditions(z, what):
+    """conditions on the 'int' data (not measurements): a double rounding can only show where an output is not its own bf16
+    rounding, an activation branch only where pre-activations of both signs exist"""
+    differ = float((rb64(z) != z).double().mean())
+    neg = float((z < 0).double().mean())
+    assert differ >= 0.10, '%s: only %.1f %% of the outputs differ from their bf16 rounding' % (what, 100 * differ)
+    assert 0.25 <= neg <= 0.75, '%s: %.1f %% of the pre-activations are negative' % (what, 100 * neg)
+    return differ, neg
+
+
+# fp32 roundings on the way to the value that is stored, as igemm_epilogue (EPI == 1), igemm_epilogue_ex, splitk_epilogue_kernel<true>,
+# splitk_eval_ex_kernel and the ring-walk's EV branch show them: K products accumulated (one rounding per addition, any order), S
+# slices folded (one addition each), and K_EVAL = 4: the scale multiply and the shift add (`sc * acc + sh`: two roundings, one where
+# the compiler fuses them), the activation's multiply by the slope, the residual add.  gcc_conv_eval_ex has no residual: its count
+# is one lower, the bound keeps the common one.
+K_EVAL = 4
+
+
+def bound_eval(ref, mag_z, K, S, act, residual=None):
+    """bf16 output of an eval-mode convolution, per element.  n = K + S + K_EVAL roundings, each relative to at most
+    M = |scale| sum |x w| + |shift| (+ |residual|): the value in front of the bf16 rounding is within A = gamma_n M of ref,
+    gamma_n = n u / (1 - n u), u = 2^-24.  Every activation is 1-Lipschitz (|slope| <= 1), so the pre-activation error carries
+    through unchanged; tanh adds the device function's documented error.  Then one rounding to bf16 of a value within A of ref.
+    mag_z: |scale| sum |x w| + |shift|; residual: the residual tensor (its magnitude is added here) or None."""
+    M = mag_z + (residual.abs() if residual is not None else 0.0)
+    n = (K + S + K_EVAL) * U24
+    A = n / (1.0 - n) * M
+    if act == EV_TANH:
+        A = A + TANH_ERR
+    return A + BF16 * (ref.abs() + A)
+
+
+def old_rule_eval_ex(got, ref):
+    """tests/test_unet_infer_gpu.py test_eval_ex_epilogue_against_fp32: max |got - ref| <= 1e-2 max(max |ref|, 1) + 2^-7 max |ref|
+    over the whole tensor; returns (passes, err / limit)"""
+    top = float(ref.abs().max())
+    err, lim = float((got - ref).abs().max()), 1e-2 * max(top, 1.0) + 2.0 ** -7 * top
+    return err <= lim, err / lim
+
+
+# ---- CPU emulation of the two eval epilogues, with named defects (tests/test_conv_bounds_cpu.py only) ----------------------------
+EVAL_DEFECTS = ('residual_before_act', 'shift_after_round', 'round_before_residual', 'act2_from_act', 'prelu_slope_ignored',
+                'scale_missing_on_fold', 'drop_last_slice', 'pad_lane_gets_shift')
+# the entry a defect can occur in: a residual exists in gcc_conv_fprop_eval alone, a second output in gcc_conv_eval_ex alone
+DEFECT_ENTRIES = dict(residual_before_act=('eval',), round_before_residual=('eval',), act2_from_act=('ex',))
+
+
+def eval_emul_parts(d, g, S):
+    """the fp32 partial sums of eval_emul: S groups of input channels"""
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    x, w = d['x'].float(), d['w'].float()
+    per = cdiv(Ci, S)
+    if tr:
+        return [F.conv_transpose2d(x[:, a:a + per], w[a:a + per], None, stride=s, padding=p) for a in range(0, Ci, per)]
+    return [F.conv2d(x[:, a:a + per], w[:, a:a + per], None, stride=s, padding=p) for a in range(0, Ci, per)]
+
+
+def eval_emul(d, g, entry, act, act2=None, residual=False, slope=0.25, scale=True, shift=True, S=1, defect=None, parts=None):
+    """conv_emul for the eval epilogues: the products accumulated in fp32 in S slices (here: S groups of input channels, another
+    order than any kernel's -- on 'int' data every order gives the same sum) that are folded in fp32, then z = scale acc + shift,
+    the activation(s), the residual after the activation, ONE rounding to bf16.  Returns (y, y2) as float64 of ceil8(Co)
+    channels: the pad lanes Co .. ceil8(Co) are part of what a call writes (exact zeros).
+    Defects: residual_before_act (act(z + residual)); shift_after_round (scale acc rounded to bf16, then the shift, the activation
+    and the store's rounding: two roundings); round_before_residual (act(z) rounded, the residual added, rounded again); act2_from_act (y2 = act2(act(z)));
+    prelu_slope_ignored (the negative side passes unscaled); scale_missing_on_fold (the fold kernel of a split launch skips the
+    scale); drop_last_slice (the fold stops one slice early); pad_lane_gets_shift (the pad lanes are treated as channels with
+    scale 0 but the last channel's shift, or 1 where that is zero)."""
+    assert defect is None or defect in EVAL_DEFECTS
+    assert entry in DEFECT_ENTRIES.get(defect, ('eval', 'ex'))
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    Ho, Wo = eval_out_hw(g)
+    parts = list(parts) if parts is not None else eval_emul_parts(d, g, S)
+    if defect == 'drop_last_slice':
+        assert len(parts) > 1
+        parts = parts[:-1]
+    acc = parts[0]
+    for q in parts[1:]:
+        acc = acc + q
+    col = lambda t: t.float()[None, :, None, None]
+    if scale and not (defect == 'scale_missing_on_fold' and S > 1):
+        acc = acc * col(d['scale'])
+    neg = 1.0 if defect == 'prelu_slope_ignored' else slope
+    rb = lambda t: t.bfloat16().float()
+    if defect == 'shift_after_round':
+        z = rb(acc) + col(d['shift']) if shift else rb(acc)
+    else:
+        z = acc + col(d['shift']) if shift else acc
+    res = d['residual'].float() if residual else None
+    if defect == 'residual_before_act':
+        y = eval_act_fn(z + res, act, neg)
+    else:
+        y = eval_act_fn(z, act, neg)
+        if defect == 'round_before_residual':
+            y = rb(y)
+        if res is not None:
+            y = y + res
+    y2 = None
+    if act2 is not None:
+        y2 = eval_act_fn(eval_act_fn(z, act, neg) if defect == 'act2_from_act' else z, act2, neg)
+
+    def store(v):
+        out = torch.zeros((N, ceil8(Co), Ho, Wo), dtype=torch.float64)
+        out[:, :Co] = rb(v).double()
+        if defect == 'pad_lane_gets_shift':
+            out[:, Co:] = float(d['shift'][Co - 1]) or 1.0
+        return out
+    return store(y), (store(y2) if y2 is not None else None)
+
+
+def eval_expected(ref, Co):
+    """the one right output of an exact eval case over ceil8(Co) lanes: one rounding of the exact value, zeros in the pad lanes"""
+    out = torch.zeros((ref.shape[0], ceil8(Co)) + tuple(ref.shape[2:]), dtype=torch.float64)
+    out[:, :Co] = rb64(ref)
+    return out
+
+
+# ---- eval cases --------------------------------------------------------------------------------------------------------------------
+def _ev_variants(acts, residuals=(False, True), coeffs=((True, True), (False, True), (True, False), (False, False))):
+    return tuple(dict(act=a, slope_i=si, residual=r, scale=sc, shift=sh) for a, si in acts for r in residuals for sc, sh in coeffs)
+
+
+# gcc_conv_fprop_eval, "all": act in NONE, PReLU(first slope), PReLU(second slope), TANH; with and without a residual; scale /
+# shift both, scale NULL, shift NULL, both NULL.  slope_i indexes INT_SLOPES / NORMAL_SLOPES.  TANH runs per element only.
+EV_ALL = _ev_variants(((EV_NONE, 0), (EV_PRELU, 0), (EV_PRELU, 1), (EV_TANH, 0)))
+EV_SR_FIRST = _ev_variants(((EV_PRELU, 0), (EV_PRELU, 1)), residuals=(False,), coeffs=((True, True), (False, True)))
+EV_SR_LAST = _ev_variants(((EV_TANH, 0), (EV_NONE, 0)), residuals=(False,), coeffs=((False, True),))
+EV_DRN = _ev_variants(((EV_NONE, 0),), coeffs=((True, True),))
+
+
+def _xv(act, act2, slope_i, y2='same', scale=True, shift=True):
+    return dict(act=act, act2=act2, slope_i=slope_i, y2=y2, scale=scale, shift=shift)
+
+
+# gcc_conv_eval_ex: (act, act2) in (LRELU, RELU), (RELU, none), (NONE, TANH), (TANH, none), (NONE, LRELU); y2 once in y's buffer
+# at a window of its own ('same') and once in a buffer with another ldy2 ('own').  (LRELU, RELU) runs with both slopes: with a
+# positive slope relu(lrelu(z)) = relu(z), so only the negative one tells act2(act(z)) from act2(z).  A NULL scale and a NULL
+# shift ride on the two single-output variants.
+EX_ALL = (_xv(EV_LRELU, EV_RELU, 0, 'same'), _xv(EV_LRELU, EV_RELU, 1, 'own'), _xv(EV_RELU, None, 0, scale=False),
+          _xv(EV_NONE, EV_TANH, 0, 'own'), _xv(EV_TANH, None, 0, shift=False), _xv(EV_NONE, EV_LRELU, 1, 'same'))
+
+
+def variant_slope(v, kind):
+    """the slope of a variant on 'int' / 'normal' data, as the fp32 number the kernel reads"""
+    return f32((INT_SLOPES if kind == 'int' else NORMAL_SLOPES)[v['slope_i']])
+
+
+def variant_reference(case, d, v, kind, conv):
+    """float64 reference of one variant of a case: dict(y, y2, z, mag, res, slope); res: the residual tensor or None"""
+    slope = variant_slope(v, kind)
+    if case['entry'] == 'eval':
+        y, z, mag = ref_eval(d, case['g'], v['act'], v['residual'], slope, v['scale'], v['shift'], conv)
+        return dict(y=y, y2=None, z=z, mag=mag, res=d['residual'] if v['residual'] else None, slope=slope)
+    y, y2, z, mag = ref_eval_ex(d, case['g'], v['act'], v['act2'], slope, v['scale'], v['shift'], conv)
+    return dict(y=y, y2=y2, z=z, mag=mag, res=None, slope=slope)
+
+
+def variant_emul(case, d, v, kind, S=1, defect=None, parts=None):
+    """eval_emul of one variant of a case"""
+    return eval_emul(d, case['g'], case['entry'], v['act'], v.get('act2'), v.get('residual', False), variant_slope(v, kind), v['scale'],
+                     v['shift'], S=S, defect=defect, parts=parts)
+
+
+def variant_id(v):
+    names = {EV_NONE: 'none', EV_PRELU: 'prelu', EV_TANH: 'tanh', EV_RELU: 'relu', EV_LRELU: 'lrelu'}
+    tag = names[v['act']] + ('' if v.get('act2') is None else '+' + names[v['act2']] + ':' + v['y2'])
+    return '%s slope#%d%s scale %d shift %d' % (tag, v['slope_i'], ' +res' if v.get('residual') else '', v['scale'], v['shift'])
+
+
+def _e(name, entry, g, variants, opts=None, ws=True, **expect):
+    """one eval launch under test.  entry: 'eval' (gcc_conv_fprop_eval) or 'ex' (gcc_conv_eval_ex); g: the 10-tuple above;
+    variants: the epilogues it runs; opts: option name -> value; ws: hand the call its split-K workspace; expect: route (0 igemm
+    un-split, 4 ring-walk, 5 split K + fold), tile, S (K slices) -- asserted BEFORE a number is compared."""
+    return dict(name=name, entry=entry, g=g, variants=variants, opts=opts or {}, ws=ws, expect=expect)
+
+
+def _sq(N, H, W, Ci, Co, k, s, p, tr=False):
+    return (N, H, W, Ci, Co, k, k, s, p, tr)
+
+
+THIN_ON, THIN_OFF = dict(IGEMM_THIN=1), dict(IGEMM_THIN=0)
+EVAL_CASES = (
+    # ---- gcc_conv_fprop_eval: un-split igemm_kernel, each column tile; 391 pixels = three full 128-pixel tiles and a partial one
+    _e('ev-t16-co13', 'eval', _sq(1, 17, 23, 24, 13, 3, 1, 1), EV_ALL, route=0, tile=128016, S=1),
+    _e('ev-t32-co24', 'eval', _sq(1, 17, 23, 24, 24, 3, 1, 1), EV_ALL, route=0, tile=128032, S=1),
+    _e('ev-t64-co64', 'eval', _sq(1, 17, 23, 24, 64, 3, 1, 1), EV_ALL, route=0, tile=128064, S=1),
+    _e('ev-t128-co136', 'eval', _sq(1, 17, 23, 24, 136, 3, 1, 1), EV_ALL, route=0, tile=128128, S=1),     # two column tiles, the second partial
+    # ---- split K + splitk_epilogue_kernel<true>; 5 and 6 slices: both loops of the fold's four-at-a-time sum run
+    _e('ev-split4-co13', 'eval', _sq(1, 6, 7, 128, 13, 3, 1, 1), EV_ALL, route=5, tile=128016, S=4),
+    _e('ev-split4-co64', 'eval', _sq(1, 6, 7, 128, 64, 3, 1, 1), EV_ALL, route=5, tile=128064, S=4),
+    _e('ev-split5-co13', 'eval', _sq(1, 6, 7, 144, 13, 3, 1, 1), EV_ALL, route=5, tile=128016, S=5),
+    _e('ev-split6-co64', 'eval', _sq(1, 6, 7, 192, 64, 3, 1, 1), EV_ALL, route=5, tile=128064, S=6),
+    _e('ev-split5-nows', 'eval', _sq(1, 6, 7, 144, 13, 3, 1, 1), EV_ALL, ws=False, route=0, tile=128016, S=1),
+    # ---- the ring-walk's EV branch (R3_MIN_PIXELS = 8192: these are its smallest) and the same calls with the option off
+    _e('ev-ring-64-64', 'eval', _sq(1, 128, 65, 64, 64, 3, 1, 1), EV_ALL, opts=THIN_ON, route=4),
+    _e('ev-ring-16-24', 'eval', _sq(1, 128, 65, 16, 24, 3, 1, 1), EV_ALL, opts=THIN_ON, route=4),
+    _e('ev-ring-16-20', 'eval', _sq(1, 128, 65, 16, 20, 3, 1, 1), EV_ALL, opts=THIN_ON, route=4),           # Co not a multiple of 8
+    _e('ev-ring-64-64-thin0', 'eval', _sq(1, 128, 65, 64, 64, 3, 1, 1), EV_ALL, opts=THIN_OFF, route=0, tile=128064, S=1),
+    _e('ev-ring-16-24-thin0', 'eval', _sq(1, 128, 65, 16, 24, 3, 1, 1), EV_ALL, opts=THIN_OFF, route=0, tile=128032, S=1),
+    _e('ev-ring-16-20-thin0', 'eval', _sq(1, 128, 65, 16, 20, 3, 1, 1), EV_ALL, opts=THIN_OFF, route=0, tile=128032, S=1),
+    # ---- SRResNet's 9 x 9 first and last layers
+    _e('ev-sr-first', 'eval', _sq(1, 12, 12, 3, 64, 9, 1, 4), EV_SR_FIRST, route=0, tile=128064, S=1),
+    _e('ev-sr-last', 'eval', _sq(1, 12, 12, 64, 3, 9, 1, 4), EV_SR_LAST, route=5, tile=128016, S=17),    # K = 5184: split, 17 = 4 x 4 + 1 slices
+    # ---- DRN geometries: 1 x 1, 3 x 3 stride 2, 1 x 1 stride 2
+    _e('ev-drn-1x1', 'eval', _sq(2, 9, 9, 72, 40, 1, 1, 0), EV_DRN, route=0, tile=128064, S=1),
+    _e('ev-drn-k3s2', 'eval', _sq(1, 15, 17, 32, 64, 3, 2, 1), EV_DRN, route=0, tile=128064, S=1),
+    _e('ev-drn-1x1s2', 'eval', _sq(1, 16, 16, 64, 64, 1, 2, 0), EV_DRN, route=0, tile=128064, S=1),
+    # ---- gcc_conv_eval_ex, forward
+    _e('ex-down-thin', 'ex', _sq(1, 16, 16, 3, 64, 4, 2, 1), EX_ALL, route=0, tile=128064, S=1),
+    _e('ex-down-co512', 'ex', _sq(3, 8, 8, 13, 512, 4, 2, 1), EX_ALL, route=0, tile=128128, S=1),
+    _e('ex-down-split', 'ex', _sq(1, 2, 2, 512, 512, 4, 2, 1), EX_ALL, route=5, tile=128128, S=32),
+    _e('ex-stem-k3s2p0', 'ex', _sq(1, 19, 19, 32, 32, 3, 2, 0), EX_ALL, route=0, tile=128032, S=1),
+    _e('ex-k5', 'ex', _sq(1, 9, 9, 48, 64, 5, 1, 2), EX_ALL, route=5, tile=128064, S=4),
+    _e('ex-1x1', 'ex', _sq(2, 9, 9, 72, 40, 1, 1, 0), EX_ALL, route=0, tile=128064, S=1),
+    _e('ex-rect-1x7', 'ex', (1, 17, 23, 128, 192, 1, 7, 1, 0, False), EX_ALL, route=0, tile=128128, S=1),
+    _e('ex-rect-7x1', 'ex', (1, 23, 17, 128, 192, 7, 1, 1, 0, False), EX_ALL, route=0, tile=128128, S=1),
+    _e('ex-drn-stem7', 'ex', _sq(1, 14, 14, 3, 16, 7, 1, 3), EX_ALL, route=0, tile=128016, S=1),
+    _e('ex-drn-k3', 'ex', _sq(1, 15, 17, 32, 64, 3, 1, 1), EX_ALL, route=0, tile=128064, S=1),
+    # ---- gcc_conv_eval_ex, transposed
+    _e('exT-bottleneck', 'ex', _sq(1, 1, 1, 512, 512, 4, 2, 1, True), EX_ALL, route=5, tile=128128, S=8),
+    _e('exT-thin-co13', 'ex', _sq(3, 4, 4, 512, 13, 4, 2, 1, True), EX_ALL, route=5, tile=128016, S=8),
+    _e('exT-image', 'ex', _sq(1, 16, 16, 64, 3, 4, 2, 1, True), EX_ALL, route=0, tile=128016, S=1),
+    _e('exT-ci13', 'ex', _sq(3, 8, 8, 13, 64, 4, 2, 1, True), EX_ALL, route=0, tile=128064, S=1),
+    _e('exT-sagan-first', 'ex', _sq(2, 1, 1, 128, 512, 4, 1, 0, True), EX_ALL, route=5, tile=128128, S=8),
+)
+EVAL_BY_NAME = {c['name']: c for c in EVAL_CASES}
+assert len(EVAL_BY_NAME) == len(EVAL_CASES), 'case names must be unique'
+
+
+def eval_seed(case):
+    return sum(ord(ch) for ch in case['name']) + sum(int(v) for v in case['g'])
+
+
+def eval_desc(lib_mod, g, ld_in=None, ld_out=None):
+    """the gcc_conv_t of an eval call (default plan).  A transposed call is described as the LAYER whose data gradient it is: the
+    descriptor's x side is the call's output, its y side the call's input."""
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    plan = (0,) * len(lib_mod.PLAN_FIELDS)
+    ld_in, ld_out = ld_in or ceil8(Ci), ld_out or ceil8(Co)
+    if not tr:
+        return lib_mod.conv_t(N, H, W, Ci, Co, kh, kw, s, p, ld_in, 0, ld_out, 0, plan)
+    Ho, Wo = eval_out_hw(g)
+    return lib_mod.conv_t(N, Ho, Wo, Co, Ci, kh, kw, s, p, ld_out, 0, ld_in, 0, plan)
+
+
+def eval_routing(lib_mod, case, d=None, ws=None):
+    """what the library says an eval call of this case runs on: dict(route, need, ws, tile, S, launches, rows, phases).
+    need: gcc_conv_eval_workspace / gcc_conv_eval_ex_workspace; ws: the bytes the call is handed (need, or 0: ws False);
+    tile: gcc_conv_tile under the one-family plan the eval entries use; S: the K slices, read back from the workspace size
+    (bytes = phases x slices x rows x padded columns x 4); launches: the partial tiles and the fold of a split call, else one."""
+    lib = lib_mod.load()
+    g = case['g']
+    N, H, W, Ci, Co, kh, kw, s, p, tr = g
+    tr = int(tr)
+    d = d if d is not None else eval_desc(lib_mod, g)
+    use = case['ws'] if ws is None else ws
+    if case['entry'] == 'eval':
+        need = int(lib.gcc_conv_eval_workspace(C.byref(d)))
+        have = need if use else 0
+        route = int(lib.gcc_conv_eval_route(C.byref(d), have))
+    else:
+        need = int(lib.gcc_conv_eval_ex_workspace(C.byref(d), tr))
+        have = need if use else 0
+        route = int(lib.gcc_conv_eval_ex_route(C.byref(d), tr, have))
+    one = type(d).from_buffer_copy(d)
+    one.plan.tile_families = 1
+    tile = int(lib.gcc_conv_tile(C.byref(one), tr))
+    Ho, Wo = eval_out_hw(g)
+    phases = s * s if tr else 1
+    rows = N * cdiv(Ho, s) * cdiv(Wo, s) if tr else N * Ho * Wo
+    bc = tile % 1000
+    S = have // (phases * rows * cdiv(Co, bc) * bc * 4) if route == 5 else 1
+    return dict(route=route, need=need, ws=have, tile=tile, S=int(S), launches=2 if route == 5 else 1, rows=rows, phases=phases)
+
+
+def check_eval_expect(case, r, launches=None):
+    """the case's intended route against what the library reports (a mismatch is a failure, never a skip); launches: the
+    gcc_launch_count of the call, when it ran"""
+    e, name = case['expect'], case['name']
+    assert r['route'] == e['route'], '%s: route %d, intended %s' % (name, r['route'], e['route'])
+    assert (r['route'] == 5) == (r['ws'] > 0 and r['S'] > 1), '%s: route %d with a workspace of %d bytes, %d slices' % (name, r['route'], r['ws'], r['S'])
+    if 'tile' in e:
+        assert r['tile'] == e['tile'], '%s: tile %d, intended %d' % (name, r['tile'], e['tile'])
+    if 'S' in e:
+        assert r['S'] == e['S'], '%s: %d K slices, intended %d' % (name, r['S'], e['S'])
+    if launches is not None:
+        assert launches == r['launches'], '%s: %d launches, intended %d' % (name, launches, r['launches'])

@@ -18,7 +18,11 @@ Outcome of the table (printed by test_defect_table, copied to docs/lab_notebook.
     data of one sign (activations behind a ReLU against weights with a mean: every output is about K mean(x) mean(w), the lost
     k-step is 64 / 8192 = 0.8 % of it, under the rule's 1.2 %).  On ZERO-mean data at K = 8192 the old rule does reject a lost
     k-step (its error, sigma / 11 per element, is 6 times the limit somewhere in the tensor): the rule looks at the largest
-    error, so "most elements stay within it" does not let the defect through there.  Both rows are in the table."""
+    error, so "most elements stay within it" does not let the defect through there.  Both rows are in the table.
+
+The checks of tests/test_conv_eval_exact_gpu.py (the inference convolutions) are examined the same way in the last section of
+this file: routes, exactness and data conditions, the emulation's bits and bound, and the defect table of the two eval
+epilogues against the rule of tests/test_unet_infer_gpu.py test_eval_ex_epilogue_against_fp32."""
 import pytest
 import torch
 
@@ -167,3 +171,128 @@ def test_halo_legs_table_of_the_one_shape_tests():
                     ops.set_plan()
                 assert got == want, ((N, H, W, Ci, Co, s), hc, got)
     assert lib.gcc_conv_halo_mode(None, 0, 0) == 0
+
+
+# ---- the eval-mode convolutions (tests/test_conv_eval_exact_gpu.py), examined without a GPU ------------------------------------
+# 1. every case is on the route, tile and K-slice count its row names (host code), its 'int' data meets the exactness condition
+#    and the two data conditions on the reference alone, the fp32 emulation gives the expected bits for every variant that has
+#    exact bits, and on 'normal' data the emulation stays inside bound_eval;
+# 2. the defect table of the two eval epilogues (tests/_conv_exact.py eval_emul): every named defect changes bits of the exact
+#    check's expectation; the rule of tests/test_unet_infer_gpu.py test_eval_ex_epilogue_against_fp32 accepts act2_from_act and
+#    round_before_residual (asserted) and whatever else the table prints.
+EVAL_IDS = [c['name'] for c in X.EVAL_CASES]
+
+
+def _exact_variant(v):
+    """has the variant exact bits on 'int' data?  tanh of a number is no fp32 number: that output is held per element"""
+    return v['act'] != X.EV_TANH
+
+
+@pytest.mark.parametrize('case', X.EVAL_CASES, ids=EVAL_IDS)
+def test_eval_case_route_conditions_and_own_bound(case):
+    g, name = case['g'], case['name']
+    with X.forced_options(_lib, case['opts']):
+        r = X.eval_routing(_lib, case)
+        X.check_eval_expect(case, r)
+        if r['need']:
+            assert X.eval_routing(_lib, case, ws=False)['route'] == 0, 'without a workspace the call must run un-split'
+    seed = X.eval_seed(case)
+    K, S = X.eval_k(g), r['S']
+    # exact data: the condition and the data conditions on the reference alone, then the emulation's bits
+    d = X.make_eval_data('int', g, seed)
+    conv = X.eval_conv(d, g)
+    top = X.assert_eval_exact_condition(d, conv, name, residual=case['entry'] == 'eval')
+    differ, neg = X.assert_eval_data_conditions(X.eval_z(d, conv)[0], name)
+    print('DATA %s route %d tile %d K-slices %d | 2^20 / worst magnitude %.1f | %.0f %% of the outputs differ from their bf16 rounding | '
+          '%.0f %% negative pre-activations' % (name, r['route'], r['tile'], S, X.EVAL_LIMIT / top, 100 * differ, 100 * neg))
+    parts = X.eval_emul_parts(d, g, max(S, 2))
+    for v in case['variants']:
+        ref = X.variant_reference(case, d, v, 'int', conv)
+        y, y2 = X.variant_emul(case, d, v, 'int', parts=parts)
+        if _exact_variant(v):
+            assert torch.equal(y, X.eval_expected(ref['y'], g[4])), '%s %s: an fp32 sum in another order must give the same bits' % (name, X.variant_id(v))
+        if ref['y2'] is not None and v['act2'] != X.EV_TANH:
+            assert torch.equal(y2, X.eval_expected(ref['y2'], g[4])), '%s %s: y2' % (name, X.variant_id(v))
+    # normal data: the emulation inside the bound
+    n = X.make_eval_data('normal', g, seed + 2)
+    conv = X.eval_conv(n, g)
+    parts = X.eval_emul_parts(n, g, max(S, 2))
+    worst = 0.0
+    for v in case['variants']:
+        ref = X.variant_reference(case, n, v, 'normal', conv)
+        y, y2 = X.variant_emul(case, n, v, 'normal', parts=parts)
+        worst = max(worst, within(y[:, :g[4]], ref['y'], X.bound_eval(ref['y'], ref['mag'], K, max(S, 2), v['act'], ref['res']), name + ' ' + X.variant_id(v)))
+        if ref['y2'] is not None:
+            worst = max(worst, within(y2[:, :g[4]], ref['y2'], X.bound_eval(ref['y2'], ref['mag'], K, max(S, 2), v['act2']), name + ' y2 ' + X.variant_id(v)))
+    report('eval-emul', (name,), worst=worst)
+
+
+# the small exact case of each entry the defects run on: 4 K slices, 13 output channels (three pad lanes), a residual, the negative
+# slope.  act2_from_act needs (LRELU, RELU) with the NEGATIVE slope: relu(lrelu(z)) = relu(z) for a positive one.
+DEFECT_G = (1, 6, 7, 128, 13, 3, 3, 1, 1, False)
+DEFECT_CASE = dict(eval=dict(name='defect-eval', entry='eval', g=DEFECT_G),
+                   ex=dict(name='defect-ex', entry='ex', g=DEFECT_G))
+DEFECT_VARIANT = dict(eval=dict(act=X.EV_PRELU, slope_i=1, residual=True, scale=True, shift=True),
+                      ex=dict(act=X.EV_LRELU, act2=X.EV_RELU, slope_i=1, y2='same', scale=True, shift=True))
+# the old test's own variant of the second output: (LRELU, RELU) with its slope 0.2 -- index 0 of NORMAL_SLOPES
+OLD_EX_VARIANT = dict(act=X.EV_LRELU, act2=X.EV_RELU, slope_i=0, y2='same', scale=True, shift=True)
+OLD_RULE_MUST_ACCEPT = ('act2_from_act', 'round_before_residual')
+DEFECT_ROWS = [(df, e) for df in X.EVAL_DEFECTS for e in X.DEFECT_ENTRIES.get(df, ('eval', 'ex'))]
+
+
+def _old_rule_row(case, n, v, defect, S):
+    """the old rule on 'normal' data with positive scales (the old test's), on both outputs: (accepted, worst err / limit)"""
+    n = dict(n, scale=n['scale'].abs())
+    conv = X.eval_conv(n, case['g'])
+    ref = X.variant_reference(case, n, v, 'normal', conv)
+    y, y2 = X.variant_emul(case, n, v, 'normal', S=S, defect=defect)
+    Co = case['g'][4]
+    rows = [X.old_rule_eval_ex(y[:, :Co], ref['y'])] + ([X.old_rule_eval_ex(y2[:, :Co], ref['y2'])] if y2 is not None else [])
+    return all(ok for ok, _ in rows), max(ratio for _, ratio in rows)
+
+
+@pytest.mark.parametrize('defect,entry', DEFECT_ROWS, ids=['%s-%s' % r for r in DEFECT_ROWS])
+def test_eval_defect_table(defect, entry):
+    case, v, S = DEFECT_CASE[entry], DEFECT_VARIANT[entry], 4
+    g, Co = case['g'], DEFECT_G[4]
+    K = X.eval_k(g)
+    # the defect-free emulation meets the exact check ...
+    d = X.make_eval_data('int', g, 4242)
+    conv = X.eval_conv(d, g)
+    X.assert_eval_exact_condition(d, conv, case['name'])
+    X.assert_eval_data_conditions(X.eval_z(d, conv)[0], case['name'])
+    ref = X.variant_reference(case, d, v, 'int', conv)
+    want = [X.eval_expected(ref['y'], Co)] + ([X.eval_expected(ref['y2'], Co)] if ref['y2'] is not None else [])
+    good = [t for t in X.variant_emul(case, d, v, 'int', S=S) if t is not None]
+    assert all(torch.equal(a, b) for a, b in zip(good, want)), 'the defect-free emulation must give the expected bits'
+    # ... and bound_eval on normal data
+    n = X.make_eval_data('normal', g, 4243)
+    nconv = X.eval_conv(n, g)
+    nref = X.variant_reference(case, n, v, 'normal', nconv)
+    ny, ny2 = X.variant_emul(case, n, v, 'normal', S=S)
+    assert within(ny[:, :Co], nref['y'], X.bound_eval(nref['y'], nref['mag'], K, S, v['act'], nref['res']), 'defect-free y') <= 1.0
+    if ny2 is not None:
+        assert within(ny2[:, :Co], nref['y2'], X.bound_eval(nref['y2'], nref['mag'], K, S, v['act2']), 'defect-free y2') <= 1.0
+    # every defect changes bits of the exact check's expectation
+    bad = [t for t in X.variant_emul(case, d, v, 'int', S=S, defect=defect) if t is not None]
+    changed = sum(int((a != b).sum()) for a, b in zip(bad, want))
+    assert changed > 0, 'the exact check must reject %s on %s' % (defect, entry)
+    # the per-element bound on normal data
+    by, by2 = X.variant_emul(case, n, v, 'normal', S=S, defect=defect)
+    ratio = float(((by[:, :Co] - nref['y']).abs() / X.bound_eval(nref['y'], nref['mag'], K, S, v['act'], nref['res'])).max())
+    if by2 is not None:
+        ratio = max(ratio, float(((by2[:, :Co] - nref['y2']).abs() / X.bound_eval(nref['y2'], nref['mag'], K, S, v['act2'])).max()))
+    if defect == 'pad_lane_gets_shift':
+        ratio = float('inf') if float(by[:, Co:].abs().max()) > 0 else ratio          # the pad lanes' bound is zero
+    # the old rule: on this test's variant, and for the second output also on the old test's own variant (slope 0.2)
+    assert _old_rule_row(case, n, v, None, S)[0], 'the old rule accepts the defect-free emulation'
+    old_ok, old_ratio = _old_rule_row(case, n, v, defect, S)
+    line = 'EVAL-DEFECT %-22s %-4s | exact check FAILS (%d elements) | bound %s (worst err / bound %.3g) | old rule %s (err / limit %.3g)' % (
+        defect, entry, changed, 'FAILS' if ratio > 1 else 'passes', ratio, 'passes' if old_ok else 'FAILS', old_ratio)
+    if defect == 'act2_from_act':
+        own_ok, own_ratio = _old_rule_row(case, n, OLD_EX_VARIANT, defect, S)
+        line += ' | old rule on the old test\'s own (LRELU 0.2, RELU): %s (err / limit %.3g)' % ('passes' if own_ok else 'FAILS', own_ratio)
+        old_ok = own_ok
+    print(line)
+    if defect in OLD_RULE_MUST_ACCEPT:
+        assert old_ok, 'the old rule was expected to accept %s' % defect

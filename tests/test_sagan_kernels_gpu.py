@@ -555,3 +555,77 @@ def test_attention_training_kernels_refuse_bad_arguments_before_launching():
     assert lib.gcc_launch_count(0) == 0
     assert fwd(512, 64) == 0 and bwd(512, 64) == 0                                                  # the limits themselves run
     torch.cuda.synchronize()
+
+
+# ---- inference attention (gcc_attention_infer) ---------------------------------------------------------------------------------
+# The smallest shape whose call can split its keys: attn_infer_slices needs at least 4 steps of 32 keys (N >= 97) on a grid
+# below 128 workgroups.  N = 97 also leaves one key in the last step.  The host query decides, not this comment.
+INFER_SPLIT_CASE = (1, 8, 1, 1, 97)
+INFER_CASES = [c for c, _ in ATTN_CASES] + [c for c in SLICE_CASES if c not in dict(ATTN_CASES)] + [INFER_SPLIT_CASE]
+# the crafted late-row-maximum data and a negative gamma: on the channel-slice cases, the case with one key in its second step,
+# and the split case
+INFER_VARIANT_CASES = SLICE_CASES + [(1, 72, 9, 3, 11), INFER_SPLIT_CASE]
+INFER_RUNS = [(c, 'plain') for c in INFER_CASES] + [(c, v) for c in INFER_VARIANT_CASES for v in ('crafted', 'negative-gamma')]
+
+
+def _infer_run(case, c, split, wide=True):
+    """one gcc_attention_infer call; wide: x and y are channel slices at lane 8 of buffers filled with 7.0 (y's pad lanes too).
+    Returns y [B, C, N] on the CPU, the whole y buffer, the route the host query names and the launches counted."""
+    ops = _ops()
+    B, Cc, C8, H, W = case
+    N = H * W
+    c8p, cp = ops.ceil8(C8), ops.ceil8(Cc)
+    offs, width = (0, c8p, 2 * c8p), 2 * c8p + cp
+    qkv = ops.new_act(B, width, H, W, DEV)
+    for t, off in ((c['q'], 0), (c['k'], c8p), (c['v'], 2 * c8p)):
+        ops.cslice(qkv, off, t.shape[1]).copy_(t.bfloat16().to(DEV))
+    if wide:
+        _, xd = _wide(ops, B, Cc, H, W, src=c['x'])
+        y_w, y = _wide(ops, B, Cc, H, W)
+    else:
+        xd = to_dev(c['x'])
+        y_w = y = ops.new_act(B, Cc, H, W, DEV)
+        torch.as_strided(y, (B, cp, H, W), y.stride()).fill_(7.0)
+    gd = torch.tensor([c['gamma']], device=DEV)
+    route = ops.attention_infer(qkv, offs, xd, gd, Cc, C8, y, split=split, route_only=True)
+    torch.cuda.synchronize()
+    ops.lib().gcc_launch_count(1)
+    ops.attention_infer(qkv, offs, xd, gd, Cc, C8, y, split=split)
+    launches = int(ops.lib().gcc_launch_count(1))
+    torch.cuda.synchronize()
+    return to_cpu(y).reshape(B, Cc, N), y_w, route, launches
+
+
+@pytest.mark.parametrize('case,variant', INFER_RUNS, ids=_attn_id)
+def test_attention_infer_against_float64(case, variant):
+    """y of the inference kernel per element against the float64 reference of _attn_case, with the bound the training forward
+    is held to for the same y: 2^-7 (|gamma| sum_j A_ij |v_jc| + |x|).  Both routes (split=False: one launch; split=True: the
+    key-split launch and its fold wherever gcc_attention_infer_workspace is non-zero), x and y as channel slices of
+    sentinel-filled buffers (pad lanes C .. ceil8(C) of y come out zero, the lanes beside the slice stay), the same bits on
+    buffers of their own; the crafted late-row-maximum data; a negative gamma."""
+    ops = _ops()
+    lib = ops.lib()
+    B, Cc, C8, H, W = case
+    N, cp = H * W, ops.ceil8(Cc)
+    c = _attn_case(case, crafted=variant == 'crafted', gamma=-0.45 if variant == 'negative-gamma' else 0.7)
+    ref = c['ref']
+    need = int(lib.gcc_attention_infer_workspace(B, N, Cc, C8))
+    if case == INFER_SPLIT_CASE:
+        assert need > 0 and int(lib.gcc_attention_infer_workspace(B, N - 1, Cc, C8)) == 0, 'the smallest split shape along its axis'
+    seen, r = set(), {}
+    for split in (False, True):
+        y, y_w, route, launches = _infer_run(case, c, split)
+        assert launches == route == (2 if split and need else 1), (case, split, route, launches, need)
+        seen.add(route)
+        what = 'attention_infer %s %s route %d' % (case, variant, route)
+        r['route%d' % route] = within(y, ref['y'], 2.0 ** -7 * ref['mag_y'], what)
+        full = full_view(y_w)
+        assert bool((full[:, :8] == 7.0).all()) and bool((full[:, 8 + cp:] == 7.0).all()), what + ': channels beside the slice changed'
+        if cp > Cc:
+            assert float(full[:, 8 + Cc:8 + cp].abs().max()) == 0.0, what + ': pad channels of y are not zero'
+        plain, _, _, _ = _infer_run(case, c, split, wide=False)
+        assert torch.equal(plain, y), what + ': y differs on slices'
+    if need:
+        assert seen == {1, 2}, (case, seen)
+    print('ROUTE attention_infer %s %s routes %s workspace %d' % (_id(case), variant, sorted(seen), need))
+    _report('test_attention_infer_against_float64', case + (variant,), **r)
