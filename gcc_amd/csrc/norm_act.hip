@@ -2184,6 +2184,25 @@ extern "C" int gcc_dw_inorm_route(const gcc_dw_inorm_t* d) {
     return rc == GCC_OK ? 1 : rc;
 }
 
+// the plan of the launch gcc_dw_inorm_fwd would make, from the launcher's own dw_inorm_prepare (nothing launched)
+extern "C" int gcc_dw_inorm_plan(const gcc_dw_inorm_t* d, int what) {
+    DwInArgs da;
+    const int rc = dw_inorm_prepare(d, &da);
+    if (rc != GCC_OK) return rc;
+    const InGridArgs& ga = da.g1;
+    switch (what) {
+        case GCC_DWIN_PLAN_S: return ga.S;
+        case GCC_DWIN_PLAN_S1: return ga.S1;
+        case GCC_DWIN_PLAN_G: return ga.G;
+        case GCC_DWIN_PLAN_ROWS: return ga.rows;
+        case GCC_DWIN_PLAN_CG: return ga.CG;
+        case GCC_DWIN_PLAN_CHG: return ga.CHg;
+        case GCC_DWIN_PLAN_PL: return 256 / ga.CHP;
+        case GCC_DWIN_PLAN_TILE: return da.tile;
+        default: return GCC_ERR_BAD_ARG;
+    }
+}
+
 extern "C" int gcc_dw_inorm_fwd(const gcc_dw_inorm_t* d, gcc_stream_t stream) {
     GCC_ENTER();
     if (gcc_device_error(0)) return GCC_ERR_LAUNCH;      // a bounded spin of an earlier launch expired: its results were wrong

@@ -1566,6 +1566,19 @@ def dw_inorm_route(mode, x, w, y, r=None, u_out=None, workspace=None):
     return lib().gcc_dw_inorm_route(C.byref(dw_inorm_desc(mode, x, w, y, r, u_out, workspace=workspace)))
 
 
+def dw_inorm_plan(mode, x, w, y, r=None, u_out=None, workspace=None):
+    """the plan gcc_dw_inorm_fwd would launch with, from the launcher's own preparation (gcc_dw_inorm_plan): a dict of S, S1, G,
+    rows, CG, CHg, PL and tile, or the (negative) code of a declined launch"""
+    d = dw_inorm_desc(mode, x, w, y, r, u_out, workspace=workspace)
+    out = {}
+    for name, what in _lib.DWIN_PLAN.items():
+        v = lib().gcc_dw_inorm_plan(C.byref(d), what)
+        if v < 0:
+            return v
+        out[name] = v
+    return out
+
+
 def dw_inorm(mode, x, w, y, r=None, u_out=None, eps=1e-5, workspace=None):
     """y = InstanceNorm(dw3x3(ReflectionPad2d(1)(u))) in one launch (gcc_dw_inorm_fwd).  mode DWIN_PLAIN: u = x;
     DWIN_NORM_RELU: u = relu(IN(x)); DWIN_RESIDUAL: u = r + IN(x), stored to u_out.  w: the fp32 master [C, 1, 3, 3]"""

@@ -352,6 +352,14 @@ typedef struct {
 } gcc_dw_inorm_t;
 int gcc_dw_inorm_fwd(const gcc_dw_inorm_t* d, gcc_stream_t stream);
 int gcc_dw_inorm_route(const gcc_dw_inorm_t* d);   /* 1: one launch; < 0: the code gcc_dw_inorm_fwd returns (nothing launched) */
+/* One number of the plan the launch would use, answered by the launcher's own preparation (nothing launched): workgroups per
+ * (image, channel group) S, workgroups one workgroup folds S1, exchange groups G, pixels per workgroup `rows`, channel groups per
+ * image CG, 16-byte chunks per group CHg, pixel lanes per workgroup PL, pixels per LDS tile of a sweep.  < 0: the code
+ * gcc_dw_inorm_route returns where the launch is declined; GCC_ERR_BAD_ARG for an unknown `what`.  Introspection for tests.
+ * Added without a GCC_HIP_ABI bump (an addition). */
+enum { GCC_DWIN_PLAN_S = 0, GCC_DWIN_PLAN_S1 = 1, GCC_DWIN_PLAN_G = 2, GCC_DWIN_PLAN_ROWS = 3, GCC_DWIN_PLAN_CG = 4,
+       GCC_DWIN_PLAN_CHG = 5, GCC_DWIN_PLAN_PL = 6, GCC_DWIN_PLAN_TILE = 7 };
+int gcc_dw_inorm_plan(const gcc_dw_inorm_t* d, int what);
 /* its backward: dx = rstd (dz - mean(dz) - xhat mean(dz xhat)) with dz = g act'(y) (y NULL: the activation output is
  * recomputed from x); dx may alias g. */
 int gcc_inorm_bwd(const void* x, int ldx, const void* y, int ldy, const void* g, int ldg, void* dx, int lddx, int C, int HW,
