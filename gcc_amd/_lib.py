@@ -111,6 +111,9 @@ POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2     # include/gcc_hip.h G
 DWIN_PLAIN, DWIN_NORM_RELU, DWIN_RESIDUAL = 0, 1, 2        # include/gcc_hip.h GCC_DWIN_*
 DW_INORM_WORKSPACE_BYTES = 4096 + (3 << 20)                # include/gcc_hip.h GCC_DW_INORM_WORKSPACE_BYTES
 DWIN_PLAN = dict(S=0, S1=1, G=2, rows=3, CG=4, CHg=5, PL=6, tile=7)      # include/gcc_hip.h GCC_DWIN_PLAN_*
+# include/gcc_hip.h GCC_CONVBN_PLAN_* (gcc_conv_bn_act_plan); the names from S on exist on route 2 only
+CONVBN_PLAN = dict(route=0, ksplit=1, launches=2, S=3, S1=4, G=5, rows=6, CG=7, CHg=8, PL=9, PPT=10)
+CONVBN_PLAN_GRID = ('S', 'S1', 'G', 'rows', 'CG', 'CHg', 'PL', 'PPT')
 
 
 class dw_inorm_t(C.Structure):
@@ -271,6 +274,7 @@ PROTOTYPES = {
     'gcc_dw_inorm_route': (_I, [C.POINTER(dw_inorm_t)]),
     'gcc_dw_inorm_plan': (_I, [C.POINTER(dw_inorm_t), _I]),
     'gcc_conv_bn_act': (_I, [C.POINTER(conv_t), _I, _P, _P, _P, C.POINTER(bn_t), C.POINTER(bnact_t), _P, _I, _I, _P, _I, _I, _P, _Z, _P]),
+    'gcc_conv_bn_act_plan': (_I, [C.POINTER(conv_t), _I, C.POINTER(bn_t), _I]),
     'gcc_bnact_bwd_workspace': (_Z, [_I, _Z]),
     'gcc_bnact_bwd': (_I, [C.POINTER(bnact_bwd_t), _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I,
                            _I, _Z, _P, _Z, _P]),

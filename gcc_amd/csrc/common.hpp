@@ -273,6 +273,9 @@ struct BnFoldDesc {
     void* ws; size_t ws_bytes;                                     // GCC_INORM_WORKSPACE_BYTES, zero-filled once, one stream
 };
 int gcc_internal_bn_fold_grid(const BnFoldDesc* d, hipStream_t st);      // GCC_ERR_UNSUPPORTED: geometry outside the plan
+// the plan of that launch (gcc_conv_bn_act_plan): grid_exchange's layout, rows per workgroup, PPT of the kernel instantiation
+struct BnFoldPlan { int S, S1, G, rows, CG, CHg, PL, PPT; };
+int gcc_internal_bn_fold_grid_plan(const BnFoldDesc* d, BnFoldPlan* out);      // the launcher's own code; nothing launched
 
 // XCD-aware remap of a linear workgroup id (8 XCDs, round-robin dispatch): logical tiles that are
 // adjacent end up on the same XCD (shared L2).  Bijective for any nwg.

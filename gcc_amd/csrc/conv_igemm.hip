@@ -1116,6 +1116,36 @@ bool gcc_internal_ring3_routed(const gcc_conv_t* c, int dgrad, const gcc_epilogu
 
 // cap on the fp32 partial tiles of a split BatchNorm layer (gcc_internal_igemm's fold, gcc_conv_bn_act's fused fold)
 constexpr size_t FUSE_BN_PARTIAL_BYTES = (size_t)4096 * 1024;
+// ... halved (rounding up) while more than four slices are over it: fewer leave the partial-tile launch with a handful of
+// workgroups (a plan of 9 or 10 slices ends at 3)
+static void cap_bn_slices(SplitPlan* sp, size_t per_slice, int nk) {
+    int ks = sp->ksplit;
+    while (ks > 4 && per_slice * ks > FUSE_BN_PARTIAL_BYTES) ks = (ks + 1) / 2;
+    if (ks != sp->ksplit) { sp->kper = cdiv(nk, ks); sp->ksplit = cdiv(nk, sp->kper); }
+}
+// The split-K decision of a batch-1 launch on the 128-pixel tiles that has a caller workspace (gcc_internal_igemm; the launch
+// count gcc_conv_bn_act_plan reports).  fold_stats: split launch with raw partial tiles + splitk_fold_stats_kernel.
+struct IgemmSplit { SplitPlan sp; bool split, fold_stats; };
+static IgemmSplit igemm_split(const gcc_conv_t* c, int dgrad, const TilePlan& tp, int phases, size_t max_rows, int Cpad, int Cout,
+                              bool stats, const void* ws, size_t ws_bytes, int rows_alloc) {
+    const int nk = conv_nk(c, dgrad);
+    IgemmSplit r = {{1, nk}, false, false};
+    if (tp.BP != 128 || !ws) return r;
+    SplitPlan sp = plan_ksplit((long)tp.mtiles * tp.ntiles * phases, nk, tp.max_slices);
+    // a BatchNorm layer's slices are all read back by the fold kernel: capped at FUSE_BN_PARTIAL_BYTES of partial tiles
+    if (sp.ksplit > 4 && stats) cap_bn_slices(&sp, (size_t)phases * max_rows * Cpad * sizeof(float), nk);
+    const size_t need = (size_t)phases * sp.ksplit * max_rows * Cpad * sizeof(float);
+    if (sp.ksplit > 1 && need <= ws_bytes && (((uintptr_t)ws) & 15) == 0) {
+        r.sp = sp; r.split = true;
+        r.fold_stats = stats && ceil8(Cout) / 8 <= 256 && rows_alloc == fold_wpp(max_rows, phases) * phases;
+    }
+    return r;
+}
+// may the launch that writes `rows` statistic rows finalize them itself (TailFin)?
+static bool tail_fin_ok(const gcc_bn_t* bnf, int rows, int rows_alloc, int Cout) {
+    if (!bnf || !bnf->finalize_in_launch || !bnf->tail_ws || (((uintptr_t)bnf->tail_ws) & 15) || rows != rows_alloc) return false;
+    return !(tail_ws_bytes(rows, Cout) > TAIL_TICKET_BYTES + TAIL_GROUP_BYTES || bnf->tail_ws_bytes < TAIL_TICKET_BYTES + TAIL_GROUP_BYTES);
+}
 
 int gcc_internal_igemm(const gcc_conv_t* c, int dgrad, const void* src, const void* w, void* dst, const gcc_epilogue_t* ep,
                        int batch, long src_bstride, long wgt_bstride, long dst_bstride, hipStream_t st) {
@@ -1221,8 +1251,7 @@ int gcc_internal_igemm(const gcc_conv_t* c, int dgrad, const void* src, const vo
     const int rows_alloc = p.stats ? gcc_conv_stat_tiles(c, dgrad) : 0;
     auto make_tail = [&](int rows, int wgs_per_row, TailFin* f) -> bool {
         *f = TailFin{};
-        if (!bnf || !bnf->finalize_in_launch || !bnf->tail_ws || (((uintptr_t)bnf->tail_ws) & 15) || rows != rows_alloc) return false;
-        if (tail_ws_bytes(rows, p.Cout) > TAIL_TICKET_BYTES + TAIL_GROUP_BYTES || bnf->tail_ws_bytes < TAIL_TICKET_BYTES + TAIL_GROUP_BYTES) return false;
+        if (!tail_fin_ok(bnf, rows, rows_alloc, p.Cout)) return false;
         f->tickets = (unsigned*)bnf->tail_ws; f->grp = (double*)((char*)bnf->tail_ws + TAIL_TICKET_BYTES);
         f->rows = rows; f->wgs_per_row = wgs_per_row; f->count = bnf->count; f->eps = bnf->eps; f->momentum = bnf->momentum;
         f->gamma = bnf->gamma; f->beta = bnf->beta; f->running_mean = bnf->running_mean; f->running_var = bnf->running_var;
@@ -1264,23 +1293,13 @@ int gcc_internal_igemm(const gcc_conv_t* c, int dgrad, const void* src, const vo
     }
     float* stats_out = p.stats;
     bool fold_stats = false;         // split launch + splitk_fold_stats_kernel (statistics rows: phases x fold_wpp)
-    if (batch == 1 && tp.BP == 128 && ep && ep->workspace) {
-        SplitPlan sp = plan_ksplit((long)p.mtiles_max * p.ntiles * phases, conv_nk(c, dgrad), tp.max_slices);
-        if (sp.ksplit > 4 && stats_out) {
-            // a BatchNorm layer's slices are all read back by the fold kernel: cap them at FUSE_BN_PARTIAL_BYTES of partial
-            // tiles, never below four (fewer leave the partial-tile launch with a handful of workgroups)
-            const size_t per_slice = (size_t)phases * max_rows * p.Cpad * sizeof(float);
-            const size_t cap = FUSE_BN_PARTIAL_BYTES;
-            const int nk = conv_nk(c, dgrad);
-            int ks = sp.ksplit;
-            while (ks > 4 && per_slice * ks > cap) ks = (ks + 1) / 2;
-            if (ks != sp.ksplit) { sp.kper = cdiv(nk, ks); sp.ksplit = cdiv(nk, sp.kper); }
-        }
-        const size_t need = (size_t)phases * sp.ksplit * max_rows * p.Cpad * sizeof(float);
-        if (sp.ksplit > 1 && need <= ep->workspace_bytes && (((uintptr_t)ep->workspace) & 15) == 0) {
-            p.ksplit = sp.ksplit; p.kper = sp.kper; p.partial = (float*)ep->workspace;
+    if (batch == 1 && ep) {
+        const IgemmSplit is = igemm_split(c, dgrad, tp, phases, max_rows, p.Cpad, p.Cout, stats_out != nullptr, ep->workspace,
+                                          ep->workspace_bytes, rows_alloc);
+        if (is.split) {
+            p.ksplit = is.sp.ksplit; p.kper = is.sp.kper; p.partial = (float*)ep->workspace;
             p.stats = nullptr;       // statistics are taken while the slices are folded
-            fold_stats = stats_out && ceil8(p.Cout) / 8 <= 256 && rows_alloc == fold_wpp(max_rows, phases) * phases;
+            fold_stats = is.fold_stats;
             if (fold_stats) p.raw_partial = 1;
         }
     }
@@ -1526,6 +1545,78 @@ extern "C" size_t gcc_conv_bn_act_workspace(const gcc_conv_t* c, int dgrad) {
     return al256(gcc_conv_workspace(c, dgrad)) + al256((size_t)gcc_conv_stat_tiles(c, dgrad) * 2 * Cout * sizeof(float));
 }
 
+// The decision of gcc_conv_bn_act, shared by the launch and by gcc_conv_bn_act_plan: tile, K split behind the slice cap, which
+// of the three routes (0: gcc_internal_igemm with statistic rows + gcc_bnact_fwd; 1: partial tiles + splitk_bn_act_kernel; 2:
+// partial tiles + bn_fold_grid_kernel, decided last by gcc_internal_bn_fold_grid's own preparation).
+struct ConvBnDecision {
+    int Cout, phases, nk, Ho, Wo, fuse;
+    size_t max_rows, split_bytes;
+    TilePlan tp; SplitPlan sp;
+    bool routed, grid_ws, fused;       // fused: routes 1 / 2 (split launch with raw partial tiles)
+};
+static int conv_bn_decide(const gcc_conv_t* c, int dgrad, const gcc_bn_t* bn, ConvBnDecision* d) {
+    const int rc = check_conv(c);
+    if (rc) return rc;
+    if (!bn || !bn->scale || !bn->shift || bn->count <= 0) return GCC_ERR_BAD_ARG;
+    d->Cout = dgrad ? c->Ci : c->Co;
+    d->phases = dgrad ? c->stride * c->stride : 1;
+    d->split_bytes = al256(gcc_conv_workspace(c, dgrad));
+    d->Ho = gcc_conv_out(c->H, c->KH, c->stride, c->pad); d->Wo = gcc_conv_out(c->W, c->KW, c->stride, c->pad);
+    // which plan would the conv take?  (same predicates as gcc_internal_igemm)
+    d->max_rows = conv_max_rows(c, dgrad);
+    d->nk = conv_nk(c, dgrad);
+    d->tp = select_tile(c->plan, d->max_rows, d->Cout, d->phases, d->nk, 1);
+    d->sp = d->tp.BP == 128 ? plan_ksplit((long)d->tp.mtiles * d->tp.ntiles * d->phases, d->nk, d->tp.max_slices) : SplitPlan{1, d->nk};
+    // The K split is sized to fill the chip with the partial-tile launch, but every slice is one more fp32 copy of the output
+    // that splitk_bn_act_kernel -- C / 8 workgroups -- has to read back: the student's 16x16 -> 8x8 layer wrote and folded 16
+    // slices = 16.8 MB for a 0.5 MB output, 59 us of fold behind 11 us of MFMA work (profiles/r3z_unet_student_chain.txt).
+    // Cap the slices at FUSE_BN_PARTIAL_BYTES of partial tiles (4 MB), never below four (fewer leave the partial-tile
+    // launch with a handful of workgroups: student forward 628 -> 569 us, teacher 836 -> 796 with 8 MB: profiles/r3z_*).
+    if (d->sp.ksplit > 4 && d->max_rows * d->phases <= FOLD_BN_MAX_ROWS)
+        cap_bn_slices(&d->sp, (size_t)d->phases * d->max_rows * d->tp.ntiles * d->tp.BC * sizeof(float), d->nk);
+    d->routed = (dgrad && thin_dgrad_shape(c)) || (!dgrad && thin_shape(c)) || head_shape(c);
+    d->fuse = gcc_opt(GCC_OPT_FUSE_BN);
+    d->grid_ws = bn->tail_ws && bn->tail_ws_bytes >= GCC_TAIL_WORKSPACE_BYTES && (((uintptr_t)bn->tail_ws) & 15) == 0;
+    d->fused = !d->routed && d->sp.ksplit > 1 && d->max_rows * d->phases <= FOLD_BN_MAX_ROWS && (d->fuse == 1 || d->fuse == 3);
+    return GCC_OK;
+}
+// the geometry of a fused route's partial-tile launch (no pointers); the codes the launch is declined with
+static int conv_bn_fused_params(const gcc_conv_t* c, int dgrad, const ConvBnDecision& d, IgemmParams* pp) {
+    IgemmParams& p = *pp;
+    p.bias = nullptr; p.stats = nullptr;
+    p.act = GCC_ACT_NONE; p.slope = 0.f;
+    p.N = c->N; p.KH = c->KH; p.KW = c->KW; p.stride = c->stride; p.pad = c->pad; p.dgrad = dgrad;
+    if (!dgrad) {
+        p.Hs = c->H; p.Ws = c->W; p.lds_ = c->ldx; p.soff = c->xoff; p.Hd = d.Ho; p.Wd = d.Wo; p.ldd = c->ldy; p.doff = c->yoff;
+        p.Ct = ceil8(c->Ci); p.Cout = c->Co;
+    } else {
+        p.Hs = d.Ho; p.Ws = d.Wo; p.lds_ = c->ldy; p.soff = c->yoff; p.Hd = c->H; p.Wd = c->W; p.ldd = c->ldx; p.doff = c->xoff;
+        p.Ct = ceil8(c->Co); p.Cout = c->Ci;
+        if (c->KH < c->stride || c->KW < c->stride) return GCC_ERR_UNSUPPORTED;
+    }
+    p.ldw = c->KH * c->KW * p.Ct;
+    const size_t sb = (size_t)p.N * p.Hs * p.Ws * p.lds_ * 2, wb = (size_t)p.Cout * p.ldw * 2;
+    if (sb >= OOB || wb >= OOB) return GCC_ERR_UNSUPPORTED;
+    p.src_bytes = (uint32_t)sb; p.wgt_bytes = (uint32_t)wb;
+    p.src_bstride = p.wgt_bstride = p.dst_bstride = 0;
+    p.ntiles = d.tp.ntiles; p.mtiles_max = d.tp.mtiles;
+    p.ksplit = d.sp.ksplit; p.kper = d.sp.kper; p.rows_max = (int)d.max_rows; p.Cpad = d.tp.ntiles * d.tp.BC;
+    p.raw_partial = 1; p.pair = 0; p.pair_slab = nullptr; p.pair_flags = nullptr;
+    if ((size_t)d.phases * d.sp.ksplit * d.max_rows * p.Cpad * sizeof(float) > d.split_bytes) return GCC_ERR_WORKSPACE;
+    return GCC_OK;
+}
+// the grid fold's descriptor behind that launch (its tensor pointers are the caller's to fill)
+static void conv_bn_fold_desc(const gcc_conv_t* c, int dgrad, const ConvBnDecision& dc, const IgemmParams& p, const gcc_bn_t* bn,
+                              BnFoldDesc* pd) {
+    BnFoldDesc& d = *pd;
+    d = BnFoldDesc{};
+    d.ksplit = p.ksplit; d.rows_max = p.rows_max; d.Cpad = p.Cpad; d.phases = dc.phases;
+    d.N = p.N; d.Hd = p.Hd; d.Wd = p.Wd; d.stride = c->stride; d.dgrad = dgrad;
+    d.ldraw = p.ldd; d.rawoff = p.doff;
+    d.C = dc.Cout; d.bn = *bn;
+    d.ws = (char*)bn->tail_ws + TAIL_TICKET_BYTES + TAIL_GROUP_BYTES; d.ws_bytes = GCC_INORM_WORKSPACE_BYTES;
+}
+
 extern "C" int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, const void* w, void* y_raw, const gcc_bn_t* bn,
                                const gcc_bnact_t* act, void* y, int ldy, int yoff, void* y2, int ldy2, int y2off, void* ws,
                                size_t ws_bytes, gcc_stream_t stream) {
@@ -1536,78 +1627,40 @@ extern "C" int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, co
     if ((y && ((ldy & 7) || (yoff & 7))) || (y2 && ((ldy2 & 7) || (y2off & 7)))) return GCC_ERR_BAD_ARG;
     if (ws_bytes < gcc_conv_bn_act_workspace(c, dgrad) || (((uintptr_t)ws) & 15)) return GCC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int Cout = dgrad ? c->Ci : c->Co;
-    const int phases = dgrad ? c->stride * c->stride : 1;
-    const size_t split_bytes = al256(gcc_conv_workspace(c, dgrad));
+    ConvBnDecision dc;
+    rc = conv_bn_decide(c, dgrad, bn, &dc);
+    if (rc) return rc;
+    const int Cout = dc.Cout;
+    const size_t split_bytes = dc.split_bytes;
     float* stats = (float*)((char*)ws + split_bytes);
-    const int Ho = gcc_conv_out(c->H, c->KH, c->stride, c->pad), Wo = gcc_conv_out(c->W, c->KW, c->stride, c->pad);
-    const size_t out_pixels = dgrad ? (size_t)c->N * c->H * c->W : (size_t)c->N * Ho * Wo;
+    const size_t out_pixels = dgrad ? (size_t)c->N * c->H * c->W : (size_t)c->N * dc.Ho * dc.Wo;
     const int out_ld = dgrad ? c->ldx : c->ldy, out_off = dgrad ? c->xoff : c->yoff;
-    // which plan would the conv take?  (same predicates as gcc_internal_igemm)
-    const size_t max_rows = conv_max_rows(c, dgrad);
-    const int nk = conv_nk(c, dgrad);
-    const TilePlan tp = select_tile(c->plan, max_rows, Cout, phases, nk, 1);
-    SplitPlan sp = tp.BP == 128 ? plan_ksplit((long)tp.mtiles * tp.ntiles * phases, nk, tp.max_slices) : SplitPlan{1, nk};
-    // The K split is sized to fill the chip with the partial-tile launch, but every slice is one more fp32 copy of the output
-    // that splitk_bn_act_kernel -- C / 8 workgroups -- has to read back: the student's 16x16 -> 8x8 layer wrote and folded 16
-    // slices = 16.8 MB for a 0.5 MB output, 59 us of fold behind 11 us of MFMA work (profiles/r3z_unet_student_chain.txt).
-    // Cap the slices at FUSE_BN_PARTIAL_BYTES of partial tiles (4 MB), never below four (fewer leave the partial-tile
-    // launch with a handful of workgroups: student forward 628 -> 569 us, teacher 836 -> 796 with 8 MB: profiles/r3z_*).
-    if (sp.ksplit > 4 && max_rows * phases <= FOLD_BN_MAX_ROWS) {
-        const size_t per_slice = (size_t)phases * max_rows * tp.ntiles * tp.BC * sizeof(float);
-        const size_t cap = FUSE_BN_PARTIAL_BYTES;
-        int ks = sp.ksplit;
-        while (ks > 4 && per_slice * ks > cap) ks = (ks + 1) / 2;
-        if (ks != sp.ksplit) { sp.kper = cdiv(nk, ks); sp.ksplit = cdiv(nk, sp.kper); }
-    }
-    const bool routed = (dgrad && thin_dgrad_shape(c)) || (!dgrad && thin_shape(c)) || head_shape(c);
-    const int fuse = gcc_opt(GCC_OPT_FUSE_BN);
-    const bool grid_ws = bn->tail_ws && bn->tail_ws_bytes >= GCC_TAIL_WORKSPACE_BYTES && (((uintptr_t)bn->tail_ws) & 15) == 0;
-    if (!routed && sp.ksplit > 1 && max_rows * phases <= FOLD_BN_MAX_ROWS && (fuse == 1 || fuse == 3)) {
+    if (dc.fused) {
         // split launch with raw partial tiles, then the fused fold + statistics + finalize + normalise kernel
         FoldBnArgs a;
         IgemmParams& p = a.p;
-        p.src = (const bf16_t*)x; p.wgt = (const bf16_t*)w; p.dst = (bf16_t*)y_raw; p.bias = nullptr; p.stats = nullptr;
-        p.act = GCC_ACT_NONE; p.slope = 0.f;
-        p.N = c->N; p.KH = c->KH; p.KW = c->KW; p.stride = c->stride; p.pad = c->pad; p.dgrad = dgrad;
-        if (!dgrad) {
-            p.Hs = c->H; p.Ws = c->W; p.lds_ = c->ldx; p.soff = c->xoff; p.Hd = Ho; p.Wd = Wo; p.ldd = c->ldy; p.doff = c->yoff;
-            p.Ct = ceil8(c->Ci); p.Cout = c->Co;
-        } else {
-            p.Hs = Ho; p.Ws = Wo; p.lds_ = c->ldy; p.soff = c->yoff; p.Hd = c->H; p.Wd = c->W; p.ldd = c->ldx; p.doff = c->xoff;
-            p.Ct = ceil8(c->Co); p.Cout = c->Ci;
-            if (c->KH < c->stride || c->KW < c->stride) return GCC_ERR_UNSUPPORTED;
-        }
-        p.ldw = c->KH * c->KW * p.Ct;
-        const size_t sb = (size_t)p.N * p.Hs * p.Ws * p.lds_ * 2, wb = (size_t)p.Cout * p.ldw * 2;
-        if (sb >= OOB || wb >= OOB) return GCC_ERR_UNSUPPORTED;
-        p.src_bytes = (uint32_t)sb; p.wgt_bytes = (uint32_t)wb;
-        p.src_bstride = p.wgt_bstride = p.dst_bstride = 0;
-        p.ntiles = tp.ntiles; p.mtiles_max = tp.mtiles;
-        p.ksplit = sp.ksplit; p.kper = sp.kper; p.partial = (float*)ws; p.rows_max = (int)max_rows; p.Cpad = tp.ntiles * tp.BC;
-        p.raw_partial = 1; p.pair = 0; p.pair_slab = nullptr; p.pair_flags = nullptr;
-        if ((size_t)phases * sp.ksplit * max_rows * p.Cpad * sizeof(float) > split_bytes) return GCC_ERR_WORKSPACE;
-        switch (tp.BC) {
-            case 128: rc = launch<128, 128>(p, phases, 1, st); break;
-            case 64: rc = launch<128, 64>(p, phases, 1, st); break;
-            case 32: rc = launch<128, 32>(p, phases, 1, st); break;
-            default: rc = launch<128, 16>(p, phases, 1, st); break;
+        rc = conv_bn_fused_params(c, dgrad, dc, &p);
+        if (rc) return rc;
+        p.src = (const bf16_t*)x; p.wgt = (const bf16_t*)w; p.dst = (bf16_t*)y_raw; p.partial = (float*)ws;
+        switch (dc.tp.BC) {
+            case 128: rc = launch<128, 128>(p, dc.phases, 1, st); break;
+            case 64: rc = launch<128, 64>(p, dc.phases, 1, st); break;
+            case 32: rc = launch<128, 32>(p, dc.phases, 1, st); break;
+            default: rc = launch<128, 16>(p, dc.phases, 1, st); break;
         }
         if (rc) return rc;
-        if (fuse == 3 && grid_ws) {
+        if (dc.fuse == 3 && dc.grid_ws) {
             // the slices folded, the statistics exchanged and the rows normalised by ONE kernel on the whole chip
-            BnFoldDesc d = {};
-            d.part = p.partial; d.ksplit = p.ksplit; d.rows_max = p.rows_max; d.Cpad = p.Cpad; d.phases = phases;
-            d.N = p.N; d.Hd = p.Hd; d.Wd = p.Wd; d.stride = c->stride; d.dgrad = dgrad;
-            d.raw = y_raw; d.ldraw = p.ldd; d.rawoff = p.doff;
+            BnFoldDesc d;
+            conv_bn_fold_desc(c, dgrad, dc, p, bn, &d);
+            d.part = p.partial; d.raw = y_raw;
             d.y = y; d.ldy = ldy; d.yoff = yoff; d.y2 = y2; d.ldy2 = ldy2; d.y2off = y2off;
-            d.C = Cout; d.bn = *bn; d.act = act->act; d.act2 = act->act2; d.slope = act->slope; d.drop_p = act->drop_p; d.seed = act->seed;
-            d.ws = (char*)bn->tail_ws + TAIL_TICKET_BYTES + TAIL_GROUP_BYTES; d.ws_bytes = GCC_INORM_WORKSPACE_BYTES;
+            d.act = act->act; d.act2 = act->act2; d.slope = act->slope; d.drop_p = act->drop_p; d.seed = act->seed;
             const int rc3 = gcc_internal_bn_fold_grid(&d, st);
             if (rc3 != GCC_ERR_UNSUPPORTED) return rc3;
         }
         a.bn = *bn; a.act = act->act; a.act2 = act->act2; a.slope = act->slope; a.drop_p = act->drop_p; a.seed = act->seed;
-        a.y = (bf16_t*)y; a.ldy = ldy; a.yoff = yoff; a.y2 = (bf16_t*)y2; a.ldy2 = ldy2; a.y2off = y2off; a.phases = phases;
+        a.y = (bf16_t*)y; a.ldy = ldy; a.yoff = yoff; a.y2 = (bf16_t*)y2; a.ldy2 = ldy2; a.y2off = y2off; a.phases = dc.phases;
         hipLaunchKernelGGL(splitk_bn_act_kernel<1024>, dim3(ceil8(Cout) / 8), dim3(1024), 0, st, a);
         GCC_CHECK_LAUNCH();
         return GCC_OK;
@@ -1617,13 +1670,75 @@ extern "C" int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, co
     // (bn->tail_ws; else a gcc_bn_finalize launch), then the normalising pass: two launches per layer, three on split layers.
     // GCC_OPT_FUSE_BN 0: the same without the in-launch finalize.
     gcc_bn_t bnf = *bn;
-    if (!gcc_opt(GCC_OPT_FUSE_BN)) { bnf.tail_ws = nullptr; bnf.tail_ws_bytes = 0; }
+    if (!dc.fuse) { bnf.tail_ws = nullptr; bnf.tail_ws_bytes = 0; }
     gcc_epilogue_t ep = {nullptr, GCC_ACT_NONE, 0.f, stats, split_bytes ? ws : nullptr, split_bytes, &bnf, nullptr, 0, 0, 0, nullptr};
     rc = gcc_internal_igemm(c, dgrad, x, w, y_raw, &ep, 1, 0, 0, 0, st);
     if (rc) return rc;
     gcc_bnact_t q = *act;
     q.scale = bn->scale; q.shift = bn->shift; q.gate = nullptr; q.gate_after_act = 0; q.groups = 1; q.residual = nullptr; q.ld_residual = 0;
     return gcc_bnact_fwd(&q, y_raw, out_ld, out_off, y, ldy, yoff, y2, ldy2, y2off, Cout, out_pixels, stream);
+}
+
+// One number of the plan gcc_conv_bn_act would run (include/gcc_hip.h), from the launch's own decision code; nothing launched.
+// The call's workspace is taken to be the gcc_conv_bn_act_workspace() bytes, 16-byte aligned, that the call demands.
+bool gcc_internal_thinout_routed(const gcc_conv_t* c, int dgrad, const gcc_epilogue_t* ep);
+extern "C" int gcc_conv_bn_act_plan(const gcc_conv_t* c, int dgrad, const gcc_bn_t* bn, int what) {
+    ConvBnDecision dc;
+    int rc = conv_bn_decide(c, dgrad, bn, &dc);
+    if (rc) return rc;
+    if (what < GCC_CONVBN_PLAN_ROUTE || what > GCC_CONVBN_PLAN_PPT) return GCC_ERR_BAD_ARG;
+    int route = 0;
+    BnFoldPlan fp = {};
+    if (dc.fused) {
+        IgemmParams p;
+        rc = conv_bn_fused_params(c, dgrad, dc, &p);
+        if (rc) return rc;
+        route = 1;
+        if (dc.fuse == 3 && dc.grid_ws) {
+            BnFoldDesc d;
+            conv_bn_fold_desc(c, dgrad, dc, p, bn, &d);
+            const int rc3 = gcc_internal_bn_fold_grid_plan(&d, &fp);
+            if (rc3 == GCC_OK) route = 2;
+            else if (rc3 != GCC_ERR_UNSUPPORTED) return rc3;
+        }
+    }
+    if (what >= GCC_CONVBN_PLAN_S && route != 2) return GCC_ERR_BAD_ARG;
+    switch (what) {
+        case GCC_CONVBN_PLAN_ROUTE: return route;
+        case GCC_CONVBN_PLAN_S: return fp.S;
+        case GCC_CONVBN_PLAN_S1: return fp.S1;
+        case GCC_CONVBN_PLAN_G: return fp.G;
+        case GCC_CONVBN_PLAN_ROWS: return fp.rows;
+        case GCC_CONVBN_PLAN_CG: return fp.CG;
+        case GCC_CONVBN_PLAN_CHG: return fp.CHg;
+        case GCC_CONVBN_PLAN_PL: return fp.PL;
+        case GCC_CONVBN_PLAN_PPT: return fp.PPT;
+        default: break;
+    }
+    if (route) return what == GCC_CONVBN_PLAN_KSPLIT ? dc.sp.ksplit : 2;      // partial tiles + one fold kernel
+    // route 0: what gcc_internal_igemm does with the statistic rows, the workspace and the BatchNorm descriptor the call hands it
+    gcc_bn_t bnf = *bn;
+    if (!dc.fuse) { bnf.tail_ws = nullptr; bnf.tail_ws_bytes = 0; }
+    void* const fake = (void*)(uintptr_t)4096;           // tested against NULL and for alignment only
+    gcc_epilogue_t ep = {nullptr, GCC_ACT_NONE, 0.f, (float*)fake, dc.split_bytes ? fake : nullptr, dc.split_bytes, &bnf, nullptr, 0, 0, 0, nullptr};
+    // the routes in front of the tiled kernel (thin output, ring walk, halo) plan their own launches: not answered here
+    if (gcc_internal_thinout_routed(c, dgrad, &ep) || gcc_internal_ring3_routed(c, dgrad, &ep) ||
+        halo_routed(c->plan, halo_plan(c, dgrad), dgrad, true, dc.tp.BP))
+        return GCC_ERR_UNSUPPORTED;
+    if (dgrad && (c->KH < c->stride || c->KW < c->stride)) return GCC_ERR_UNSUPPORTED;
+    const int rows_alloc = gcc_conv_stat_tiles(c, dgrad);
+    if (dc.tp.pair && dc.split_bytes && pair_workspace((size_t)dc.tp.mtiles * dc.tp.ntiles * dc.phases) <= dc.split_bytes) {
+        if (what == GCC_CONVBN_PLAN_KSPLIT) return 2;
+        return 1 + (tail_fin_ok(&bnf, dc.tp.mtiles * dc.phases, rows_alloc, dc.Cout) ? 0 : 1) + 1;
+    }
+    const IgemmSplit is = igemm_split(c, dgrad, dc.tp, dc.phases, dc.max_rows, dc.tp.ntiles * dc.tp.BC, dc.Cout, true, ep.workspace,
+                                      ep.workspace_bytes, rows_alloc);
+    if (what == GCC_CONVBN_PLAN_KSPLIT) return is.split ? is.sp.ksplit : 1;
+    int n;                                             // conv launches, a gcc_bn_finalize launch unless the rows' writer finalizes
+    if (!is.split) n = 1 + (tail_fin_ok(&bnf, dc.tp.mtiles * dc.phases, rows_alloc, dc.Cout) ? 0 : 1);
+    else if (is.fold_stats) n = 2 + (tail_fin_ok(&bnf, fold_wpp(dc.max_rows, dc.phases) * dc.phases, rows_alloc, dc.Cout) ? 0 : 1);
+    else n = 3 + 1;                                    // partials, splitk_epilogue_kernel, channel_stats_kernel, finalize
+    return n + 1;                                      // gcc_bnact_fwd
 }
 
 extern "C" size_t gcc_conv_workspace(const gcc_conv_t* c, int dgrad) {

@@ -1899,12 +1899,12 @@ int dw_inorm_prepare(const gcc_dw_inorm_t* d, DwInArgs* da) {
     return GCC_OK;
 }
 
-}  // namespace
-int gcc_internal_bn_fold_grid(const BnFoldDesc* d, hipStream_t st) {
-    if (!d || !d->part || !d->raw || !d->ws || d->ws_bytes < INORM_WS_HEADER + 16384 || !d->bn.scale || !d->bn.shift) return GCC_ERR_BAD_ARG;
-    if (gcc_device_error(0)) return GCC_ERR_LAUNCH;
+// the checks of gcc_internal_bn_fold_grid behind its pointers and the launch's arguments (nothing launched); *ppt: rows per lane
+static int bn_fold_grid_prepare(const BnFoldDesc* d, FoldGridArgs* pfa, int* ppt_out) {
+    if (!d || !d->ws || d->ws_bytes < INORM_WS_HEADER + 16384 || !d->bn.scale || !d->bn.shift) return GCC_ERR_BAD_ARG;
     if (!gcc_opt(GCC_OPT_INORM_GRID)) return GCC_ERR_UNSUPPORTED;
-    FoldGridArgs fa = {};
+    FoldGridArgs& fa = *pfa;
+    fa = FoldGridArgs{};
     const int st_ = d->dgrad ? d->stride : 1;
     if (d->dgrad && ((d->Hd % st_) || (d->Wd % st_))) return GCC_ERR_UNSUPPORTED;        // phases of different sizes: the other route
     fa.ostr = st_; fa.Hd = d->Hd; fa.Wd = d->Wd; fa.Hg = d->Hd / st_; fa.Wg = d->Wd / st_;
@@ -1916,6 +1916,7 @@ int gcc_internal_bn_fold_grid(const BnFoldDesc* d, hipStream_t st) {
     const int PL = 256 / ga.CHP;
     const int ppt = (ga.rows + PL - 1) / PL;
     if (ppt > 4) return GCC_ERR_UNSUPPORTED;
+    *ppt_out = ppt;
     ga.cnt = (unsigned*)d->ws;
     ga.partial = (float*)((char*)d->ws + INORM_WS_HEADER);
     ga.level2 = (float*)((char*)d->ws + INORM_WS_HEADER + (size_t)ga.CG * ga.S * ga.V * 8);
@@ -1932,6 +1933,29 @@ int gcc_internal_bn_fold_grid(const BnFoldDesc* d, hipStream_t st) {
     fa.running_mean = d->bn.running_mean; fa.running_var = d->bn.running_var; fa.mean = d->bn.mean; fa.rstd = d->bn.rstd;
     fa.scale = d->bn.scale; fa.shift = d->bn.shift;
     fa.act = d->act; fa.act2 = d->act2; fa.slope = d->slope; fa.drop_p = d->drop_p; fa.seed = d->seed;
+    return GCC_OK;
+}
+
+}  // namespace
+// the plan of the launch gcc_internal_bn_fold_grid would make, from its own preparation (the tensor pointers are not looked at)
+int gcc_internal_bn_fold_grid_plan(const BnFoldDesc* d, BnFoldPlan* out) {
+    FoldGridArgs fa;
+    int ppt = 0;
+    const int rc = bn_fold_grid_prepare(d, &fa, &ppt);
+    if (rc != GCC_OK) return rc;
+    const InGridArgs& ga = fa.g;
+    out->S = ga.S; out->S1 = ga.S1; out->G = ga.G; out->rows = ga.rows; out->CG = ga.CG; out->CHg = ga.CHg; out->PL = 256 / ga.CHP;
+    out->PPT = ppt <= 1 ? 1 : (ppt == 2 ? 2 : 4);          // the instantiation of bn_fold_grid_kernel
+    return GCC_OK;
+}
+int gcc_internal_bn_fold_grid(const BnFoldDesc* d, hipStream_t st) {
+    if (!d || !d->part || !d->raw || !d->ws || d->ws_bytes < INORM_WS_HEADER + 16384 || !d->bn.scale || !d->bn.shift) return GCC_ERR_BAD_ARG;
+    if (gcc_device_error(0)) return GCC_ERR_LAUNCH;
+    FoldGridArgs fa;
+    int ppt = 0;
+    const int rc = bn_fold_grid_prepare(d, &fa, &ppt);
+    if (rc != GCC_OK) return rc;
+    const InGridArgs& ga = fa.g;
     if (ga.S > 1) inorm_ws_scrub(d->ws, d->ws_bytes, st);
     const dim3 grid(ga.S, ga.CG, 1);
     if (ppt <= 1) hipLaunchKernelGGL((bn_fold_grid_kernel<1>), grid, dim3(256), 0, st, fa);

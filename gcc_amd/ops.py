@@ -1025,6 +1025,30 @@ def conv_bn_act(dgrad, src, w, raw, k, stride, pad, bn_module, st, count, y, y2=
                            Cs if dgrad else Cr, k, stride))
 
 
+def conv_bn_act_plan(dgrad, src, raw, k, stride, pad, bn_module, st, count):
+    """the plan conv_bn_act would run with these tensors, from the launcher's own decision code (gcc_conv_bn_act_plan): a dict of
+    route (0 / 1 / 2), ksplit and launches (None where the library does not answer it), on route 2 also S, S1, G, rows, CG, CHg,
+    PL and PPT; or the (negative) code of a declined call"""
+    sp, N, Cs, Hs, Ws, lds = geom(src)
+    rp, _, Cr, Hr, Wr, ldr = geom(raw)
+    d = conv_desc(N, Hr, Wr, Cr, Cs, k, stride, pad, ldr, lds) if dgrad else conv_desc(N, Hs, Ws, Cs, Cr, k, stride, pad, lds, ldr)
+    bn = bn_desc(bn_module, st, count, src.device)
+    return conv_bn_act_plan_of(d, dgrad, bn)
+
+
+def conv_bn_act_plan_of(d, dgrad, bn):
+    """conv_bn_act_plan for a gcc_conv_t and a gcc_bn_t"""
+    out = {}
+    for name, what in _lib.CONVBN_PLAN.items():
+        if name in _lib.CONVBN_PLAN_GRID and out.get('route') != 2:
+            continue
+        v = lib().gcc_conv_bn_act_plan(C.byref(d), int(dgrad), C.byref(bn), what)
+        if v < 0 and name != 'launches':
+            return v
+        out[name] = v if v >= 0 else None
+    return out
+
+
 def conv_wgrad(x, dy, dw, k, stride, pad, accumulate=False):
     """dw: fp32 [Co, Ci, k, k] channels_last gradient buffer (physical [Co][taps][Ci])."""
     xp, N, Ci, H, W, ldx = geom(x)

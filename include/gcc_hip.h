@@ -429,6 +429,19 @@ size_t gcc_conv_bn_act_workspace(const gcc_conv_t* c, int dgrad);
 int gcc_conv_bn_act(const gcc_conv_t* c, int dgrad, const void* x, const void* w, void* y_raw, const gcc_bn_t* bn,
                     const gcc_bnact_t* act, void* y, int ldy, int yoff, void* y2, int ldy2, int y2off, void* ws,
                     size_t ws_bytes, gcc_stream_t stream);
+/* One number of the plan that call would run, answered by the launcher's own decision code (nothing launched; the call's
+ * workspace is taken to be the gcc_conv_bn_act_workspace() bytes it demands; bn: the call's descriptor -- its tail_ws decides
+ * between the routes).  ROUTE: 0 the conv with statistic rows (gcc_conv_fprop / _dgrad's kernels, finalize in the launch or
+ * by gcc_bn_finalize) + gcc_bnact_fwd; 1 partial tiles + splitk_bn_act_kernel; 2 partial tiles + bn_fold_grid_kernel on the
+ * whole chip.  KSPLIT: the K slices behind the 4 MB cap (1: un-split).  LAUNCHES: kernel launches of the call (route 0 on the
+ * thin-output, ring-walk or halo conv routes: GCC_ERR_UNSUPPORTED, those plan their own).  Route 2 only (GCC_ERR_BAD_ARG on the
+ * others): S, S1, G, ROWS, CG, CHG, PL as GCC_DWIN_PLAN_* with the rows of all phases as one plane, PPT the rows-per-lane
+ * instantiation of the kernel (1, 2, 4).  < 0: the code the call itself is declined with; GCC_ERR_BAD_ARG for an unknown `what`.
+ * Introspection for tests.  Added without a GCC_HIP_ABI bump (an addition). */
+enum { GCC_CONVBN_PLAN_ROUTE = 0, GCC_CONVBN_PLAN_KSPLIT = 1, GCC_CONVBN_PLAN_LAUNCHES = 2, GCC_CONVBN_PLAN_S = 3,
+       GCC_CONVBN_PLAN_S1 = 4, GCC_CONVBN_PLAN_G = 5, GCC_CONVBN_PLAN_ROWS = 6, GCC_CONVBN_PLAN_CG = 7, GCC_CONVBN_PLAN_CHG = 8,
+       GCC_CONVBN_PLAN_PL = 9, GCC_CONVBN_PLAN_PPT = 10 };
+int gcc_conv_bn_act_plan(const gcc_conv_t* c, int dgrad, const gcc_bn_t* bn, int what);
 
 /* ---------------------------------------------------------------------------------------------
  * Inference (eval-mode) convolution: the layers of SRGAN's generator (models/SRGAN.py:19-199) with BatchNorm in eval mode, i.e.

@@ -15,7 +15,9 @@ tests/test_sagan_kernels_gpu.py; the norm and activation kernels of norm_act.hip
 backward route, in channel windows and in eval mode, in tests/test_norm_kernels_gpu.py; the bf16 training convolutions
 (igemm_kernel's tile families, split K and the pair combine, the thin, head, thin-output, ring-walk and halo routes, every
 weight-gradient form) bit for bit on integer data, per element against float64 and with exact statistic rows, each test
-asserting the route it ran on, in tests/test_conv_bf16_exact_gpu.py (its checks examined in tests/test_conv_bounds_cpu.py).
+asserting the route it ran on, in tests/test_conv_bf16_exact_gpu.py (its checks examined in tests/test_conv_bounds_cpu.py);
+gcc_conv_bn_act on each of its three routes, at every regime of the grid fold and through every fallback, in
+tests/test_convbn_exact_gpu.py (tests/test_convbn_bounds_cpu.py).
 The one-shape tests of those kernels below stay as they are."""
 import math
 import os
@@ -365,6 +367,12 @@ def test_conv_bn_act_one_call(case, fuse):
         st = ops.BNState(Cn, DEV)
         count = ref_raw.shape[0] * ref_raw.shape[2] * ref_raw.shape[3]
         seed = 1234567
+        # the route this (case, fuse) pair is meant to run (gcc_conv_bn_act_plan): the four split layers fold in the grid kernel
+        # (fuse 3) or in splitk_bn_act_kernel (fuse 1); everything else is the conv with statistic rows + gcc_bnact_fwd
+        split_layer = (N, H, W, Ci, Co) in ((16, 8, 8, 256, 256), (16, 4, 4, 512, 512), (16, 2, 2, 256, 512), (16, 8, 8, 256, 512))
+        want_route = {3: 2, 1: 1}.get(fuse, 0) if split_layer else 0
+        plan = ops.conv_bn_act_plan(transposed, src, raw, 4, 2, 1, bn, st, count)
+        assert isinstance(plan, dict) and plan['route'] == want_route, (case, fuse, plan)
         ops.conv_bn_act(transposed, src, wpk, raw, 4, 2, 1, bn, st, count, y, y2, act=ops.ACT_LRELU if not transposed else ops.ACT_RELU,
                         act2=ops.ACT_RELU, drop_p=drop, seed=seed)
         torch.cuda.synchronize()

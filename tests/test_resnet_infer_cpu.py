@@ -19,6 +19,9 @@ def test_dw_inorm_struct_matches_header(tmp_path):
     src += '  printf("ws %zu\\n", GCC_DW_INORM_WORKSPACE_BYTES);\n'
     src += '  printf("plan %d %d %d %d %d %d %d %d\\n", GCC_DWIN_PLAN_S, GCC_DWIN_PLAN_S1, GCC_DWIN_PLAN_G, GCC_DWIN_PLAN_ROWS, '
     src += 'GCC_DWIN_PLAN_CG, GCC_DWIN_PLAN_CHG, GCC_DWIN_PLAN_PL, GCC_DWIN_PLAN_TILE);\n'
+    src += '  printf("convbn %d %d %d %d %d %d %d %d %d %d %d\\n", GCC_CONVBN_PLAN_ROUTE, GCC_CONVBN_PLAN_KSPLIT, GCC_CONVBN_PLAN_LAUNCHES, '
+    src += 'GCC_CONVBN_PLAN_S, GCC_CONVBN_PLAN_S1, GCC_CONVBN_PLAN_G, GCC_CONVBN_PLAN_ROWS, GCC_CONVBN_PLAN_CG, GCC_CONVBN_PLAN_CHG, '
+    src += 'GCC_CONVBN_PLAN_PL, GCC_CONVBN_PLAN_PPT);\n'
     src += '  printf("abi %d\\n", GCC_HIP_ABI);\n  return 0;\n}\n'
     (tmp_path / 'l.c').write_text(src)
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(tmp_path / 'l.c'), '-o', str(tmp_path / 'l')])
@@ -29,6 +32,7 @@ def test_dw_inorm_struct_matches_header(tmp_path):
     assert [int(v) for v in out['modes']] == [_lib.DWIN_PLAIN, _lib.DWIN_NORM_RELU, _lib.DWIN_RESIDUAL]
     assert int(out['ws'][0]) == _lib.DW_INORM_WORKSPACE_BYTES
     assert [int(v) for v in out['plan']] == [_lib.DWIN_PLAN[k] for k in ('S', 'S1', 'G', 'rows', 'CG', 'CHg', 'PL', 'tile')]
+    assert [int(v) for v in out['convbn']] == [_lib.CONVBN_PLAN[k] for k in ('route', 'ksplit', 'launches') + _lib.CONVBN_PLAN_GRID]
     assert int(out['abi'][0]) == _lib.GCC_HIP_ABI
 
 
