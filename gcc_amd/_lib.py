@@ -329,6 +329,11 @@ PROTOTYPES = {
     'gcc_attention_infer': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),
     'gcc_attention_infer_workspace': (_Z, [_I, _I, _I, _I]),
     'gcc_attention_infer_route': (_I, [_I, _I, _I, _I, _Z]),
+    'gcc_attention_infer_f32': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
+    'gcc_attention_infer_f32_route': (_I, [_I, _I, _I, _I]),
+    'gcc_conv_eval_f32_z4': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
+    'gcc_conv_eval_f32_z4_route': (_I, [_I, _I, _I]),
+    'gcc_conv_eval_f32_z4_kp': (_I, [_I]),
     'gcc_l1_loss': (_I, [_P, _I, _I, _P, _I, _I, _I, _Z, _F, _P, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_mse_loss': (_I, [_P, _I, _I, _P, _I, _I, _I, _Z, _F, _P, _I, _P, _I, _I, _P, _Z, _P]),
     'gcc_loss_workspace': (_Z, [_Z, _I]),

@@ -1,4 +1,5 @@
-// The one fp32 implicit-GEMM tile of the inference convolutions (conv_f32.hip, resnet_f32.hip), on the f32-input matrix instruction
+// The one fp32 implicit-GEMM tile of the inference convolutions (conv_f32.hip, resnet_f32.hip; sagan_f32.hip's first-layer GEMM is a
+// sixth entry on it), on the f32-input matrix instruction
 // (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain, at 1/16 of the bf16 MFMA rate): its constants, what the hosts of
 // its five entries decide alike, and this description.  The device text is conv_f32_tile_body.inc, included inside each kernel.
 //

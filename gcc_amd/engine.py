@@ -2102,8 +2102,19 @@ class SaganGeneratorEngine:
         self._ev_views = v
         return v
 
-    def infer_input(self, N):
-        """the slab's input view z [N, z_dim, 1, 1] (NHWC bf16): fill it, then infer(it)"""
+    PRECISIONS = ('bf16', 'fp32')
+
+    def _precision(self, precision, where):
+        if precision not in self.PRECISIONS:
+            raise _lib.GccError('SaganGeneratorEngine.%s: precision %r; expected one of %s'
+                                % (where, precision, ', '.join(self.PRECISIONS)))
+        return precision == 'fp32'
+
+    def infer_input(self, N, precision='bf16'):
+        """the slab's input view z [N, z_dim, 1, 1] (NHWC bf16; precision='fp32': NHWC fp32, the fp32 route's own slab): fill it,
+        then infer(it, precision)"""
+        if self._precision(precision, 'infer_input'):
+            return self._infer_bufs_f32(N).z[:, :self.z_dim]
         return self._infer_bufs(N).z
 
     def _infer(self, z, count_only=False):
@@ -2137,11 +2148,17 @@ class SaganGeneratorEngine:
         launches += r if count_only else 0
         return launches if count_only else v.out
 
-    def infer(self, z):
+    def infer(self, z, precision='bf16'):
         """eval-mode generator forward of z [N, z_dim, 1, 1] (NHWC bf16, e.g. infer_input(N) filled): one power iteration of
         every SN layer (u, v move as in an eval forward()), l1..l4 with BatchNorm and ReLU in the conv epilogue, each attention
         block as a q | k | v conv and gcc_attention_infer, `last` + tanh.  Returns the NHWC bf16 image [N, 3, 64, 64], a view
-        of the slab valid until the next call (infer_launches() says how many launches it takes)."""
+        of the slab valid until the next call (infer_launches() says how many launches it takes).
+        precision='fp32': z (infer_input(N, 'fp32') filled) and the image are NHWC fp32 and the program is 12 launches at every
+        N -- the same coefficient launches (u, v move as on the bf16 route), gcc_conv_eval_f32_z4, three gcc_conv_eval_f32_unet,
+        per attention block gcc_conv_eval_f32_act and gcc_attention_infer_f32, `last`: the reference's own arithmetic (fp32
+        weights, fp32 activations, exact k-ordered sums, nothing split)."""
+        if self._precision(precision, 'infer'):
+            return self._infer_f32(z)
         N = z.shape[0]
         if N > getattr(self, '_ev_max_n', 0):
             # the split-K and key-split scratch a batch needs is not monotonic in N (small grids split): size the grow-only
@@ -2152,11 +2169,145 @@ class SaganGeneratorEngine:
             self._ev_max_n = N
         return self._infer(z)
 
-    def infer_launches(self, N):
+    def infer_launches(self, N, precision='bf16'):
         """kernel launches infer() makes for a batch of N, from the library's route introspection (launches nothing and
         writes nothing: an image an earlier infer() returned stays valid); includes the repacking a moved weight generation
-        costs the next call"""
+        costs the next call (bf16; the fp32 packings are refreshed by strided device copies, no library launch)"""
+        if self._precision(precision, 'infer_launches'):
+            return self._infer_f32(self.infer_input(N, 'fp32'), count_only=True)
         return self._infer(self.infer_input(N), count_only=True)
+
+    # ---- the same program at the reference's own precision ------------------------------------------------------------------
+    # fp32 packings of W_bar, q | k | v and `last`, coefficient buffers and a slab of its own; every width is carried at the next
+    # multiple of 8 with zero weights, zero scale and zero shift in the pad channels, which therefore stay 0 through ReLU and the
+    # attention blocks (v = 0 and x = 0 there).  The coefficient launch is the bf16 route's call on the same W_bar, u, v with
+    # scale / shift / t / sigma buffers of this route: u, v move the same bits.  Nothing of the bf16 route is read or written.
+
+    def _ev_weights_f32(self):
+        """the fp32 route's packings and coefficient buffers (made once; filled by _ev_repack_f32)"""
+        if getattr(self, '_ev32_w', None) is not None:
+            return self._ev32_w
+        dev, L = self.device, ops.ceil8
+        w = type('SaganInferWeights32', (), {})()
+        wp = [L(c) for c in self.width]
+        zp = (self.z_dim + 3) // 4 * 4
+        w.wp, w.zp = wp, zp
+        w.l1, w.l1_dst = ops.z4_weights_f32(zp, wp[0], dev)
+        w.up, w.up_dst = [None], [None]
+        for i in (1, 2, 3):
+            u, dst = ops.unet_weights_f32(wp[i - 1], wp[i], True, dev)
+            w.up.append(u)
+            w.up_dst.append(dst)
+        w.last, w.last_dst = ops.unet_weights_f32(wp[3], 8, True, dev)
+        w.last_b = torch.zeros(8, dtype=torch.float32, device=dev)
+        w.t = [torch.zeros(op.rows, dtype=torch.float32, device=dev) for op in self.sn]
+        w.sigma = torch.zeros(4, dtype=torch.float32, device=dev)
+        w.scale = [torch.zeros(wp[i], dtype=torch.float32, device=dev) for i in range(4)]
+        w.shift = [torch.zeros(wp[i], dtype=torch.float32, device=dev) for i in range(4)]
+        w.items = None
+        # q | k | v as one 1x1 conv over the padded width: rows [Wq; 0; Wk; 0; Wv; 0] at the bf16 route's slice offsets
+        w.qkv_width = [2 * L(a.C8) + L(a.C) for a in self.attn]
+        w.qkv_w, w.qkv_b = [], []
+        for a, width in zip(self.attn, w.qkv_width):
+            kp = ops.lib().gcc_conv_eval_f32_kp(L(a.C), 1, 1)
+            _lib.check(min(kp, 0), 'gcc_conv_eval_f32_kp')
+            w.qkv_w.append(torch.zeros((width, kp), dtype=torch.float32, device=dev))
+            w.qkv_b.append(torch.zeros(width, dtype=torch.float32, device=dev))
+        w.gen = None
+        self._ev32_w = w
+        return w
+
+    def _ev_repack_f32(self):
+        """refresh the fp32 packings when the weight generation moved (strided device copies into the standing buffers)"""
+        w = self._ev_weights_f32()
+        if w.gen == getattr(self, 'wgen', 0):
+            return
+        m = self.sn[0].w_bar.detach()                                      # [Z, C, 4, 4]
+        w.l1_dst[:, :, :m.shape[1], :m.shape[0]].copy_(m.permute(2, 3, 1, 0))
+        for i in (1, 2, 3):
+            m = self.sn[i].w_bar.detach()                                  # [Ci, Co, 4, 4]
+            for p, d in enumerate(w.up_dst[i]):
+                d[:m.shape[1], :, :, :m.shape[0]].copy_(m[:, :, 1 - (p >> 1)::2, 1 - (p & 1)::2].permute(1, 2, 3, 0))
+        m = self.last.weight.detach()
+        for p, d in enumerate(w.last_dst):
+            d[:m.shape[1], :, :, :m.shape[0]].copy_(m[:, :, 1 - (p >> 1)::2, 1 - (p & 1)::2].permute(1, 2, 3, 0))
+        if self.last.bias is not None:
+            w.last_b[:m.shape[1]].copy_(self.last.bias.detach())
+        for a, wq, bq in zip(self.attn, w.qkv_w, w.qkv_b):
+            for conv, (off, Cc) in zip(a.convs, a.slices):
+                cw = conv.weight.detach()
+                wq[off:off + Cc, :cw.shape[1]].copy_(cw.reshape(Cc, cw.shape[1]))
+                if conv.bias is not None:
+                    bq[off:off + Cc].copy_(conv.bias.detach())
+        w.items = ops.spectral_eval_items([(op.w_bar.data, op.u.data, op.v.data, w.t[i], w.sigma[i:i + 1], self.bn[i].bn,
+                                            op.bias.data if op.bias is not None else None, w.scale[i][:op.cols], w.shift[i][:op.cols])
+                                           for i, op in enumerate(self.sn)])
+        w.gen = getattr(self, 'wgen', 0)
+
+    def _infer_bufs_f32(self, N):
+        """views of the fp32 slab, every one at its full padded width: the input z and three regions the layers rotate through (a
+        layer never writes a region it reads); the image (ld 8) lands in region 0"""
+        w = self._ev_weights_f32()
+        wp, zp = w.wp, w.zp
+        per = [N * s * s * wp[i] for i, s in enumerate((4, 8, 16, 32))] + [N * 64 * 64 * 8]
+        per += [N * 256 * w.qkv_width[0], N * 1024 * w.qkv_width[1]]
+        size_z, size_r = N * zp, max(per)
+        total = size_z + 3 * size_r
+        if getattr(self, '_ev32_slab', None) is None or self._ev32_slab.numel() < total:
+            self._ev32_slab = self._ev32_views = None
+            self._ev32_slab = torch.zeros(total, dtype=torch.float32, device=self.device)
+        if getattr(self, '_ev32_views', None) is not None and self._ev32_views.N == N:
+            return self._ev32_views
+        slab = self._ev32_slab
+
+        def view(off, Cc, s):
+            return slab[off:off + N * s * s * Cc].view(N, s, s, Cc).permute(0, 3, 1, 2)
+        R = [size_z + i * size_r for i in range(3)]
+        v = type('SaganInferBufs32', (), {})()
+        v.N = N
+        v.z = view(0, zp, 1)
+        v.act = [view(R[0], wp[0], 4), view(R[1], wp[1], 8), view(R[0], wp[2], 16), view(R[0], wp[3], 32)]
+        v.qkv = [view(R[1], w.qkv_width[0], 16), view(R[1], w.qkv_width[1], 32)]
+        v.y = [view(R[2], wp[2], 16), view(R[2], wp[3], 32)]
+        v.out = view(R[0], 8, 64)
+        self._ev32_views = v
+        return v
+
+    def _infer_f32(self, z, count_only=False):
+        N = z.shape[0]
+        v = self._infer_bufs_f32(N)
+        w = self._ev_weights_f32()
+        E = _lib
+        if z.data_ptr() != v.z.data_ptr() or z.dtype is not torch.float32:
+            raise _lib.GccError("SaganGeneratorEngine.infer: precision 'fp32' takes infer_input(N, 'fp32'), filled")
+        launches = 0
+
+        def ran(r, what):
+            nonlocal launches
+            if count_only:
+                _lib.check(min(r, 0), what)
+                launches += 1
+        if not count_only:
+            self._ev_repack_f32()
+            ops.spectral_eval_coeffs_group(w.items, self.device)
+        launches += 3
+        ran(ops.conv_eval_f32_z4(v.z, w.l1, v.act[0], scale=w.scale[0], shift=w.shift[0], act=E.EVAL_ACT_RELU, route_only=count_only),
+            'gcc_conv_eval_f32_z4_route')
+        src = v.act[0]
+        for i in (1, 2, 3):
+            ran(ops.conv_eval_f32_unet(src, w.up[i], w.wp[i], v.act[i], transposed=True, scale=w.scale[i], shift=w.shift[i],
+                                       act=E.EVAL_ACT_RELU, route_only=count_only), 'gcc_conv_eval_f32_unet_route')
+            src = v.act[i]
+            if i >= 2:
+                a, j = self.attn[i - 2], i - 2
+                ran(ops.conv_eval_f32_act(src, w.qkv_w[j], w.qkv_width[j], (1, 1), (0, 0), v.qkv[j], shift=w.qkv_b[j],
+                                          route_only=count_only), 'gcc_conv_eval_f32_act_route')
+                r = ops.attention_infer_f32(v.qkv[j], a.offs, src, a.module.gamma.data, w.wp[i], a.C8, v.y[j], route_only=count_only)
+                launches += r if count_only else 0
+                src = v.y[j]
+        ran(ops.conv_eval_f32_unet(src, w.last, 8, v.out, transposed=True, shift=w.last_b, act=E.EVAL_ACT_TANH,
+                                   route_only=count_only), 'gcc_conv_eval_f32_unet_route')
+        return launches if count_only else v.out[:, :3]
 
 
 class SaganDiscriminatorEngine:

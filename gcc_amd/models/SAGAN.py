@@ -17,6 +17,7 @@ Reference behaviour that is reproduced on purpose (SURVEY.md section 8 hazards):
   * Adam betas (0, 0.9); the discriminator's learning rate is 4x; only the arch scheduler steps.
 """
 import copy
+import os
 from collections import OrderedDict
 
 import torch
@@ -31,6 +32,21 @@ from .DifferentiableOp import DifferentiableOP
 from .Pix2Pix import gen_precision
 from ._base import GANModelBase, _ChainWgrad
 from ._optim import HipAdam
+
+
+SAGAN_PRECISION_ENV = 'GCC_SAGAN_PRECISION'
+SAGAN_PRECISIONS = ('bf16', 'fp32')
+
+
+def sagan_precision():
+    """the precision of the SAGAN generator's inference path (SAGANModel.infer_nhwc) in gcc_amd.test --model sagan and in the
+    per-epoch FID evaluation: the environment variable GCC_SAGAN_PRECISION, 'bf16' (the default) or 'fp32' (the reference's own
+    arithmetic: SaganGeneratorEngine.infer(z, 'fp32')); any other value raises GccError.  The one place that reads it, and only
+    where a SAGAN generator infers: the other models never look at it."""
+    precision = os.environ.get(SAGAN_PRECISION_ENV) or 'bf16'
+    if precision not in SAGAN_PRECISIONS:
+        raise GccError('%s=%s: expected one of %s' % (SAGAN_PRECISION_ENV, precision, ', '.join(SAGAN_PRECISIONS)))
+    return precision
 
 
 def l2normalize(v, eps=1e-12):
@@ -246,18 +262,25 @@ class SAGANModel(GANModelBase):
         """fake_img = G(z) with the generator in eval mode, whatever mode the model is in, through the fused inference path
         (SaganGeneratorEngine.infer): an NHWC bf16 [N, 3, 64, 64] view valid until the next call.  z: [N, z_dim] (or
         [N, z_dim, 1, 1]) on the host or the device, or a dataset batch dict.  Like an eval forward() it advances the
-        generator's power iterations (u, v); it touches no training buffer.  forward() keeps its own route."""
+        generator's power iterations (u, v); it touches no training buffer.  forward() keeps its own route.
+        GCC_SAGAN_PRECISION=fp32 (sagan_precision): the NHWC fp32 view of SaganGeneratorEngine.infer(z, 'fp32'), the reference's
+        own arithmetic; u, v move the same bits under either precision.  GCC_GEN_PRECISION=fp32 is refused here as before."""
         gen_precision(only_bf16='--model sagan')
+        precision = sagan_precision()
         if isinstance(z, dict):
             z = z['z']
         N = z.shape[0]
+        z = z.to(self.device, torch.float32).reshape(N, -1, 1, 1).contiguous()
+        if precision == 'fp32':
+            return self.G.infer(ops.nchw_to_nhwc_f32(z, self.G.infer_input(N, 'fp32')), 'fp32')
         x = self.G.infer_input(N)
-        ops.nchw_to_nhwc(z.to(self.device, torch.float32).reshape(N, -1, 1, 1).contiguous(), x)
+        ops.nchw_to_nhwc(z, x)
         return self.G.infer(x)
 
     def infer(self, z):
         """infer_nhwc as NCHW fp32"""
-        return ops.nhwc_to_nchw(self.infer_nhwc(z), 3)
+        image = self.infer_nhwc(z)
+        return ops.nhwc_to_nchw_f32(image, Cc=3) if image.dtype is torch.float32 else ops.nhwc_to_nchw(image, 3)
 
     @property
     def fake_img(self):

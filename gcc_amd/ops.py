@@ -873,6 +873,40 @@ def conv_eval_f32_resnet(x, w, Co, kind, k, out, scale=None, shift=None, act=_li
     return out
 
 
+def z4_weights_f32(Z, Cp, device):
+    """(w, dst) for gcc_conv_eval_f32_z4: the zero-filled packed buffer [16 Cp][Kp] of ConvTranspose2d(Z, C, 4) on a 1 x 1 map (Z a
+    multiple of 4, Cp the width padded to 8) and the strided view [4, 4, Cp, Z] of it that dst[:, :, :C].copy_(weight.permute(2, 3,
+    1, 0)) fills from the master's [Z, C, 4, 4]; a view of fewer channels leaves the pad rows zero."""
+    kp = lib().gcc_conv_eval_f32_z4_kp(Z)
+    check(min(kp, 0), 'gcc_conv_eval_f32_z4_kp')
+    w = torch.zeros((16 * Cp, kp), dtype=torch.float32, device=device)
+    return w, w[:, :Z].view(4, 4, Cp, Z)
+
+
+def pack_weights_f32_z4(master):
+    """the packing gcc_conv_eval_f32_z4 reads, from ConvTranspose2d's [Z, C, 4, 4]: fp32 [16 Cp][Kp] with Cp = C padded to 8"""
+    m = master.detach().float()
+    Z, Cc = m.shape[0], m.shape[1]
+    w, dst = z4_weights_f32(Z, (Cc + 7) // 8 * 8, m.device)
+    dst[:, :, :Cc].copy_(m.permute(2, 3, 1, 0))
+    return w
+
+
+def conv_eval_f32_z4(x, w, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, route_only=False):
+    """the SAGAN generator's first layer in fp32 (gcc_conv_eval_f32_z4): out[n, c, kh, kw] = act(scale[c] sum_z x[n, z] W[z, c, kh,
+    kw] + shift[c]), act none / ReLU.  x [N, Z, 1, 1], out [N, C, 4, 4] (C a multiple of 8): NHWC fp32 views; w from
+    pack_weights_f32_z4.  One launch, no workspace.  route_only: the tile the library takes (>= 0) or its error, nothing launched."""
+    xp, N, Z, _, _, ldx = geom_f32(x)
+    yp, _, Cc, H, W, ldy = geom_f32(out)
+    if (H, W) != (4, 4) or x.shape[2:] != (1, 1) or out.shape[0] != N:
+        raise _lib.GccError('conv_eval_f32_z4: %s into %s' % (tuple(x.shape), tuple(out.shape)))
+    if route_only:
+        return lib().gcc_conv_eval_f32_z4_route(N, Z, Cc)
+    check(lib().gcc_conv_eval_f32_z4(xp, ldx, w.data_ptr(), _p(scale), _p(shift), act, N, Z, Cc, yp, ldy, stream()),
+          'gcc_conv_eval_f32_z4')
+    return out
+
+
 def pack_dw_f32(weight, bias, C8=None, out=None):
     """(w [9][C8], b [C8]) fp32 of a depthwise Conv2d(C, C, 3, groups=C)'s weight [C, 1, 3, 3] and bias [C] or None, tap-major and
     zero-padded to C8 channels: what gcc_dwconv3x3_reflect_f32 reads.  out: the (w, b) of an earlier call, refilled in place."""
@@ -1848,6 +1882,23 @@ def attention_infer(qkv, offs, x, gamma, Cc, C8, y, split=True, slot='eval_attn'
     check(lib().gcc_attention_infer(qp, ldq, offs[0], offs[1], offs[2], xp, ldx, gamma.data_ptr(), B, H * W, Cc, C8, yp, ldy,
                                     ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream()),
           'gcc_attention_infer')
+    return y
+
+
+def attention_infer_f32(qkv, offs, x, gamma, Cc, C8, y, route_only=False):
+    """eval-only y = gamma * softmax(q^T k) v + x in fp32 (gcc_attention_infer_f32): qkv, x, y NHWC fp32 views, q | k | v at the
+    channel offsets offs (multiples of 4) of qkv; Cc a multiple of 8.  One launch, no workspace.
+    route_only: the launches the call would make (1), nothing launched; a geometry it declines raises."""
+    qp, B, _, H, W, ldq = geom_f32(qkv)
+    if route_only:
+        rc = lib().gcc_attention_infer_f32_route(B, H * W, Cc, C8)
+        if rc < 0:
+            check(rc, 'gcc_attention_infer_f32_route')
+        return rc
+    xp, _, _, _, _, ldx = geom_f32(x)
+    yp, _, _, _, _, ldy = geom_f32(y)
+    check(lib().gcc_attention_infer_f32(qp, ldq, offs[0], offs[1], offs[2], xp, ldx, gamma.data_ptr(), B, H * W, Cc, C8, yp, ldy,
+                                        stream()), 'gcc_attention_infer_f32')
     return y
 
 

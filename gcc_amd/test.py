@@ -182,6 +182,10 @@ def run(opt, model):
         from .models.Pix2Pix import resnet_precision
         if resnet_precision() != 'bf16':         # the default run's lines stay as they were
             print('generator precision: %s' % resnet_precision())
+    elif opt.model == 'sagan':
+        from .models.SAGAN import sagan_precision
+        if sagan_precision() != 'bf16':          # the default run's lines stay as they were
+            print('generator precision: %s' % sagan_precision())
     dataset = create_dataset(topt, model.device)
     if scorer is not None and getattr(dataset, 'paths', None) is not None:
         scorer.prefetch(dataset.paths)
@@ -205,7 +209,11 @@ def run(opt, model):
                 fid.add(data['A_paths'][0], visuals['fake_B'], 0)
                 fid.add(data['B_paths'][0], model.infer_nhwc(model.real_B, 'B'), 1)
         elif opt.model == 'sagan':
-            visuals = {'fake_img': model.infer_nhwc(data), 'real_img': model.real_img}
+            fake = model.infer_nhwc(data)
+            if fake.dtype == torch.float32:      # the fp32 route: tensor2im's bytes once, for the PNG and the scorer
+                from . import ops
+                fake = ops.image_to_u8(fake)
+            visuals = {'fake_img': fake, 'real_img': model.real_img}
             if fid is not None:
                 fid.add(data['img_path'][0], visuals['fake_img'])
         else:

@@ -116,7 +116,7 @@ def _generator_note(opt):
     """what an evaluation's announcement says about the generator whose images it scores: nothing on the default bf16 inference
     route, its precision once GCC_GEN_PRECISION -- for a MobileResnet generator GCC_RESNET_PRECISION -- selects another
     (models/Pix2Pix.py gen_precision, resnet_precision; GCC_GEN_PRECISION=fp32 on a generator other than the U-Net raises here,
-    before the first epoch)"""
+    before the first epoch), for the SAGAN generator GCC_SAGAN_PRECISION (models/SAGAN.py sagan_precision)"""
     from .models.Pix2Pix import gen_precision, resnet_precision
     if opt.model == 'pix2pix':
         precision = gen_precision(only_bf16='--backbone resnet' if opt.backbone == 'resnet' else None)
@@ -124,6 +124,9 @@ def _generator_note(opt):
         precision = gen_precision(only_bf16='--model %s' % opt.model)
     if opt.model == 'cyclegan' or (opt.model == 'pix2pix' and opt.backbone == 'resnet'):
         precision = resnet_precision()           # a MobileResnet generator: GCC_RESNET_PRECISION (GCC_GEN_PRECISION=fp32 raised above)
+    if opt.model == 'sagan':
+        from .models.SAGAN import sagan_precision
+        precision = sagan_precision()            # the SAGAN generator: a variable of its own, as the MobileResnet's
     return '' if precision == 'bf16' else '; generator images in %s' % precision
 
 

@@ -915,6 +915,43 @@ int gcc_attention_infer(const void* qkv, int ldq, int qoff, int koff, int voff, 
                         int B, int N, int C, int C8, void* y, int ldy, void* ws, size_t ws_bytes, gcc_stream_t stream);
 size_t gcc_attention_infer_workspace(int B, int N, int C, int C8);
 int gcc_attention_infer_route(int B, int N, int C, int C8, size_t ws_bytes);
+/* gcc_attention_infer_f32: gcc_attention_infer at the reference's own precision (SaganGeneratorEngine.infer, precision 'fp32';
+ * gcc_amd/csrc/sagan_f32.hip).  q, k (C8 channels) and v (C channels) are fp32 channel slices of one NHWC fp32 buffer, x and y NHWC
+ * fp32; both products run on v_mfma_f32_16x16x4_f32 (bit for bit k-ordered fmaf chains); the N x N matrices are never stored.
+ * ONE launch: no key split, no workspace, no atomics, no workgroup waiting for another; an image alone and the same image inside a
+ * batch give the same bits.  Added without a GCC_HIP_ABI bump (additions only).  The arithmetic contract:
+ *     s_ij = the fmaf chain from 0 over the channels d = 0, 1, ... C8 - 1 of q_i[d] k_j[d] (zero padding to the instruction's K
+ *            step adds exact zeros);  m_i = max_j s_ij;  p_ij = expf(s_ij - m_i) with the device library's expf
+ *     l_i = sum_j p_ij,  O_ic = sum_j p_ij v_jc: fp32 fmaf chains from 0 (l_i: of p_ij x 1) in ONE order of the keys -- the tiles
+ *            of 16 keys ascending, inside a tile key 4 g + r with r = 0..3 outer and g = 0..3 inner (0, 4, 8, 12, 1, 5, ...) --
+ *            which depends on N alone: not on B, the grid, the tile a query fell into, or C.  O is never rescaled (two passes
+ *            over the keys: the row maximum first, then l and O from recomputed scores)
+ *     y_ic = fmaf(gamma, O_ic / l_i, x_ic), the division correctly rounded
+ * Limits as gcc_attention_infer (N <= 1024, C <= 512, 0 < C8 <= min(64, C)), C a multiple of 8, any C8, B <= 65535:
+ *   GCC_ERR_UNSUPPORTED otherwise.  ld and offsets in floats, multiples of 4, pointers 16-byte aligned, ldq >= voff + C (and
+ *   >= qoff + C8, koff + C8), ldx >= C, ldy >= C; a null pointer or a bad ld / offset: GCC_ERR_BAD_ARG.  Every refusal happens
+ *   before anything is launched.  Only channels [0, C) of y are written.
+ * gcc_attention_infer_f32_route: 1 (the launches the call makes) or the geometry's error; launches nothing. */
+int gcc_attention_infer_f32(const float* qkv, int ldq, int qoff, int koff, int voff, const float* x, int ldx,
+                            const float* gamma, int B, int N, int C, int C8, float* y, int ldy, gcc_stream_t stream);
+int gcc_attention_infer_f32_route(int B, int N, int C, int C8);
+/* gcc_conv_eval_f32_z4: the SAGAN generator's first layer at the reference's own precision, ConvTranspose2d(Z, C, 4) on a 1 x 1
+ * map: the GEMM [N, Z] x [Z, 16 C] on gcc_conv_eval_f32's tile (its matrix instruction and ONE order of K, walked in steps of 16,
+ * every product an fmaf onto the running sum; no split-K, no atomics, no workspace: an image does not depend on its batch or
+ * tile).  One launch.  Added without a GCC_HIP_ABI bump (additions only); the five entries on that tile keep their bits.
+ *     y[n][kh][kw][c] = act(fmaf(acc, scale[c], shift[c]))      act: GCC_EVAL_ACT_NONE | _RELU; scale / shift NULL: 1 / 0
+ * x: NHWC fp32 [N][1][1][ldx] (pointer to channel 0 of the Z channels), y: NHWC fp32 [N][4][4][ldy] (pointer to channel 0 of
+ *   the C written ones); ld in floats, multiples of 4, ldx >= Z, ldy >= C, pointers 16-byte aligned.
+ * Weights: fp32 [16 C][Kp], row (kh 4 + kw) C + c holding element [z][c][kh][kw] of ConvTranspose2d's [Z][C][4][4] at k = z,
+ *   zeros from Z to Kp = gcc_conv_eval_f32_z4_kp(Z), the next multiple of 16.
+ * Z a multiple of 4 (<= 2^20), C a multiple of 8 (<= 65536), N <= 2^24: GCC_ERR_UNSUPPORTED otherwise; a non-positive size, a
+ *   null x / w / y, another act, a bad ld or alignment: GCC_ERR_BAD_ARG.  Every refusal happens before anything is launched.
+ * gcc_conv_eval_f32_z4_route: the tile (0: 128 latents x 128 columns, 1: 64 x 64, chosen as the sibling entries do from N rows
+ *   and 16 C columns -- the 32-column tile is never taken) or the geometry's error; launches nothing. */
+int gcc_conv_eval_f32_z4(const float* x, int ldx, const float* w, const float* scale, const float* shift, int act, int N, int Z,
+                         int C, float* y, int ldy, gcc_stream_t stream);
+int gcc_conv_eval_f32_z4_route(int N, int Z, int C);
+int gcc_conv_eval_f32_z4_kp(int Z);
 
 /* ---------------------------------------------------------------------------------------------
  * SRGAN (models/SRGAN.py, models/GANLoss.py:95-145).
