@@ -114,6 +114,7 @@ DWIN_PLAN = dict(S=0, S1=1, G=2, rows=3, CG=4, CHg=5, PL=6, tile=7)      # inclu
 # include/gcc_hip.h GCC_CONVBN_PLAN_* (gcc_conv_bn_act_plan); the names from S on exist on route 2 only
 CONVBN_PLAN = dict(route=0, ksplit=1, launches=2, S=3, S1=4, G=5, rows=6, CG=7, CHg=8, PL=9, PPT=10)
 CONVBN_PLAN_GRID = ('S', 'S1', 'G', 'rows', 'CG', 'CHg', 'PL', 'PPT')
+KID_TILE, KID_KSTEP = 128, 16                                # include/gcc_hip.h GCC_KID_TILE, GCC_KID_KSTEP (gcc_kid_poly_sum)
 
 
 class dw_inorm_t(C.Structure):
@@ -324,6 +325,8 @@ PROTOTYPES = {
     'gcc_fid_input': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'gcc_frechet_workspace': (_Z, [_I]),
     'gcc_frechet_distance': (_I, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P]),
+    'gcc_kid_workspace': (_Z, [_I, _I, _I]),
+    'gcc_kid_poly_sum': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     'gcc_attention_fwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_bwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_infer': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),

@@ -1,7 +1,13 @@
 """Evaluation arithmetic on MI355X -- the reference's ``metric`` package surface (metric/__init__.py:8-25) over
 libgcc_hip.so.  The evaluator networks (Inception-v3 for FID, DRN for mIoU) are external inputs, exactly as their
 weights are in the reference: ``model`` is any callable with the reference models' output convention."""
+import warnings
+
 import torch
+
+# `python -m gcc_amd.metric.fid_score` runs a module this package has already imported (below): runpy says so on every start; the
+# second copy holds a parser and functions, no state
+warnings.filterwarnings('ignore', message=r"'gcc_amd\.metric\.fid_score' found in sys\.modules", category=RuntimeWarning)
 
 from .fid_score import _compute_statistics_of_ims, calculate_frechet_distance
 from .mIoU_score import test

@@ -12,10 +12,16 @@ resolution in (resizing and normalisation are the network's own), element 0 of t
 
 Nothing is read back before that last step, and the device holds d^2 doubles of statistics whatever the number of images.
 
+With a feature file real_act*.npz beside every real_stat*.npz the evaluation needs (python -m gcc_amd.metric.get_real_stat
+--features_path), the activations are also kept (kid_score.FeatureStore) and a ``KID: %.6f`` line follows the FID line: the
+Kernel Inception Distance (kid_score.polynomial_mmd2), three gcc_kid_poly_sum calls per slot, the real set's self term once
+per run.  Checkpoints are still chosen by FID alone.  Without the files nothing is stored, launched or logged for it.
+
 The one deliberate difference from the reference: it runs Inception at batch 1 (its evaluations set opt.batch_size = 1); this
 evaluator batches up to 50 images (get_activations' own default).  An eval-mode network's output for an image does not depend on
 its batch neighbours, so the activations are those of the batch-1 run up to the network's own batched arithmetic."""
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -97,9 +103,10 @@ class ImageStatistics:
     [batch_size, 3, H, W] buffer; a full buffer (and the remainder at the end) goes through the network and into the streamed
     statistics, all on the current stream."""
 
-    def __init__(self, inception, batch_size=50):
+    def __init__(self, inception, batch_size=50, keep_features=False):
         self.inception, self.bs = inception, max(1, int(batch_size))
         self.buf, self.k, self.seen, self.stream = None, 0, set(), None
+        self.keep_features, self.features = bool(keep_features), None      # a kid_score.FeatureStore, only when asked
 
     @property
     def count(self):
@@ -132,6 +139,11 @@ class ImageStatistics:
         if self.stream is None:
             self.stream = ActivationStream(pred.shape[1], self.bs, pred.device)
         self.stream.update(pred)
+        if self.keep_features:
+            if self.features is None:
+                from .kid_score import FeatureStore
+                self.features = FeatureStore(pred.shape[1], pred.device)
+            self.features.append(pred)
         self.k = 0
 
     def result(self):
@@ -153,12 +165,20 @@ def load_real_stat(path, d, device):
 
 
 class FidScorer:
-    """one evaluation: generated images in (per slot), one FID per slot out"""
+    """one evaluation: generated images in (per slot), one FID per slot out -- and one KID per slot (``kid()``) when a feature
+    file real_act*.npz (get_real_stat --features_path) lies beside every slot's real_stat*.npz; with one missing, no activation
+    is kept and nothing is launched for it.  ``kid_cache``: a dict that outlives the scorer (the evaluator's): the real sets'
+    activations and self terms are loaded and computed once per run."""
 
-    def __init__(self, inception, dataroot, slots, batch_size=50):
+    def __init__(self, inception, dataroot, slots, batch_size=50, kid_cache=None):
+        from .kid_score import features_name
         self.files = [os.path.join(str(dataroot), name) for name, _ in slots]
         self.tags = [tag for _, tag in slots]
-        self.stats = [ImageStatistics(inception, batch_size) for _ in slots]
+        self.feature_files = [features_name(f) for f in self.files]
+        self.with_kid = bool(slots) and all(f is not None and os.path.isfile(f) for f in self.feature_files)
+        self.kid_cache = kid_cache if kid_cache is not None else {}
+        self.label = network_label(inception)
+        self.stats = [ImageStatistics(inception, batch_size, keep_features=self.with_kid) for _ in slots]
 
     def add(self, key, fake, slot=0):
         self.stats[slot].add(key, fake)
@@ -171,6 +191,34 @@ class FidScorer:
             values.append(float(calculate_frechet_distance(m1, s1, mu, sigma)))         # metric/__init__.py:8-14
         return values
 
+    def _real_features(self, path, d, device):
+        """(activations, self term) of a feature file, from the cache after the first evaluation of a run"""
+        from . import kid_score
+        if path not in self.kid_cache:
+            act, label = kid_score.load_features(path, d, device)
+            if label != self.label and not self.kid_cache.get('warned'):
+                self.kid_cache['warned'] = True
+                warnings.warn('%s was written with the Inception network%s, this evaluation scores with the network%s: KID '
+                              'compares activations of two networks' % (path, label or ' (TorchScript)', self.label or ' (TorchScript)'))
+            self.kid_cache[path] = (act, kid_score.polynomial_self_sum(act))
+        return self.kid_cache[path]
+
+    def kid(self):
+        """one Kernel Inception Distance per slot (real set first, as the FID's arguments), or None when a slot has no feature
+        file"""
+        if not self.with_kid:
+            return None
+        from .kid_score import polynomial_mmd2
+        values = []
+        for path, st in zip(self.feature_files, self.stats):
+            if st.count < 2:
+                raise GccError('KID needs at least 2 images, %d were scored' % st.count)
+            st.flush()
+            fake = st.features.rows()
+            real, real_self = self._real_features(path, fake.shape[1], fake.device)
+            values.append(polynomial_mmd2(real, fake, self_x=real_self))
+        return values
+
 
 def fid_line(values, tags, model):
     if 'cyclegan' in model:
@@ -178,16 +226,22 @@ def fid_line(values, tags, model):
     return 'FID: %.2f' % values[0]
 
 
+def kid_line(values, tags, model):
+    if 'cyclegan' in model:
+        return ' | '.join('%s KID: %.6f' % (t, v) for v, t in zip(values, tags))
+    return 'KID: %.6f' % values[0]
+
+
 def fid_evaluator(inception, logger=None, batch_size=50):
     """evaluate(model, opt) for gcc_amd.train.run_evaluation: test_pix2pix_fid / test_cyclegan_fid / test_sagan_fid.
     ``evaluate.scorer(model, opt)`` gives python -m gcc_amd.test the scorer of the images it writes.  Inception runs on batches
     of up to ``batch_size`` images where the reference runs it at batch 1: the one deliberate difference (see the module)."""
-    state = {'inception': None}
+    state = {'inception': None, 'kid': {}}
 
     def scorer(model, opt):
         if state['inception'] is None:
             state['inception'] = _prepare(inception, model.device)
-        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size)
+        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size, kid_cache=state['kid'])
 
     def evaluate(model, opt):
         from ..data import create_dataset
@@ -212,6 +266,9 @@ def fid_evaluator(inception, logger=None, batch_size=50):
         values = sc.result()
         if logger is not None:
             logger.info(fid_line(values, sc.tags, opt.model))
+        kid = sc.kid()                             # None without a feature file beside every real_stat*.npz: no line, no launch
+        if kid is not None and logger is not None:
+            logger.info(kid_line(kid, sc.tags, opt.model))
         return list(zip(values, sc.tags))
 
     evaluate.state = state

@@ -1,5 +1,14 @@
 """FID arithmetic on the GPU (metric/fid_score.py:150-214, 219-284, 327-328): activation statistics in f64 and the Frechet
-distance with a Newton-Schulz matrix square root.  No CPU path: a missing library / GPU raises GccError."""
+distance with a Newton-Schulz matrix square root; and the reference's path-based half (:55-145, 287-322, 332-370): image folders,
+statistics files and feature files scored against each other,
+
+    python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 2048] [-c GPU]
+
+prints ``FID: %.2f`` and, when both sides have activations (folders, or the feature files get_real_stat --features_path writes),
+``KID: %.6f`` (gcc_amd.metric.kid_score).  No CPU path: a missing library / GPU raises GccError."""
+import argparse
+import os
+
 import numpy as np
 import torch
 
@@ -140,3 +149,201 @@ def get_activations_from_ims(ims, model, batch_size=50, dims=2048, device=None, 
 def _compute_statistics_of_ims(ims, model, batch_size, dims, device, use_tqdm=True):
     act = get_activations_from_ims(ims, model, batch_size, dims, device, verbose=False, use_tqdm=use_tqdm)
     return activation_statistics(act)
+
+
+# ---- the path-based half of metric/fid_score.py (:55-145, 287-322, 332-370) ---------------------------------------------------
+DIMS = (64, 192, 768, 2048)         # metric/inception.py BLOCK_INDEX_BY_DIM: the widths the reference's --dims accepts
+
+parser = argparse.ArgumentParser(prog='python -m gcc_amd.metric.fid_score', formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                                 description='FID (and KID, when both sides have activations) of two image sets')
+parser.add_argument('path', type=str, nargs=2,
+                    help='two of: a folder of *.jpg / *.png images, a real_stat*.npz statistics file (mu, sigma), '
+                         'a real_act*.npz feature file (get_real_stat --features_path)')
+parser.add_argument('--batch-size', type=int, default=50, help='images per pass of the network')
+parser.add_argument('--dims', type=int, default=2048, choices=list(DIMS), help='width of the network\'s features')
+parser.add_argument('-c', '--gpu', default='', type=str, help='index of the GPU to use (blank: the current device; there is no CPU path)')
+
+
+def list_image_files(path):
+    """the *.jpg and *.png files of a folder (metric/fid_score.py:318-319), sorted by name: the reference takes them in
+    directory order, which decides nothing but which images a partial last batch drops"""
+    names = [f for f in os.listdir(str(path)) if os.path.splitext(f)[1] in ('.jpg', '.png') and os.path.isfile(os.path.join(str(path), f))]
+    return [os.path.join(str(path), f) for f in sorted(names)]
+
+
+def batch_plan(n_files, batch_size, warn=print):
+    """(batch size, number of batches) of get_activations (:92-102): the batch size is clamped to the file count, a partial last
+    batch is dropped, each with the reference's warning"""
+    batch_size = int(batch_size)
+    if n_files < 1 or batch_size < 1:
+        raise GccError('get_activations: %d files at batch size %d' % (n_files, batch_size))
+    if n_files % batch_size != 0:
+        warn('Warning: number of images is not a multiple of the batch size. Some samples are going to be ignored.')
+    if batch_size > n_files:
+        warn('Warning: batch size is bigger than the datasets size. Setting batch size to datasets size')
+        batch_size = n_files
+    return batch_size, n_files // batch_size
+
+
+def _cuda_device(cuda):
+    if not cuda:
+        raise GccError('gcc_amd runs on MI355X only (no CPU path): cuda must be set')
+    return cuda if isinstance(cuda, torch.device) else _dev()
+
+
+def _activation_batches(files, model, batch_size, dims, cuda, verbose=False):
+    """the [b, dims] fp32 device activations of get_activations, one batch at a time"""
+    from PIL import Image
+    from .fid_eval import fid_input
+    dev = _cuda_device(cuda)
+    if hasattr(model, 'eval'):
+        model.eval()
+    files = [str(f) for f in files]
+    batch_size, n_batches = batch_plan(len(files), batch_size)
+    size = None
+    for i in range(n_batches):
+        if verbose:
+            print('\rPropagating batch %d/%d' % (i + 1, n_batches), end='', flush=True)
+        images = []
+        for f in files[i * batch_size:(i + 1) * batch_size]:
+            with Image.open(f) as im:
+                a = np.asarray(im.convert('RGB'), dtype=np.uint8)
+            size = size or a.shape
+            if a.shape != size:
+                raise GccError('get_activations: %s is %d x %d, the images before it %d x %d: the images of one call share a size'
+                               % (f, a.shape[1], a.shape[0], size[1], size[0]))
+            images.append(a)
+        batch = fid_input(torch.from_numpy(np.stack(images)).to(dev))
+        with torch.no_grad():
+            pred = model(batch)[0]
+        if not torch.is_tensor(pred) or pred.dim() != 4 or pred.dtype != torch.float32 or pred.shape[0] != batch.shape[0]:
+            raise GccError('the Inception network must return [N, d, h, w] fp32 activations as element 0, got %s'
+                           % ('%s %s' % (pred.dtype, tuple(pred.shape)) if torch.is_tensor(pred) else type(pred).__name__))
+        if pred.shape[1] != dims:
+            raise GccError('the network\'s activations have d = %d, dims = %d was asked for' % (pred.shape[1], dims))
+        if pred.shape[2] != 1 or pred.shape[3] != 1:
+            pred = pred.mean((2, 3), keepdim=True)
+        yield pred.reshape(pred.shape[0], -1)
+    if verbose:
+        print(' done')
+
+
+def get_activations(files, model, batch_size=50, dims=2048, cuda=True, verbose=False, use_tqdm=False):
+    """metric/fid_score.py:69-145: the network's activations of image files, [n_used, dims] fp32, on the device.  The files are
+    decoded on the host (PIL, as RGB), go to the device as bytes and become the network's input through gcc_fid_input: byte /
+    255, the reference's imread(f).astype(float32) / 255.  As there, the batch size is clamped to the file count and a
+    partial last batch is dropped, each with its warning.  The images of one call must share a size (GccError names the file
+    that does not).  One difference: the reference decodes with cv2, which hands the network blue first; this decodes as RGB,
+    the order every other route of this package (and the real statistics) feeds."""
+    return torch.cat(list(_activation_batches(files, model, batch_size, dims, cuda, verbose)), 0)
+
+
+def calculate_activation_statistics(files, model, batch_size=50, dims=2048, cuda=True, verbose=False, use_tqdm=False, store=None):
+    """metric/fid_score.py:287-309 through ActivationStream: (mu [dims], sigma [dims, dims]) f64 device tensors of the files'
+    activations, batch by batch; ``store``: a kid_score.FeatureStore that receives the same activations"""
+    stream = None
+    for act in _activation_batches(files, model, batch_size, dims, cuda, verbose):
+        if stream is None:
+            stream = ActivationStream(act.shape[1], act.shape[0], act.device)
+        stream.update(act)
+        if store is not None:
+            store.append(act)
+    return stream.result()
+
+
+def _statistics_of_features(act, batch=512):
+    stream = ActivationStream(act.shape[1], min(batch, act.shape[0]), act.device)
+    for s in range(0, act.shape[0], batch):
+        stream.update(act[s:s + batch])
+    return stream.result()
+
+
+def _path_statistics(path, model, batch_size, dims, cuda):
+    """(mu, sigma, activations or None) of a folder, a statistics file or a feature file; ``model``: a callable that returns the
+    network, called only when a folder has to be scored"""
+    from . import kid_score
+    path = str(path)
+    if path.endswith('.npz'):
+        if kid_score.is_features_file(path):
+            act, _ = kid_score.load_features(path, dims, _cuda_device(cuda))
+            return _statistics_of_features(act) + (act,)
+        with np.load(path) as f:
+            return f['mu'][:], f['sigma'][:], None
+    files = list_image_files(path)
+    if not files:
+        raise GccError('%s holds no *.jpg or *.png file' % path)
+    store = kid_score.FeatureStore(dims, _cuda_device(cuda))
+    mu, sigma = calculate_activation_statistics(files, model(), batch_size, dims, cuda, store=store)
+    return mu, sigma, store.rows()
+
+
+def _compute_statistics_of_path(path, model, batch_size, dims, cuda, use_tqdm=False):
+    """metric/fid_score.py:312-322: mu / sigma of a .npz as they are stored, else of the folder's *.jpg + *.png"""
+    return _path_statistics(path, lambda: model, batch_size, dims, cuda)[:2]
+
+
+def _network(model, dims, cuda):
+    """a callable that returns the scoring network on the device: ``model``, or the file GCC_FID_INCEPTION names (loaded on the
+    first call, at the precision GCC_FID_PRECISION names)"""
+    state = {}
+
+    def get():
+        if 'net' not in state:
+            from .cityscapes import _prepare
+            from .fid_eval import load_inception
+            net = model
+            if net is None:
+                net, why = load_inception()
+                if net is None:
+                    raise GccError('fid_score: %s' % why)
+            state['net'] = _prepare(net, _cuda_device(cuda))
+        return state['net']
+    return get
+
+
+def calculate_fid_given_ims(ims_fake, ims_real, batch_size, cuda, dims, model=None, use_tqdm=False):
+    """metric/fid_score.py:332-347; ``model`` None: the network GCC_FID_INCEPTION names.  A network whose activations are not
+    ``dims`` wide is a GccError."""
+    net = _network(model, dims, cuda)()
+    dev = _cuda_device(cuda)
+    stats = []
+    for ims in (ims_fake, ims_real):
+        act = get_activations_from_ims(ims, net, batch_size, dims, dev, use_tqdm=use_tqdm)
+        if act.shape[1] != dims:
+            raise GccError('the network\'s activations have d = %d, dims = %d was asked for' % (act.shape[1], dims))
+        stats.append(activation_statistics(act))
+    return calculate_frechet_distance(*stats[0], *stats[1])
+
+
+def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqdm=False, kid=False):
+    """metric/fid_score.py:350-370: the FID of two paths, each a folder of images, a real_stat*.npz or a real_act*.npz feature
+    file.  ``kid``: return (FID, KID) instead, KID None unless both sides have activations (folders or feature files)."""
+    for p in paths:
+        if not os.path.exists(str(p)):
+            raise RuntimeError('Invalid path: %s' % p)
+    net = _network(model, dims, cuda)
+    (m1, s1, a1), (m2, s2, a2) = (_path_statistics(p, net, batch_size, dims, cuda) for p in paths[:2])
+    if tuple(m1.shape) != (dims,) or tuple(m2.shape) != (dims,):
+        raise GccError('the statistics have mu %s and %s, dims = %d was asked for' % (tuple(m1.shape), tuple(m2.shape), dims))
+    fid_value = calculate_frechet_distance(m1, s1, m2, s2)
+    if not kid:
+        return fid_value
+    from .kid_score import polynomial_mmd2
+    return fid_value, (polynomial_mmd2(a1, a2) if a1 is not None and a2 is not None else None)
+
+
+def main(argv=None, model=None):
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU')
+    if args.gpu != '':
+        torch.cuda.set_device(int(args.gpu))
+    fid_value, kid_value = calculate_fid_given_paths(args.path, args.batch_size, True, args.dims, model=model, kid=True)
+    print('FID: %.2f' % fid_value)
+    if kid_value is not None:
+        print('KID: %.6f' % kid_value)
+    return fid_value, kid_value
+
+
+if __name__ == '__main__':
+    main()

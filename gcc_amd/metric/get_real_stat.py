@@ -14,6 +14,9 @@ Images are read through gcc_amd.data, keyed by path (a repeated path counts once
 gcc_fid_input -- util.tensor2imgs' byte of the loader's [-1, 1] tensor over 255, exactly: 63 of the 256 byte values come back
 one lower from that round trip, and the reference's statistics are statistics of those bytes -- and go through the network at
 batch 32 (the reference's value) into the streamed statistics.  The file is the reference's: np.savez(mu=, sigma=) in f64.
+``--features_path F.npz`` (this tool's own flag) also writes the activations those statistics were built from,
+np.savez(act=<fp32 [n, d]>, network=<which network made them>): named real_act*.npz beside its real_stat*.npz, it lets every FID
+evaluation report the Kernel Inception Distance as well (gcc_amd.metric.kid_score).
 
 One difference: the reference sets max_dataset_size = -1, which makes its file listing drop whichever file os.walk listed
 last; this tool reads every file of the split."""
@@ -42,6 +45,11 @@ parser.add_argument('--output_path', type=str, required=True, help='the path to 
 parser.add_argument('--gpu_ids', type=str, default='0', help='gpu ids: the first one is used')
 parser.add_argument('--z_dim', type=int, default=128)
 parser.add_argument('--center_crop', action='store_true')
+# `parser` is the reference's surface, argument for argument; the tool parses with it plus the flags that are its own
+tool_parser = argparse.ArgumentParser(parents=[parser], add_help=False, description=parser.description)
+tool_parser.add_argument('--features_path', type=str, default=None,
+                         help='also save the activations the statistics were built from (np.savez(act=, network=)): a '
+                              'real_act*.npz beside its real_stat*.npz lets every FID evaluation report KID as well')
 
 # dataset mode -> (image, its path) of a batch, per direction
 _PICK = {'aligned': lambda AtoB: ('B', 'B_paths') if AtoB else ('A', 'A_paths'),
@@ -50,7 +58,7 @@ _PICK = {'aligned': lambda AtoB: ('B', 'B_paths') if AtoB else ('A', 'A_paths'),
 
 
 def parse(argv=None):
-    opt = parser.parse_args(argv)
+    opt = tool_parser.parse_args(argv)
     if opt.dataset_mode not in _PICK:
         raise GccError('get_real_stat: --dataset_mode %s (aligned, sa and unaligned have real images to score)' % opt.dataset_mode)
     opt.num_threads, opt.batch_size, opt.serial_batches, opt.no_flip = 0, 1, True, True
@@ -59,18 +67,19 @@ def parse(argv=None):
     return opt
 
 
-def real_statistics(opt, inception, device, batch_size=BATCH_SIZE):
-    """(mu [d], sigma [d, d]) f64 device tensors of the split's real images"""
+def real_statistics(opt, inception, device, batch_size=BATCH_SIZE, features=False):
+    """(mu [d], sigma [d, d]) f64 device tensors of the split's real images; ``features``: and the fp32 [n, d] activations they
+    were built from, as a third element"""
     from ..data import create_dataset
     from .cityscapes import _prepare, adopt_batch
     from .fid_eval import ImageStatistics
     image, path = _PICK[opt.dataset_mode](opt.direction == 'AtoB')
-    stats = ImageStatistics(_prepare(inception, device), batch_size)
+    stats = ImageStatistics(_prepare(inception, device), batch_size, keep_features=features)
     cur = torch.cuda.current_stream(device)
     for data in create_dataset(opt, device):
         adopt_batch(data, cur)
         stats.add(data[path][0], data[image])
-    return stats.result()
+    return stats.result() + ((stats.features.rows(),) if features else ())
 
 
 def main(argv=None, inception=None):
@@ -88,9 +97,13 @@ def main(argv=None, inception=None):
         inception, why = load_inception()
         if inception is None:
             raise GccError('get_real_stat: %s' % why)
-    mu, sigma = real_statistics(opt, inception, device)
+    mu, sigma, *act = real_statistics(opt, inception, device, features=opt.features_path is not None)
     np.savez(opt.output_path, mu=mu.cpu().numpy(), sigma=sigma.cpu().numpy())
     from .fid_eval import network_label
+    if act:
+        from .kid_score import save_features
+        save_features(opt.features_path, act[0], network_label(inception))
+        print('get_real_stat: %s written (%d x %d activations)' % ((opt.features_path,) + tuple(act[0].shape)))
     print('get_real_stat: %s written with the Inception network%s' % (opt.output_path, network_label(inception) or ' (TorchScript)'))
     return opt.output_path
 

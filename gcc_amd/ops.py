@@ -1327,6 +1327,46 @@ def global_avgpool_f32(x, out=None):
     return out
 
 
+def _kid_rows(t, what):
+    """(pointer, is_f64, ld, rows, d) of a [rows, d] fp32 / f64 device matrix whose rows may be strided (read in place)"""
+    if not torch.is_tensor(t) or t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or not t.is_cuda or \
+            t.shape[0] < 1 or t.shape[1] < 1:
+        raise _lib.GccError('%s: expected a fp32 / f64 [rows, d] device tensor, got %s'
+                            % (what, '%s %s on %s' % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+    rows, d = t.shape
+    if (d > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < d):
+        t = t.contiguous()
+    return t, t.data_ptr(), int(t.dtype == torch.float64), (t.stride(0) if rows > 1 else d), rows, d
+
+
+def kid_workspace_bytes(m, n, d):
+    """gcc_kid_workspace: one double per tile of pairs"""
+    return lib().gcc_kid_workspace(m, n, d)
+
+
+def kid_poly_sum(X, Y=None, out=None, slot='kid'):
+    """gcc_kid_poly_sum: out[0] (an f64 device scalar, made if not given) = the sum of (x_i . y_j / d + 1)^3 over all pairs of rows
+    of X [m, d] and Y [n, d]; Y None: the symmetric form, the pairs i != j of X.  Nothing is read back."""
+    X, xp, xf, ldx, m, d = _kid_rows(X, 'kid_poly_sum')
+    symmetric = Y is None
+    if symmetric:
+        if m < 2:
+            raise _lib.GccError('kid_poly_sum: the pairs i != j need at least 2 rows, got %d' % m)
+        Y, yp, yf, ldy, n = X, xp, xf, ldx, m
+    else:
+        Y, yp, yf, ldy, n, dy = _kid_rows(Y, 'kid_poly_sum')
+        if dy != d or Y.device != X.device:
+            raise _lib.GccError('kid_poly_sum: %s on %s against %s on %s' % (tuple(X.shape), X.device, tuple(Y.shape), Y.device))
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=X.device)
+    if out.dtype != torch.float64 or out.numel() < 1 or out.device != X.device:
+        raise _lib.GccError('kid_poly_sum: out must be an f64 tensor on %s' % X.device)
+    ws = workspace(kid_workspace_bytes(m, n, d), X.device, slot)
+    check(lib().gcc_kid_poly_sum(xp, xf, ldx, m, yp, yf, ldy, n, d, int(symmetric), out.data_ptr(), ws.data_ptr(), ws.numel(), stream()),
+          'gcc_kid_poly_sum')
+    return out
+
+
 def conv_eval_rect(x, w, Co, kernel, stride, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slot='eval', route_only=False):
     """inference conv with a (kh, kw) kernel and NO padding (gcc_conv_eval_ex with KH != KW allowed): out = act(scale[c] conv(x, w)
     + shift[c]).  gcc_conv_t has one `pad` for both directions, so a rectangular kernel's own padding (ph, pw) is border_copy's

@@ -1192,6 +1192,26 @@ int gcc_activation_stats_update(const void* act, int is_f64, int ld, int b, int 
                                 void* ws, size_t ws_bytes, gcc_stream_t stream);
 int gcc_activation_stats_finish(const double* m2, long long n, int d, double* sigma, gcc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Kernel Inception Distance (Binkowski et al. 2018) on the same activations (gcc_amd/csrc/kid.hip, gcc_amd/metric/kid_score.py).
+ * Added without a GCC_HIP_ABI bump (additions only).
+ * gcc_kid_poly_sum: out[0] = sum over pairs (i, j) of k(x_i, y_j), k = t t t with t = dot(x_i, y_j) (1.0 / d) + 1.0, all in f64.
+ *   X [m][ldx], Y [n][ldy]: fp32 (x_f64 / y_f64 == 0) or f64 rows of d elements, row stride ld >= d elements; what lies between
+ *   d and ld, or after the last row, is never read.  symmetric != 0: Y is X (the Y-side arguments are not read) and only the
+ *   pairs i != j count; m >= 2.  Any m, n, d >= 1: nothing needs to be a multiple of the tile or the k-step.
+ *   One workgroup per GCC_KID_TILE x GCC_KID_TILE tile of pairs (symmetric: the tiles on and above the diagonal, those above
+ *   it counted twice) walks d in steps of GCC_KID_KSTEP and writes one f64 partial to ws; a second launch folds the partials in
+ *   an order fixed by the tile index.  The m x n matrix is never stored: ws holds gcc_kid_workspace(m, n, d) bytes = one double
+ *   per tile.  No floating-point atomics, no workgroup waits for another: the same input gives the same bits.  Two launches.
+ *   GCC_ERR_BAD_ARG (a null pointer, a size < 1, ld < d, symmetric with m < 2), GCC_ERR_WORKSPACE (ws_bytes short) and
+ *   GCC_ERR_UNSUPPORTED (2^31 tiles or more) are returned before anything is launched.
+ * --------------------------------------------------------------------------------------------- */
+#define GCC_KID_TILE 128
+#define GCC_KID_KSTEP 16
+size_t gcc_kid_workspace(int m, int n, int d);
+int gcc_kid_poly_sum(const void* X, int x_f64, int ldx, int m, const void* Y, int y_f64, int ldy, int n, int d, int symmetric,
+                     double* out, void* ws, size_t ws_bytes, gcc_stream_t stream);
+
 /* ---- gradient exchange ---------------------------------------------------------------------------------
  * The reference trains on one device (models/Pix2Pix.py:356); the data-parallel path sums the five optimizers' flat fp32
  * gradient buffers over ranks before each `optimizer.step()` (train.py has no counterpart: this is the exchange a
