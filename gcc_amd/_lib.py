@@ -114,6 +114,10 @@ DWIN_PLAN = dict(S=0, S1=1, G=2, rows=3, CG=4, CHg=5, PL=6, tile=7)      # inclu
 # include/gcc_hip.h GCC_CONVBN_PLAN_* (gcc_conv_bn_act_plan); the names from S on exist on route 2 only
 CONVBN_PLAN = dict(route=0, ksplit=1, launches=2, S=3, S1=4, G=5, rows=6, CG=7, CHg=8, PL=9, PPT=10)
 CONVBN_PLAN_GRID = ('S', 'S1', 'G', 'rows', 'CG', 'CHg', 'PL', 'PPT')
+# include/gcc_hip.h GCC_DISTILL_PLAN_* (gcc_distill_plan), in the enum's order
+DISTILL_PLAN = ('off_scal', 'off_gf', 'off_gt', 'off_s', 'off_dfg', 'ws_bytes', 'gram_splits', 'gram_kper', 'gram_col_tiles',
+                'gram_co_tiles', 'gram_fold', 'bwd_route', 'bwd_bp', 'bwd_bc', 'bwd_ntiles', 'bwd_mtiles', 'fwd_launches',
+                'bwd_launches')
 KID_TILE, KID_KSTEP = 128, 16                                # include/gcc_hip.h GCC_KID_TILE, GCC_KID_KSTEP (gcc_kid_poly_sum)
 
 
@@ -345,6 +349,7 @@ PROTOTYPES = {
     'gcc_pool_linear_fwd': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     'gcc_pool_linear_bwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P]),
     'gcc_distill_workspace': (_Z, [_I, _I, _I]),
+    'gcc_distill_plan': (_I, [_I, _I, _I, C.POINTER(C.c_longlong)]),
     'gcc_distill_fwd': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     'gcc_distill_bwd': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I, _I, _P, _Z, _P]),
     'gcc_adam_step': (_I, [_P, _P, _I, _I, _F, _F, _F, _F, _I, _P]),

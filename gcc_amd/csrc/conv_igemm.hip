@@ -1377,6 +1377,25 @@ extern "C" int gcc_conv_route(const gcc_conv_t* c, int dgrad, const gcc_epilogue
     return 0;
 }
 
+// read-only: out = {route, BP, BC, ntiles, mtiles, launches} of gcc_internal_igemm(c, dgrad, ..., ep = NULL, batch, ...) -- the
+// call gcc_distill_bwd makes.  batch > 1 stands behind every `batch == 1` route of the dispatch: igemm_kernel with select_tile's
+// batch plan; batch == 1 takes gcc_conv_route's answer (tile fields 0 off route 0).  No epilogue: no workspace, so no K split
+// and one launch.  GCC_ERR_UNSUPPORTED for what the dispatch refuses and for the halo kernels, which plan their own tiles.
+int gcc_internal_igemm_plan(const gcc_conv_t* c, int dgrad, int batch, int out[6]) {
+    const int rc = check_conv(c);
+    if (rc) return rc;
+    if (!out || batch < 1) return GCC_ERR_BAD_ARG;
+    if (dgrad && (c->KH < c->stride || c->KW < c->stride)) return GCC_ERR_UNSUPPORTED;
+    const int route = batch == 1 ? gcc_conv_route(c, dgrad, nullptr) : 0;
+    out[0] = route; out[1] = out[2] = out[3] = out[4] = 0; out[5] = 1;
+    if (route != 0) return GCC_OK;
+    const int phases = dgrad ? c->stride * c->stride : 1;
+    const TilePlan tp = select_tile(c->plan, conv_max_rows(c, dgrad), dgrad ? c->Ci : c->Co, phases, conv_nk(c, dgrad), batch);
+    if (batch == 1 && halo_routed(c->plan, halo_plan(c, dgrad), dgrad, false, tp.BP)) return GCC_ERR_UNSUPPORTED;
+    out[1] = tp.BP; out[2] = tp.BC; out[3] = tp.ntiles; out[4] = tp.mtiles;
+    return GCC_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // conv + BatchNorm(training) + activation in one call (include/gcc_hip.h gcc_conv_bn_act)
 namespace gcc_igemm {

@@ -732,7 +732,37 @@ int plan_splits(const gcc_conv_t* c, int batch, int* ksteps_per_split, bool* big
     return splits;
 }
 
+// What the column-tiled launch of gcc_internal_wgrad does with a call -- its pixel splits, its tile grid and which kernel writes dW
+// behind wgrad_kernel -- decided in one place for the launch and for gcc_internal_wgrad_plan (gcc_distill_plan).
+enum { WFOLD_DIRECT = 0, WFOLD_FLAT = 1, WFOLD_VEC = 2, WFOLD_STRIDED = 3, WFOLD_STRIDED_DEEP = 4 };
+struct WgradTiling { int splits, kper, fold, col_tiles, co_tiles; bool big, regular; };
+WgradTiling wgrad_tiling(const gcc_conv_t* c, int batch, bool seg, const float* dw) {
+    WgradTiling t;
+    bool big = false;
+    t.splits = plan_splits(c, batch, &t.kper, &big);
+    t.regular = !seg && (c->Ci & 7) == 0 && (((uintptr_t)dw) & 15) == 0;
+    t.big = big && t.regular;          // concatenated / unaligned gradients keep the 128 x 128 tiling (same split plan)
+    if (t.regular) t.fold = t.splits == 1 ? WFOLD_DIRECT : (t.splits <= 8 ? WFOLD_FLAT : WFOLD_VEC);
+    else t.fold = t.splits >= 32 ? WFOLD_STRIDED_DEEP : WFOLD_STRIDED;     // many slabs, few outputs: 16 outputs x 16 split lanes
+    const int tcol = t.big ? 256 : 128;
+    t.col_tiles = cdiv(c->KH * c->KW * ceil8(c->Ci), tcol); t.co_tiles = cdiv(c->Co, tcol);
+    return t;
+}
+
 }  // namespace
+
+// read-only: out = {pixel splits, k-steps per split, column tiles, output-channel tiles, WFOLD_* kind, launches} of the
+// gcc_internal_wgrad call with this descriptor, batch and (16-byte aligned, unsegmented) dw; GCC_ERR_UNSUPPORTED where the call
+// would take the tap-stationary kernel instead
+int gcc_internal_wgrad_plan(const gcc_conv_t* c, int batch, int out[6]) {
+    if (!c || !out || batch < 1 || c->Ci <= 0 || c->Co <= 0) return GCC_ERR_BAD_ARG;
+    const WgradTiling t = wgrad_tiling(c, batch, false, nullptr);
+    int tper = 0;
+    if (t.regular && ts_plan(c, batch, &tper) > 0) return GCC_ERR_UNSUPPORTED;
+    out[0] = t.splits; out[1] = t.kper; out[2] = t.col_tiles; out[3] = t.co_tiles; out[4] = t.fold;
+    out[5] = t.fold == WFOLD_DIRECT ? 1 : 2;
+    return GCC_OK;
+}
 
 size_t gcc_internal_wgrad_workspace(const gcc_conv_t* c, int batch) {
     if (!c || c->Ci <= 0 || c->Co <= 0 || batch < 1) return 0;
@@ -804,13 +834,13 @@ int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float
     const size_t xb = (size_t)c->N * c->H * c->W * c->ldx * 2, yb = M * c->ldy * 2;
     if (xb >= OOB || yb >= OOB || M >= (1u << 30)) return GCC_ERR_UNSUPPORTED;
     p.M = (int)M; p.x_bytes = (uint32_t)xb; p.dy_bytes = (uint32_t)yb;
-    bool big = false;
-    const int splits = plan_splits(c, batch, &p.ksteps_per_split, &big);
     p.batch = batch; p.x_bstride = x_bstride; p.dy_bstride = dy_bstride;
     const bool seg = rows_l > 0;      // c holds physical sizes, dw is [rows_l][taps][cols_l]
-    const bool regular = !seg && (c->Ci & 7) == 0 && (((uintptr_t)dw) & 15) == 0;
-    big = big && regular;              // concatenated / unaligned gradients keep the 128 x 128 tiling (same split plan)
-    p.direct = (splits == 1 && regular) ? 1 : 0;
+    const WgradTiling wt = wgrad_tiling(c, batch, seg, dw);
+    const int splits = wt.splits;
+    const bool regular = wt.regular, big = wt.big;
+    p.ksteps_per_split = wt.kper;
+    p.direct = wt.fold == WFOLD_DIRECT ? 1 : 0;
     p.accumulate = accumulate; p.dw = dw;
     p.debug = gcc_diag_bits();
     p.rowmode = (c->KH <= 15 && c->KW <= 15) ? 1 : 0;     // taller or wider kernels decompose the pixels in every lane
@@ -854,8 +884,7 @@ int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float
         GCC_CHECK_LAUNCH();
         return GCC_OK;
     }
-    const int tcol = big ? 256 : 128;
-    p.col_tiles = cdiv(p.ncols, tcol); p.co_tiles = cdiv(c->Co, tcol);
+    p.col_tiles = wt.col_tiles; p.co_tiles = wt.co_tiles;
     p.dHW = make_fastdiv(Ho * Wo); p.dW = make_fastdiv(Wo); p.dCip = make_fastdiv(p.Cip); p.dKW = make_fastdiv(c->KW);
     static std::once_flag attr_once;
     std::call_once(attr_once, [] {
@@ -878,7 +907,7 @@ int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float
     const size_t total = (size_t)batch * c->Co * c->KH * c->KW * c->Ci;
     if (regular) {
         const size_t n4 = total / 4;
-        if (splits <= 8) {
+        if (wt.fold == WFOLD_FLAT) {
             int blocks = (int)((n4 + 255) / 256);
             if (blocks > 8192) blocks = 8192;
             hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, dw, splits, n4,
@@ -891,7 +920,7 @@ int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float
         }
     } else {
         const size_t outs = seg ? (size_t)rows_l * c->KH * c->KW * cols_l : total;
-        const bool deep = splits >= 32;           // many slabs, few outputs: 16 outputs x 16 split lanes
+        const bool deep = wt.fold == WFOLD_STRIDED_DEEP;
         int blocks = (int)((outs + (deep ? 15 : 63)) / (deep ? 16 : 64));
         if (blocks > 4096) blocks = 4096;
         const int rows = seg ? rows_l : batch * c->Co, cols = seg ? cols_l : c->Ci, cop = seg ? c->Co : batch * c->Co;

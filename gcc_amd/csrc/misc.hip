@@ -12,6 +12,8 @@ size_t gcc_internal_wgrad_workspace(const gcc_conv_t* c, int batch);
 int gcc_internal_wgrad(const gcc_conv_t* c, const void* x, const void* dy, float* dw, int accumulate, void* ws,
                        size_t ws_bytes, int batch, long x_bstride, long dy_bstride, hipStream_t st, int rows_l, int cols_l,
                        int row_split, int col_split);
+int gcc_internal_wgrad_plan(const gcc_conv_t* c, int batch, int out[6]);                  // conv_wgrad.hip
+int gcc_internal_igemm_plan(const gcc_conv_t* c, int dgrad, int batch, int out[6]);       // conv_igemm.hip
 
 namespace {
 
@@ -726,9 +728,19 @@ extern "C" int gcc_mse_loss(const void* a, int lda, int aoff, const void* b, int
 //   Gf [N][C][C] fp32 | Gt [N][C][C] fp32 | S [N][C][C] bf16 | dfg [N][HW][C] bf16 | wgrad slabs
 static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 struct DistillWs { size_t scal, partial, gf, gt, s, dfg, slabs, total; };
+// the two products as convolutions of one image [1][HW] pixels, N problems: G = F^T F is the 1x1 weight gradient with x = dy = the
+// feature window; dfg = f . S the 1x1 forward with S as its weight and the dense dfg as its output
+static gcc_conv_t distill_gram_conv(int C, int HW, int ld, int off) {
+    gcc_conv_t c = {1, 1, HW, C, C, 1, 1, 1, 0, ld, off, ld, off};
+    return c;
+}
+static gcc_conv_t distill_bwd_conv(int C, int HW, int ldf, int foff) {
+    gcc_conv_t c = {1, 1, HW, C, C, 1, 1, 1, 0, ldf, foff, C, 0};
+    return c;
+}
 static DistillWs distill_layout(int N, int C, int HW) {
     DistillWs w;
-    gcc_conv_t c = {1, 1, HW, C, C, 1, 1, 1, 0, C, 0, C, 0};
+    const gcc_conv_t c = distill_gram_conv(C, HW, C, 0);
     size_t o = 0;
     w.scal = o; o = al256(o + 16 * sizeof(float));
     w.partial = o; o = al256(o + 2 * RED_BLOCKS * sizeof(float));
@@ -746,6 +758,32 @@ extern "C" size_t gcc_distill_workspace(int N, int C, int HW) {
     return distill_layout(N, C, HW).total;
 }
 
+// kernel launches of gcc_distill_fwd behind the two Gram products: gram_diff + finalize, diff_reduce + finalize (the copy of the
+// two scalars is a memcpy node); of gcc_distill_bwd behind the 1x1 product: distill_combine_kernel
+constexpr int DISTILL_FWD_TAIL_LAUNCHES = 4, DISTILL_BWD_TAIL_LAUNCHES = 1;
+
+extern "C" int gcc_distill_plan(int N, int C, int HW, long long* plan) {
+    if (!plan || N <= 0 || C <= 0 || HW <= 0 || (C & 7)) return GCC_ERR_BAD_ARG;
+    const DistillWs L = distill_layout(N, C, HW);
+    plan[GCC_DISTILL_PLAN_OFF_SCAL] = (long long)L.scal; plan[GCC_DISTILL_PLAN_OFF_GF] = (long long)L.gf;
+    plan[GCC_DISTILL_PLAN_OFF_GT] = (long long)L.gt; plan[GCC_DISTILL_PLAN_OFF_S] = (long long)L.s;
+    plan[GCC_DISTILL_PLAN_OFF_DFG] = (long long)L.dfg; plan[GCC_DISTILL_PLAN_WS_BYTES] = (long long)L.total;
+    const gcc_conv_t cg = distill_gram_conv(C, HW, C, 0), cb = distill_bwd_conv(C, HW, C, 0);
+    int w[6], g[6];
+    int rc = gcc_internal_wgrad_plan(&cg, N, w);
+    if (rc) return rc;
+    rc = gcc_internal_igemm_plan(&cb, 0, N, g);
+    if (rc) return rc;
+    plan[GCC_DISTILL_PLAN_GRAM_SPLITS] = w[0]; plan[GCC_DISTILL_PLAN_GRAM_KPER] = w[1];
+    plan[GCC_DISTILL_PLAN_GRAM_COL_TILES] = w[2]; plan[GCC_DISTILL_PLAN_GRAM_CO_TILES] = w[3];
+    plan[GCC_DISTILL_PLAN_GRAM_FOLD] = w[4];
+    plan[GCC_DISTILL_PLAN_BWD_ROUTE] = g[0]; plan[GCC_DISTILL_PLAN_BWD_BP] = g[1]; plan[GCC_DISTILL_PLAN_BWD_BC] = g[2];
+    plan[GCC_DISTILL_PLAN_BWD_NTILES] = g[3]; plan[GCC_DISTILL_PLAN_BWD_MTILES] = g[4];
+    plan[GCC_DISTILL_PLAN_FWD_LAUNCHES] = 2 * w[5] + DISTILL_FWD_TAIL_LAUNCHES;
+    plan[GCC_DISTILL_PLAN_BWD_LAUNCHES] = g[5] + DISTILL_BWD_TAIL_LAUNCHES;
+    return GCC_OK;
+}
+
 extern "C" int gcc_distill_fwd(const void* f, int ldf, int foff, const void* t, int ldt, int toff, int N, int C, int HW,
                                int squared, float* out2, void* ws, size_t ws_bytes, gcc_stream_t stream) {
     GCC_ENTER();
@@ -758,8 +796,7 @@ extern "C" int gcc_distill_fwd(const void* f, int ldf, int foff, const void* t, 
     float* scal = (float*)(base + L.scal);
     float* partial = (float*)(base + L.partial);
     // raw gram matrices: per image, G = F^T F over the HW pixels  (a 1x1 weight-gradient product)
-    gcc_conv_t cf = {1, 1, HW, C, C, 1, 1, 1, 0, ldf, foff, ldf, foff};
-    gcc_conv_t ct = {1, 1, HW, C, C, 1, 1, 1, 0, ldt, toff, ldt, toff};
+    const gcc_conv_t cf = distill_gram_conv(C, HW, ldf, foff), ct = distill_gram_conv(C, HW, ldt, toff);
     const size_t slab_bytes = L.total - L.slabs;
     int rc = gcc_internal_wgrad(&cf, f, f, (float*)(base + L.gf), 0, base + L.slabs, slab_bytes, N, (long)HW * ldf,
                                 (long)HW * ldf, st, 0, 0, 0, 0);
@@ -799,7 +836,7 @@ extern "C" int gcc_distill_bwd(const void* f, int ldf, int foff, const void* t, 
     char* base = (char*)ws;
     hipStream_t st = (hipStream_t)stream;
     // dfg[pix][c] = sum_c' f[pix][c'] * D[c'][c]   (D symmetric): per-image 1x1 product
-    gcc_conv_t c1 = {1, 1, HW, C, C, 1, 1, 1, 0, ldf, foff, C, 0};
+    const gcc_conv_t c1 = distill_bwd_conv(C, HW, ldf, foff);
     int rc = gcc_internal_igemm(&c1, 0, f, base + L.s, base + L.dfg, nullptr, N, (long)HW * ldf, (long)C * C, (long)HW * C, st);
     if (rc) return rc;
     const double kg0 = (double)wg * 2.0 / ((double)N * C * C * (double)C * HW);

@@ -2034,6 +2034,17 @@ def distill_workspace_bytes(N, Cc, HW):
     return lib().gcc_distill_workspace(N, Cc, HW)
 
 
+def distill_plan(N, Cc, HW):
+    """what distill_fwd / distill_bwd do at this size, from the launchers' own decision code (gcc_distill_plan): a dict of the
+    _lib.DISTILL_PLAN names -- workspace offsets, the Gram product's splits and fold, the 1x1 product's route and tile, the launches
+    of each call -- or the (negative) code of a refused size"""
+    out = (C.c_longlong * len(_lib.DISTILL_PLAN))()
+    rc = lib().gcc_distill_plan(int(N), int(Cc), int(HW), out)
+    if rc:
+        return rc
+    return {name: int(out[i]) for i, name in enumerate(_lib.DISTILL_PLAN)}
+
+
 def distill_fwd(f, t, out2, ws, squared=False):
     """out2 = (gram term, content term): RMSE form (Pix2Pix) or, squared, plain MSE (CycleGAN)"""
     fp, N, Cc, H, W, ldf = geom(f)

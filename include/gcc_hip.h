@@ -824,6 +824,23 @@ int gcc_distill_fwd(const void* f, int ldf, int foff, const void* t, int ldt, in
 int gcc_distill_bwd(const void* f, int ldf, int foff, const void* t, int ldt, int toff, int N, int C, int HW,
                     int squared, float wg, float wc, void* df, int lddf, int dfoff, void* ws, size_t ws_bytes,
                     gcc_stream_t stream);
+/* What a gcc_distill_fwd / gcc_distill_bwd call of this size does, from the launchers' own decision code (the workspace
+ * layout, the weight-gradient split plan and fold choice, the tile choice and batch-1 route predicates of the 1x1 product);
+ * launches nothing.  plan[GCC_DISTILL_PLAN_N]:
+ *   OFF_SCAL .. OFF_DFG  byte offsets in the workspace of scal (fp32 Lg, Lc), Gf, Gt (fp32 [N][C][C]), S (bf16 [N][C][C]) and
+ *                        dfg (bf16 [N][HW][C]);  WS_BYTES = gcc_distill_workspace()
+ *   GRAM_SPLITS, GRAM_KPER  pixel splits of a Gram product and 64-pixel k-steps per split;  GRAM_COL_TILES x GRAM_CO_TILES its
+ *                        128 x 128 output tiles;  GRAM_FOLD 0: written directly, 1: wgrad_reduce_flat_kernel, 2: wgrad_reduce_vec_kernel
+ *   BWD_ROUTE            gcc_conv_route's answer for the 1x1 product at N == 1, 0 (igemm_kernel, problems on grid.y) at N > 1;
+ *   BWD_BP, BWD_BC, BWD_NTILES, BWD_MTILES  its tile plan (route 0)
+ *   FWD_LAUNCHES, BWD_LAUNCHES  kernel launches of one call (gcc_launch_count)
+ * GCC_ERR_BAD_ARG for the sizes the two entries refuse (and a NULL plan). */
+enum { GCC_DISTILL_PLAN_OFF_SCAL = 0, GCC_DISTILL_PLAN_OFF_GF, GCC_DISTILL_PLAN_OFF_GT, GCC_DISTILL_PLAN_OFF_S,
+       GCC_DISTILL_PLAN_OFF_DFG, GCC_DISTILL_PLAN_WS_BYTES, GCC_DISTILL_PLAN_GRAM_SPLITS, GCC_DISTILL_PLAN_GRAM_KPER,
+       GCC_DISTILL_PLAN_GRAM_COL_TILES, GCC_DISTILL_PLAN_GRAM_CO_TILES, GCC_DISTILL_PLAN_GRAM_FOLD, GCC_DISTILL_PLAN_BWD_ROUTE,
+       GCC_DISTILL_PLAN_BWD_BP, GCC_DISTILL_PLAN_BWD_BC, GCC_DISTILL_PLAN_BWD_NTILES, GCC_DISTILL_PLAN_BWD_MTILES,
+       GCC_DISTILL_PLAN_FWD_LAUNCHES, GCC_DISTILL_PLAN_BWD_LAUNCHES, GCC_DISTILL_PLAN_N };
+int gcc_distill_plan(int N, int C, int HW, long long* plan);
 
 /* ---------------------------------------------------------------------------------------------
  * SAGAN (models/SAGAN.py).

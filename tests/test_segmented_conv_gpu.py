@@ -7,13 +7,18 @@ concatenated LOGICAL tensors (autograd for both gradients), from the same bf16-r
 The physical operands are built the way the engine builds them: each part at its 8-aligned offset (0 and ceil8(split)), pad lanes
 zero.  The second part is drawn at 3x the scale of the first, so a mapping that is off by the pad gap lands far outside tolerance.
 Tolerances are the suite's: bf16 tensors close() default (1.2e-2 max|ref| + 1e-6), fp32 weight gradients tol 5e-3 floor 1e-4,
-packings bit-exact."""
+packings bit-exact.
+
+test_segmented_conv_exact runs the same nine cases on the data of tests/_conv_exact.py: integers (every logical position bit for
+bit, exact zeros in the pad and gap lanes) and seeded normals against float64 with the per-element bounds bound_out / bound_wgrad."""
 import ctypes as C
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _conv_exact as X
+from tests._perelem import within
 from tests.test_kernels_gpu import BAD_ARG, DEV, ERR_WORKSPACE, _ops, close, full_view, rb
 
 pytestmark = pytest.mark.gpu
@@ -222,6 +227,97 @@ def test_segmented_conv(name, wgrad_plan):
     dw2 = torch.zeros_like(dw)
     ops.conv_wgrad_seg(cxg, cdyg, dw2, rows, cols, rs, cs, k, s, p, accumulate=False)
     assert torch.equal(dw2.cpu(), fresh), 'pad lanes of x / dy leak into the weight gradient'
+
+
+def check_act_exact(got, ref, mag, split, kind, K, S, what):
+    """every logical lane against ref -- 'int': the one bf16 rounding of the exact value, bit for bit; 'normal': bound_out per
+    element -- and every other lane of the buffer exactly zero; returns the largest err / bound"""
+    idx, _ = seg_index(ref.shape[1], split)
+    full = full_view(got)
+    lanes = full[:, idx]
+    if kind == 'int':
+        want = X.expected_bits(ref)
+        bad = lanes.bfloat16().view(torch.int16) != want.view(torch.int16)
+        assert not bool(bad.any()), '%s: %d of %d logical elements are not the rounding of the exact value, first at %s' % (
+            what, int(bad.sum()), bad.numel(), tuple(int(v) for v in bad.nonzero()[0]))
+        worst = 0.0
+    else:
+        worst = within(lanes, ref, X.bound_out(ref, mag, K, S), what)
+    pad = sorted(set(range(full.shape[1])) - set(idx))
+    if pad:
+        assert float(full[:, pad].abs().max()) == 0.0, '%s: pad / gap lanes %s are not zero' % (what, pad)
+    return worst
+
+
+@pytest.mark.parametrize('kind', ['int', 'normal'])
+@pytest.mark.parametrize('name', list(CASES))
+def test_segmented_conv_exact(name, kind, wgrad_plan):
+    """The nine cases of test_segmented_conv on the data of tests/_conv_exact.py, drawn on the LOGICAL tensors.  'int': the weight
+    gradient is the exact integer at every logical position -- fresh over a stale fill, exactly twice when accumulating, the same
+    bits on a second run and with finite non-zero pad and gap lanes in both operands -- and forward / data gradient are
+    expected_bits at every logical lane, exact zeros in every pad and gap lane of a buffer of ones.  'normal': bound_wgrad(mag, M,
+    S) with S read from the workspace size, bound_out per element with K the physical products per output and at most one K slice
+    per k-step of 64.  The geometry g is the convolution whose weight gradient gcc_conv_wgrad_seg forms: a transposed layer is
+    that convolution's adjoint (its forward the data gradient, its data gradient the forward)."""
+    ops = _ops()
+    rows, rs, cols, cs, k, s, p, tr, N, H, W, wgs, slabs = CASES[name]
+    g = (N, H, W, cols, rows, k, s, p)
+    d = X.make_data(kind, g, sum(ord(ch) for ch in name))
+    Cip, Cop = ops.seg_phys(cols, cs), ops.seg_phys(rows, rs)
+    gp = (N, H, W, Cip, Cop, k, s, p)                     # what the kernels multiply: the pad and gap lanes are zero products
+    fwd_op, bwd_op = ('D', 'F') if tr else ('F', 'D')
+    x, dy = (d['dy'], d['x']) if tr else (d['x'], d['dy'])     # the LAYER's input and the gradient of its output
+    xs, ys = (rs, cs) if tr else (cs, rs)
+    y_ref, _, y_mag = X.reference(fwd_op, d, g)
+    dx_ref, _, dx_mag = X.reference(bwd_op, d, g)
+    dw_ref, dw_mag = X.ref_wgrad(d, g)
+    if kind == 'int':
+        for m, what in ((y_mag, 'forward'), (dx_mag, 'data gradient'), (2 * dw_mag + 7, 'weight gradient, accumulated')):
+            X.assert_exact_condition(m, name + ' ' + what)
+
+    wgrad_plan(wgs)
+    c = make_conv(d['w'].float(), k, s, p, tr, rs, cs)
+    ops.PackPlan([c], DEV).run()
+    xd, dyd = to_phys(x.float(), xs), to_phys(dy.float(), ys)
+    ratios = {}
+    out = produced(N, dy.shape[1], ys, dy.shape[2], dy.shape[3])
+    c.forward(xd, out)
+    Kf, Kb = X.k_products(gp, fwd_op), X.k_products(gp, bwd_op)
+    ratios['fwd'] = check_act_exact(out, y_ref, y_mag, ys, kind, Kf, X.cdiv(Kf, X.BK), '%s %s forward' % (name, kind))
+    dx = produced(N, x.shape[1], xs, x.shape[2], x.shape[3])
+    c.backward_data(dyd, dx)
+    ratios['dgrad'] = check_act_exact(dx, dx_ref, dx_mag, xs, kind, Kb, X.cdiv(Kb, X.BK), '%s %s data gradient' % (name, kind))
+
+    cx, cdy = (dyd, xd) if tr else (xd, dyd)
+    dsc = ops.conv_desc(N, H, W, Cip, Cop, k, s, p, cx.stride(3), cdy.stride(3))
+    S = ops.lib().gcc_conv_wgrad_workspace(C.byref(dsc)) // (Cop * k * k * ceil8(Cip) * 4)
+    if slabs:
+        assert S == slabs, 'the plan gives %d slabs, this case is written for %d' % (S, slabs)
+    fold = 'wgrad_reduce_kernel<16,16>' if S >= 32 else 'wgrad_reduce_kernel<64,4>'
+    print('ROUTE segmented %s %s: %d slabs, %s' % (name, kind, S, fold))
+    M = X.k_products(g, 'W')
+    dw = torch.full_like(c.weight.grad, 7.0)                  # stale contents must not survive a fresh gradient
+    ops.conv_wgrad_seg(cx, cdy, dw, rows, cols, rs, cs, k, s, p, accumulate=False)
+    fresh = dw.cpu().clone()
+    assert fresh.shape == dw_ref.shape
+    if kind == 'int':
+        bad = fresh.double() != dw_ref
+        assert not bool(bad.any()), '%s: %d of %d weight-gradient entries are not the exact integer, first at %s' % (
+            name, int(bad.sum()), bad.numel(), tuple(int(v) for v in bad.nonzero()[0]))
+        ops.conv_wgrad_seg(cx, cdy, dw, rows, cols, rs, cs, k, s, p, accumulate=True)
+        assert torch.equal(dw.cpu().double(), 2 * dw_ref), name + ': accumulating does not give exactly twice'
+        ratios['wgrad'] = 0.0
+    else:
+        ratios['wgrad'] = within(fresh, dw_ref, X.bound_wgrad(dw_mag, M, S), '%s normal weight gradient' % name)
+    again = torch.full_like(dw, -3.0)
+    ops.conv_wgrad_seg(cx, cdy, again, rows, cols, rs, cs, k, s, p, accumulate=False)
+    assert torch.equal(again.cpu().view(torch.int32), fresh.view(torch.int32)), name + ': a second run gives other bits'
+    xg, dyg = to_phys(x.float(), xs, pad_value=0.75), to_phys(dy.float(), ys, pad_value=-1.5)
+    cxg, cdyg = (dyg, xg) if tr else (xg, dyg)
+    dw2 = torch.zeros_like(dw)
+    ops.conv_wgrad_seg(cxg, cdyg, dw2, rows, cols, rs, cs, k, s, p, accumulate=False)
+    assert torch.equal(dw2.cpu().view(torch.int32), fresh.view(torch.int32)), name + ': pad / gap lanes of x / dy leak into the weight gradient'
+    print('RATIO segmented %s %s %s' % (name, kind, ' '.join('%s=%.3g' % kv for kv in sorted(ratios.items()))))
 
 
 def _probe(lib, buf, Co, Ci, rows, cols, rs, cs):
