@@ -119,6 +119,9 @@ DISTILL_PLAN = ('off_scal', 'off_gf', 'off_gt', 'off_s', 'off_dfg', 'ws_bytes', 
                 'gram_co_tiles', 'gram_fold', 'bwd_route', 'bwd_bp', 'bwd_bc', 'bwd_ntiles', 'bwd_mtiles', 'fwd_launches',
                 'bwd_launches')
 KID_TILE, KID_KSTEP = 128, 16                                # include/gcc_hip.h GCC_KID_TILE, GCC_KID_KSTEP (gcc_kid_poly_sum)
+# include/gcc_hip.h GCC_PRDC_* (gcc_prdc_kth_dist, gcc_prdc_ball_count)
+PRDC_TILE, PRDC_COL_TILE, PRDC_SMALL_TILE, PRDC_SMALL_BELOW, PRDC_KSTEP = 128, 128, 64, 256, 16
+PRDC_MAX_K, PRDC_MAX_CHUNKS, PRDC_FILL_WORKGROUPS = 8, 16, 512
 
 
 class dw_inorm_t(C.Structure):
@@ -331,6 +334,11 @@ PROTOTYPES = {
     'gcc_frechet_distance': (_I, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P, _Z, _P]),
     'gcc_kid_workspace': (_Z, [_I, _I, _I]),
     'gcc_kid_poly_sum': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    'gcc_prdc_workspace': (_Z, [_I, _I, _I]),
+    'gcc_prdc_tile': (_I, [_I, _I]),
+    'gcc_prdc_chunks': (_I, [_I, _I]),
+    'gcc_prdc_kth_dist': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    'gcc_prdc_ball_count': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _Z, _P]),
     'gcc_attention_fwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_bwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_infer': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),

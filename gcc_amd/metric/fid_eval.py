@@ -17,6 +17,10 @@ With a feature file real_act*.npz beside every real_stat*.npz the evaluation nee
 Kernel Inception Distance (kid_score.polynomial_mmd2), three gcc_kid_poly_sum calls per slot, the real set's self term once
 per run.  Checkpoints are still chosen by FID alone.  Without the files nothing is stored, launched or logged for it.
 
+``GCC_FID_PRDC=<k>`` (1..GCC_PRDC_MAX_K; unset, empty or 0: off) adds one more line after the KID line: ``Precision: %.4f |
+Recall: %.4f | Density: %.4f | Coverage: %.4f`` of the same activations (prdc_score.prdc with k nearest neighbours), the real
+set's radii computed once per run.  It needs the feature files: with the variable set and one missing, the scorer raises.
+
 The one deliberate difference from the reference: it runs Inception at batch 1 (its evaluations set opt.batch_size = 1); this
 evaluator batches up to 50 images (get_activations' own default).  An eval-mode network's output for an image does not depend on
 its batch neighbours, so the activations are those of the batch-1 run up to the network's own batched arithmetic."""
@@ -170,12 +174,20 @@ class FidScorer:
     is kept and nothing is launched for it.  ``kid_cache``: a dict that outlives the scorer (the evaluator's): the real sets'
     activations and self terms are loaded and computed once per run."""
 
-    def __init__(self, inception, dataroot, slots, batch_size=50, kid_cache=None):
+    def __init__(self, inception, dataroot, slots, batch_size=50, kid_cache=None, prdc_k=None):
         from .kid_score import features_name
+        from .prdc_score import ENV as PRDC_ENV, check_k
         self.files = [os.path.join(str(dataroot), name) for name, _ in slots]
         self.tags = [tag for _, tag in slots]
         self.feature_files = [features_name(f) for f in self.files]
         self.with_kid = bool(slots) and all(f is not None and os.path.isfile(f) for f in self.feature_files)
+        self.prdc_k = None if prdc_k is None else check_k(prdc_k, PRDC_ENV)
+        if self.prdc_k is not None and not self.with_kid:
+            missing = [(f, s) for f, s in zip(self.feature_files, self.files) if f is None or not os.path.isfile(f)]
+            raise GccError('%s=%d needs the real activations of every slot: %s missing (python -m gcc_amd.metric.get_real_stat '
+                           '--dataroot ... --output_path %s --features_path %s writes it)'
+                           % (PRDC_ENV, self.prdc_k, ', '.join(str(f or s) for f, s in missing), missing[0][1],
+                              missing[0][0] or 'real_act*.npz'))
         self.kid_cache = kid_cache if kid_cache is not None else {}
         self.label = network_label(inception)
         self.stats = [ImageStatistics(inception, batch_size, keep_features=self.with_kid) for _ in slots]
@@ -219,6 +231,26 @@ class FidScorer:
             values.append(polynomial_mmd2(real, fake, self_x=real_self))
         return values
 
+    def prdc(self):
+        """one {'precision', 'recall', 'density', 'coverage'} per slot at the scorer's k, or None when it was made without one.
+        The real set's radii are computed on the first evaluation of a run and kept beside its KID self term."""
+        if self.prdc_k is None:
+            return None
+        from . import prdc_score
+        values = []
+        for path, st in zip(self.feature_files, self.stats):
+            if st.count <= self.prdc_k:
+                raise GccError('precision / recall / density / coverage with k = %d need more than k images, %d were scored'
+                               % (self.prdc_k, st.count))
+            st.flush()
+            fake = st.features.rows()
+            real, _ = self._real_features(path, fake.shape[1], fake.device)
+            key = (path, 'radii', self.prdc_k)
+            if key not in self.kid_cache:
+                self.kid_cache[key] = prdc_score.nearest_radii(real, self.prdc_k)
+            values.append(prdc_score.prdc(real, fake, self.prdc_k, real_radii=self.kid_cache[key]))
+        return values
+
 
 def fid_line(values, tags, model):
     if 'cyclegan' in model:
@@ -232,6 +264,13 @@ def kid_line(values, tags, model):
     return 'KID: %.6f' % values[0]
 
 
+def prdc_line(values, tags, model):
+    from .prdc_score import prdc_text
+    if 'cyclegan' in model:
+        return ' | '.join('%s %s' % (t, prdc_text(v)) for v, t in zip(values, tags))
+    return prdc_text(values[0])
+
+
 def fid_evaluator(inception, logger=None, batch_size=50):
     """evaluate(model, opt) for gcc_amd.train.run_evaluation: test_pix2pix_fid / test_cyclegan_fid / test_sagan_fid.
     ``evaluate.scorer(model, opt)`` gives python -m gcc_amd.test the scorer of the images it writes.  Inception runs on batches
@@ -241,7 +280,8 @@ def fid_evaluator(inception, logger=None, batch_size=50):
     def scorer(model, opt):
         if state['inception'] is None:
             state['inception'] = _prepare(inception, model.device)
-        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size, kid_cache=state['kid'])
+        from .prdc_score import env_k
+        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size, kid_cache=state['kid'], prdc_k=env_k())
 
     def evaluate(model, opt):
         from ..data import create_dataset
@@ -269,6 +309,9 @@ def fid_evaluator(inception, logger=None, batch_size=50):
         kid = sc.kid()                             # None without a feature file beside every real_stat*.npz: no line, no launch
         if kid is not None and logger is not None:
             logger.info(kid_line(kid, sc.tags, opt.model))
+        prdc = sc.prdc()                           # None unless GCC_FID_PRDC names a k
+        if prdc is not None and logger is not None:
+            logger.info(prdc_line(prdc, sc.tags, opt.model))
         return list(zip(values, sc.tags))
 
     evaluate.state = state

@@ -2,10 +2,12 @@
 distance with a Newton-Schulz matrix square root; and the reference's path-based half (:55-145, 287-322, 332-370): image folders,
 statistics files and feature files scored against each other,
 
-    python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 2048] [-c GPU]
+    python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 2048] [-c GPU] [--prdc [--nearest-k 5]]
 
 prints ``FID: %.2f`` and, when both sides have activations (folders, or the feature files get_real_stat --features_path writes),
-``KID: %.6f`` (gcc_amd.metric.kid_score).  No CPU path: a missing library / GPU raises GccError."""
+``KID: %.6f`` (gcc_amd.metric.kid_score); with --prdc one more line, ``Precision: %.4f | Recall: %.4f | Density: %.4f | Coverage:
+%.4f`` (gcc_amd.metric.prdc_score) of the second path against the first as the real set.  No CPU path: a missing library / GPU
+raises GccError."""
 import argparse
 import os
 
@@ -162,6 +164,10 @@ parser.add_argument('path', type=str, nargs=2,
 parser.add_argument('--batch-size', type=int, default=50, help='images per pass of the network')
 parser.add_argument('--dims', type=int, default=2048, choices=list(DIMS), help='width of the network\'s features')
 parser.add_argument('-c', '--gpu', default='', type=str, help='index of the GPU to use (blank: the current device; there is no CPU path)')
+parser.add_argument('--prdc', action='store_true',
+                    help='also print precision, recall, density and coverage (gcc_amd.metric.prdc_score) of the second path '
+                         'against the first as the real set; both sides need activations: folders or real_act*.npz')
+parser.add_argument('--nearest-k', type=int, default=5, help='the k of the nearest-neighbour balls of --prdc')
 
 
 def list_image_files(path):
@@ -315,9 +321,11 @@ def calculate_fid_given_ims(ims_fake, ims_real, batch_size, cuda, dims, model=No
     return calculate_frechet_distance(*stats[0], *stats[1])
 
 
-def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqdm=False, kid=False):
+def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqdm=False, kid=False, prdc_k=None):
     """metric/fid_score.py:350-370: the FID of two paths, each a folder of images, a real_stat*.npz or a real_act*.npz feature
-    file.  ``kid``: return (FID, KID) instead, KID None unless both sides have activations (folders or feature files)."""
+    file.  ``kid``: return (FID, KID) instead, KID None unless both sides have activations (folders or feature files).
+    ``prdc_k``: return (FID, KID, prdc_score.prdc(first, second, k)) -- the first path is the real set, as the FID's arguments
+    are ordered; a side without activations is a GccError that names it."""
     for p in paths:
         if not os.path.exists(str(p)):
             raise RuntimeError('Invalid path: %s' % p)
@@ -325,11 +333,20 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqd
     (m1, s1, a1), (m2, s2, a2) = (_path_statistics(p, net, batch_size, dims, cuda) for p in paths[:2])
     if tuple(m1.shape) != (dims,) or tuple(m2.shape) != (dims,):
         raise GccError('the statistics have mu %s and %s, dims = %d was asked for' % (tuple(m1.shape), tuple(m2.shape), dims))
+    if prdc_k is not None:
+        for p, a in zip(paths[:2], (a1, a2)):
+            if a is None:
+                raise GccError('fid_score --prdc: %s holds statistics (mu, sigma) only; precision / recall / density / coverage '
+                               'need the activations: a folder of images or a real_act*.npz (get_real_stat --features_path)' % p)
     fid_value = calculate_frechet_distance(m1, s1, m2, s2)
-    if not kid:
+    if not kid and prdc_k is None:
         return fid_value
     from .kid_score import polynomial_mmd2
-    return fid_value, (polynomial_mmd2(a1, a2) if a1 is not None and a2 is not None else None)
+    kid_value = polynomial_mmd2(a1, a2) if a1 is not None and a2 is not None else None
+    if prdc_k is None:
+        return fid_value, kid_value
+    from .prdc_score import prdc
+    return fid_value, kid_value, prdc(a1, a2, prdc_k)
 
 
 def main(argv=None, model=None):
@@ -338,11 +355,18 @@ def main(argv=None, model=None):
         raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU')
     if args.gpu != '':
         torch.cuda.set_device(int(args.gpu))
-    fid_value, kid_value = calculate_fid_given_paths(args.path, args.batch_size, True, args.dims, model=model, kid=True)
+    prdc_k = None
+    if args.prdc:
+        from .prdc_score import check_k, prdc_text
+        prdc_k = check_k(args.nearest_k, '--nearest-k')
+    values = calculate_fid_given_paths(args.path, args.batch_size, True, args.dims, model=model, kid=True, prdc_k=prdc_k)
+    fid_value, kid_value = values[:2]
     print('FID: %.2f' % fid_value)
     if kid_value is not None:
         print('KID: %.6f' % kid_value)
-    return fid_value, kid_value
+    if prdc_k is not None:
+        print(prdc_text(values[2]))
+    return values
 
 
 if __name__ == '__main__':

@@ -1367,6 +1367,69 @@ def kid_poly_sum(X, Y=None, out=None, slot='kid'):
     return out
 
 
+def prdc_workspace_bytes(m, n, k):
+    """gcc_prdc_workspace: per row and chunk of columns, k doubles (or one integer), never the m x n distances"""
+    return lib().gcc_prdc_workspace(m, n, k)
+
+
+def prdc_chunks(m, n):
+    """gcc_prdc_chunks: the column ranges the library splits n columns into for m rows when `chunks` is 0"""
+    return lib().gcc_prdc_chunks(m, n)
+
+
+def prdc_tile(m, n):
+    """gcc_prdc_tile: the tile side (rows and columns) the library walks m rows against n columns with when `tile` is 0"""
+    return lib().gcc_prdc_tile(m, n)
+
+
+def prdc_kth_dist(X, Y=None, k=5, out=None, chunks=0, tile=0, slot='prdc'):
+    """gcc_prdc_kth_dist: out[i] (f64 [m] on the device, made if not given) = the k-th smallest over j of the squared distance
+    |x_i - y_j|^2 of the rows of X [m, d] to those of Y [n, d]; Y None: the symmetric form, the rows j != i of X itself.
+    ``chunks``, ``tile``: 0 for the library's choice, a positive value forces it (the bits do not depend on either).  Nothing is
+    read back."""
+    X, xp, xf, ldx, m, d = _kid_rows(X, 'prdc_kth_dist')
+    k, chunks = int(k), int(chunks)
+    symmetric = Y is None
+    if symmetric:
+        Y, yp, yf, ldy, n = X, xp, xf, ldx, m
+    else:
+        Y, yp, yf, ldy, n, dy = _kid_rows(Y, 'prdc_kth_dist')
+        if dy != d or Y.device != X.device:
+            raise _lib.GccError('prdc_kth_dist: %s on %s against %s on %s' % (tuple(X.shape), X.device, tuple(Y.shape), Y.device))
+    most = n - 1 if symmetric else n
+    if not 1 <= k <= min(_lib.PRDC_MAX_K, most):
+        raise _lib.GccError('prdc_kth_dist: k = %d, expected 1..%d (at most GCC_PRDC_MAX_K = %d and the %d rows to choose from)'
+                            % (k, min(_lib.PRDC_MAX_K, most), _lib.PRDC_MAX_K, most))
+    if out is None:
+        out = torch.empty(m, dtype=torch.float64, device=X.device)
+    if out.dtype != torch.float64 or out.dim() != 1 or out.numel() != m or not out.is_contiguous() or out.device != X.device:
+        raise _lib.GccError('prdc_kth_dist: out must be a contiguous f64 [%d] tensor on %s' % (m, X.device))
+    ws = workspace(prdc_workspace_bytes(m, n, k), X.device, slot)
+    check(lib().gcc_prdc_kth_dist(xp, xf, ldx, m, yp, yf, ldy, n, d, int(symmetric), k, chunks, int(tile), out.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), stream()), 'gcc_prdc_kth_dist')
+    return out
+
+
+def prdc_ball_count(Q, C, r2, out=None, chunks=0, tile=0, slot='prdc'):
+    """gcc_prdc_ball_count: out[j] (int32 [m] on the device, made if not given) = the number of centres i, rows of C [n, d], whose
+    ball of squared radius r2[i] (f64 [n]) holds the query q_j, row j of Q [m, d]: |q_j - c_i|^2 <= r2[i], inclusive."""
+    Q, qp, qf, ldq, m, d = _kid_rows(Q, 'prdc_ball_count')
+    C, cp, cf, ldc, n, dc = _kid_rows(C, 'prdc_ball_count')
+    if dc != d or C.device != Q.device:
+        raise _lib.GccError('prdc_ball_count: %s on %s against %s on %s' % (tuple(Q.shape), Q.device, tuple(C.shape), C.device))
+    if not torch.is_tensor(r2) or r2.dtype != torch.float64 or r2.dim() != 1 or r2.numel() != n or not r2.is_contiguous() or \
+            r2.device != Q.device:
+        raise _lib.GccError('prdc_ball_count: r2 must be a contiguous f64 [%d] tensor on %s' % (n, Q.device))
+    if out is None:
+        out = torch.empty(m, dtype=torch.int32, device=Q.device)
+    if out.dtype != torch.int32 or out.dim() != 1 or out.numel() != m or not out.is_contiguous() or out.device != Q.device:
+        raise _lib.GccError('prdc_ball_count: out must be a contiguous int32 [%d] tensor on %s' % (m, Q.device))
+    ws = workspace(prdc_workspace_bytes(m, n, 1), Q.device, slot)
+    check(lib().gcc_prdc_ball_count(qp, qf, ldq, m, cp, cf, ldc, n, d, r2.data_ptr(), int(chunks), int(tile), out.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), stream()), 'gcc_prdc_ball_count')
+    return out
+
+
 def conv_eval_rect(x, w, Co, kernel, stride, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slot='eval', route_only=False):
     """inference conv with a (kh, kw) kernel and NO padding (gcc_conv_eval_ex with KH != KW allowed): out = act(scale[c] conv(x, w)
     + shift[c]).  gcc_conv_t has one `pad` for both directions, so a rectangular kernel's own padding (ph, pw) is border_copy's

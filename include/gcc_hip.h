@@ -1229,6 +1229,55 @@ size_t gcc_kid_workspace(int m, int n, int d);
 int gcc_kid_poly_sum(const void* X, int x_f64, int ldx, int m, const void* Y, int y_f64, int ldy, int n, int d, int symmetric,
                      double* out, void* ws, size_t ws_bytes, gcc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) on the same activations: the pairwise
+ * half (gcc_amd/csrc/prdc.hip, gcc_amd/metric/prdc_score.py).  Added without a GCC_HIP_ABI bump (additions only).
+ * Rows are given as in gcc_kid_poly_sum: fp32 (*_f64 == 0) or f64 rows of d elements, row stride ld >= d elements; what lies
+ * between d and ld, or after the last row, is never read.  Any m, n, d >= 1.
+ * The distance.  D(x, y) = sum_c (x_c - y_c)^2 in f64, the DIFFERENCE form: t = x_c - y_c (fp32 inputs are converted first,
+ *   exactly), acc = fma(t, t, acc), for c = 0, 1, ..., d - 1 in this order from acc = +0: one chain of d subtractions and d fused
+ *   multiply-adds per pair, two roundings per element.  Hence D >= 0, D(x, x') == 0 exactly for equal rows, D(x, y) == D(y, x)
+ *   bit for bit, |D_computed - D| <= gamma_{d+2} D (relative to D itself, gamma_n = n u / (1 - n u), u = 2^-53: the subtraction's
+ *   rounding enters squared, every term is non-negative and passes at most d additions), and the bits of D(i, j) are a function
+ *   of the two rows and d alone -- not of where they sit in X / Y, of m, n, k, of `chunks` or of the tile.
+ * gcc_prdc_kth_dist: out[i] (f64, i < m) = the k-th smallest over j < n of D(x_i, y_j).  symmetric != 0: Y is X (the Y-side
+ *   arguments are not read) and j == i is left out.  1 <= k <= GCC_PRDC_MAX_K, and k <= n (symmetric: k <= m - 1).
+ * gcc_prdc_ball_count: out[j] (int, j < m) = #{ i < n : D(q_j, c_i) <= r2[i] }; r2: n f64 squared radii.  <= is inclusive.
+ * A workgroup owns T rows and walks one of `chunks` ranges of T-column tiles (range c of the N = ceil(n / T) column tiles is
+ *   [c N / chunks, (c + 1) N / chunks)), d in steps of GCC_PRDC_KSTEP; the distances are consumed in registers and never stored:
+ *   ws receives, per row and chunk, the k smallest so far (k doubles) or a count (one int), and a second launch merges them per
+ *   row.  T, rows and columns alike, is GCC_PRDC_TILE (= GCC_PRDC_COL_TILE) where that tile can give every compute unit a
+ *   workgroup -- ceil(m / 128) min(ceil(n / 128), GCC_PRDC_MAX_CHUNKS) >= GCC_PRDC_SMALL_BELOW -- and GCC_PRDC_SMALL_TILE below:
+ *   a quarter of the work per workgroup and four times the workgroups for the sets of 120 to 1000 images this project scores.
+ *   gcc_prdc_tile(m, n) says which; `tile` == 0 takes it, either constant forces it (for tests).  chunks == 0: the library's
+ *   choice gcc_prdc_chunks(m, n) = min(ceil(GCC_PRDC_FILL_WORKGROUPS / ceil(m / T)), N, GCC_PRDC_MAX_CHUNKS) at T =
+ *   gcc_prdc_tile(m, n) (with `tile` forced: the same formula at that tile), a function of (m, n) alone; 1 <= chunks <= min(N,
+ *   GCC_PRDC_MAX_CHUNKS) forces it.  The k smallest of a multiset and a sum of integers do not depend on order, and both tiles
+ *   run the same chain per pair: every legal `chunks` and either tile give the same bits.  No floating-point atomics, no
+ *   workgroup waits for another: the same input gives the same bits.  Two launches each.
+ * gcc_prdc_workspace(m, n, k): bytes that serve either entry at m rows against n at any legal `chunks` and `tile` (m min(ceil(n
+ *   / GCC_PRDC_SMALL_TILE), GCC_PRDC_MAX_CHUNKS) k doubles; ball_count needs no more than k = 1); 0 for a size < 1 or k outside
+ *   1..GCC_PRDC_MAX_K.
+ * GCC_ERR_BAD_ARG (a null pointer, a size < 1, ld < d, k out of range or above the number of admissible j, a `tile` that is
+ *   neither constant nor 0, `chunks` negative or above what n and the tile admit), GCC_ERR_WORKSPACE (ws_bytes short of what the
+ *   chunks in use need) and GCC_ERR_UNSUPPORTED (2^31 workgroups or more) are returned before anything is launched.
+ * --------------------------------------------------------------------------------------------- */
+#define GCC_PRDC_TILE 128
+#define GCC_PRDC_COL_TILE 128
+#define GCC_PRDC_SMALL_TILE 64
+#define GCC_PRDC_SMALL_BELOW 256
+#define GCC_PRDC_KSTEP 16
+#define GCC_PRDC_MAX_K 8
+#define GCC_PRDC_MAX_CHUNKS 16
+#define GCC_PRDC_FILL_WORKGROUPS 512
+size_t gcc_prdc_workspace(int m, int n, int k);
+int gcc_prdc_tile(int m, int n);
+int gcc_prdc_chunks(int m, int n);
+int gcc_prdc_kth_dist(const void* X, int x_f64, int ldx, int m, const void* Y, int y_f64, int ldy, int n, int d, int symmetric,
+                      int k, int chunks, int tile, double* out, void* ws, size_t ws_bytes, gcc_stream_t stream);
+int gcc_prdc_ball_count(const void* Q, int q_f64, int ldq, int m, const void* C, int c_f64, int ldc, int n, int d,
+                        const double* r2, int chunks, int tile, int* out, void* ws, size_t ws_bytes, gcc_stream_t stream);
+
 /* ---- gradient exchange ---------------------------------------------------------------------------------
  * The reference trains on one device (models/Pix2Pix.py:356); the data-parallel path sums the five optimizers' flat fp32
  * gradient buffers over ranks before each `optimizer.step()` (train.py has no counterpart: this is the exchange a
