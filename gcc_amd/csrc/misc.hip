@@ -537,14 +537,25 @@ extern "C" int gcc_nhwc_bf16_to_nchw_f32(const void* src, float* dst, int N, int
     GCC_CHECK_LAUNCH();
     return GCC_OK;
 }
+// which kernel a channel-slice copy (or add: Cfill == C) runs on: 0 the 16-byte vector kernel (everything a multiple of 8), 1 the
+// one-group read-modify-write kernel, 2 the scalar kernel; GCC_ERR_BAD_ARG for a window that does not fit its row.  The launch
+// below takes its decision from here, so the query cannot say anything else.
+extern "C" int gcc_nhwc_copy_route(int lds, int soff, int ldd, int doff, int C, int Cfill) {
+    const int Cw = Cfill > C ? Cfill : C;
+    if (C <= 0 || soff < 0 || doff < 0 || soff + C > lds || doff + Cw > ldd) return GCC_ERR_BAD_ARG;
+    if (!((lds | soff | ldd | doff | C) & 7) && Cfill <= C) return 0;
+    if (!((lds | ldd) & 7) && (soff & 7) + C <= 8 && (doff & 7) + Cw <= 8) return 1;
+    return 2;
+}
 static int nhwc_copy_impl(const void* src, int lds, int soff, void* dst, int ldd, int doff, int C, int Cfill, size_t pixels,
                           int add, gcc_stream_t stream) {
-    if (!src || !dst || C <= 0 || pixels == 0 || soff + C > lds || doff + (Cfill > C ? Cfill : C) > ldd) return GCC_ERR_BAD_ARG;
-    const bool vec = !((lds | soff | ldd | doff | C) & 7) && Cfill <= C;
-    if (vec)
+    if (!src || !dst || pixels == 0) return GCC_ERR_BAD_ARG;
+    const int route = gcc_nhwc_copy_route(lds, soff, ldd, doff, C, Cfill);
+    if (route < 0) return route;
+    if (route == 0)
         hipLaunchKernelGGL(nhwc_copy_vec_kernel, dim3(grid_for(pixels * (C / 8))), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)src, lds, soff, (bf16_t*)dst, ldd, doff, C / 8, pixels, add);
-    else if (!((lds | ldd) & 7) && (soff & 7) + C <= 8 && (doff & 7) + (Cfill > C ? Cfill : C) <= 8)
+    else if (route == 1)
         hipLaunchKernelGGL(nhwc_copy_group_kernel, dim3(grid_for(pixels)), dim3(256), 0, (hipStream_t)stream,
                            (const bf16_t*)src, lds, soff, (bf16_t*)dst, ldd, doff, C, Cfill, pixels, add);
     else

@@ -284,6 +284,11 @@ int gcc_nhwc_bf16_to_nchw_f32(const void* src, float* dst, int N, int C, int H, 
  * required; [C, Cfill) zero-filled in dst). */
 int gcc_nhwc_copy(const void* src, int lds, int soff, void* dst, int ldd, int doff, int C, int Cfill,
                   size_t pixels, gcc_stream_t stream);
+/* The kernel gcc_nhwc_copy (and gcc_nhwc_add, with Cfill = C) runs a window on: 0 vector (16-byte accesses: lds, soff, ldd, doff
+ * and C multiples of 8, nothing to zero-fill), 1 group (source and destination window each inside one aligned 8-channel group of
+ * rows that are multiples of 8: one 16-byte read-modify-write per pixel), 2 scalar; GCC_ERR_BAD_ARG for a window the entries
+ * refuse (C <= 0, a negative offset, soff + C > lds, doff + max(C, Cfill) > ldd).  Host only: the entries decide by this call. */
+int gcc_nhwc_copy_route(int lds, int soff, int ldd, int doff, int C, int Cfill);
 /* channel concatenation of two thin tensors into one 8-wide group: dst[.., doff + c] = a[.., aoff + c] (c < Ca), then
  * b[.., boff + c] (c < Cb), zeros up to 8 (Ca + Cb <= 8).  Replaces torch.cat((real_A, fake_B), 1) at
  * models/Pix2Pix.py:466-470, 483 (the discriminator's conditional input). */

@@ -17,7 +17,9 @@ backward route, in channel windows and in eval mode, in tests/test_norm_kernels_
 weight-gradient form) bit for bit on integer data, per element against float64 and with exact statistic rows, each test
 asserting the route it ran on, in tests/test_conv_bf16_exact_gpu.py (its checks examined in tests/test_conv_bounds_cpu.py);
 gcc_conv_bn_act on each of its three routes, at every regime of the grid fold and through every fallback, in
-tests/test_convbn_exact_gpu.py (tests/test_convbn_bounds_cpu.py).
+tests/test_convbn_exact_gpu.py (tests/test_convbn_bounds_cpu.py); the channel sums, the layout copies and conversions, the weight
+packings and the gate mask, bit for bit and per element against float64 on every fold, route and alignment, in
+tests/test_plumbing_exact_gpu.py (tests/test_plumbing_bounds_cpu.py).
 The one-shape tests of those kernels below stay as they are."""
 import math
 import os
