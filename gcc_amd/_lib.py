@@ -122,6 +122,7 @@ KID_TILE, KID_KSTEP = 128, 16                                # include/gcc_hip.h
 # include/gcc_hip.h GCC_PRDC_* (gcc_prdc_kth_dist, gcc_prdc_ball_count)
 PRDC_TILE, PRDC_COL_TILE, PRDC_SMALL_TILE, PRDC_SMALL_BELOW, PRDC_KSTEP = 128, 128, 64, 256, 16
 PRDC_MAX_K, PRDC_MAX_CHUNKS, PRDC_FILL_WORKGROUPS = 8, 16, 512
+MAP_MEAN_MAX_SEGMENTS, MAP_MEAN_PIXELS_PER_THREAD = 64, 64   # include/gcc_hip.h GCC_MAP_MEAN_* (gcc_map_mean)
 
 
 class dw_inorm_t(C.Structure):
@@ -320,6 +321,10 @@ PROTOTYPES = {
     'gcc_fid_resize_f32': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     'gcc_pool3x3_f32': (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     'gcc_global_avgpool_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'gcc_map_mean_segments': (_I, [_I, _I, _I]),
+    'gcc_map_mean_workspace': (_Z, [_I, _I, _I, _I]),
+    'gcc_map_mean': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    'gcc_map_mean_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     'gcc_argmax_channels': (_I, [_P, _I, _I, _Z, _P, _P]),
     'gcc_confusion_hist': (_I, [_P, _P, _Z, _I, _P, _P]),
     'gcc_psnr_workspace': (_Z, []),

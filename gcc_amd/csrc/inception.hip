@@ -7,6 +7,8 @@
 //   gcc_border_copy      an NHWC bf16 channel window copied into the middle of a map with a zero border of (ph, pw) pixels, border
 //                        included: a (1, 7) / (7, 1) / (1, 3) / (3, 1) convolution with its own padding is then a padding-0 call
 //   gcc_global_avgpool   the mean over the pixels of an NHWC bf16 channel window in fp32
+//   gcc_map_mean         the same mean of a LARGE map (the network's earlier output blocks) in f64, the pixels of an image split
+//                        over workgroups: the one kernel here that is not one thread per chunk (see map_mean_kernel)
 // gcc_fid_resize_f32 / gcc_pool3x3_f32 / gcc_global_avgpool_f32 are the same kernels on NHWC fp32 maps (the network at the
 // reference's own precision, around gcc_conv_eval_f32_ex): the same arithmetic in the same order without the bf16 roundings, a
 // 16-byte chunk holding 4 channels.  Rectangular padding is the fp32 convolution's own index arithmetic: no fp32 border copy.
@@ -33,6 +35,7 @@ template <typename T> struct Chunk;
 template <> struct Chunk<bf16_t> {
     static constexpr int CH = 8;
     static __device__ __forceinline__ void load(const bf16_t* p, float* f) { unpack8(*(const i32x4*)p, f); }
+    static __device__ __forceinline__ void unpack(const i32x4& v, float* f) { unpack8(v, f); }
     static __device__ __forceinline__ void store(bf16_t* p, const float* f) { *(i32x4*)p = pack8(f); }
 };
 template <> struct Chunk<float> {
@@ -43,6 +46,10 @@ template <> struct Chunk<float> {
         for (int j = 0; j < 4; j++) f[j] = v[j];
     }
     static __device__ __forceinline__ void store(float* p, const float* f) { *(f32x4*)p = f32x4{f[0], f[1], f[2], f[3]}; }
+    static __device__ __forceinline__ void unpack(const i32x4& v, float* f) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) f[j] = __int_as_float(v[j]);
+    }
 };
 
 // torch's area_pixel_compute_source_index (align_corners = False, not cubic): index and the weight of the upper neighbour.  The
@@ -193,9 +200,123 @@ __global__ __launch_bounds__(IN_THREADS) void global_avgpool_kernel(const T* __r
     }
 }
 
+// gcc_map_mean: the mean of a LARGE map (the 73 x 73, 35 x 35 and 17 x 17 taps of the network), the pixels of an image split over
+// workgroups.  Workgroup (n, cb, s) owns image n, a block of CW chunks and pixel range [s P / S, (s + 1) P / S); its MM_THREADS
+// threads are R = MM_THREADS / CW pixel rows of CW chunk lanes: thread (pr, cl) adds pixels lo + pr, lo + pr + R, ... of its chunk
+// in f64, ascending, MM_FLIGHT 16-byte loads in flight.  The R rows are then folded through LDS in ascending pr by one thread per
+// channel.  S == 1: that sum is divided and stored; S > 1: it goes to ws [n][s][C] and map_mean_fold_kernel adds the segments in
+// ascending s.  CW is a function of C alone, so the order is a function of (P, C, S): no atomics, nothing grid-wide.
+constexpr int MM_THREADS = 256, MM_FLIGHT = 8;
+
+template <typename T>
+__global__ __launch_bounds__(MM_THREADS) void map_mean_kernel(const T* __restrict__ x, int ld, int off, int P, int C, int CW, int CB,
+                                                               int S, float* __restrict__ out, double* __restrict__ ws) {
+    constexpr int CH = Chunk<T>::CH;
+    __shared__ double part[MM_THREADS * CH];
+    const int b = blockIdx.x;
+    const int s = b % S, cb = (b / S) % CB;
+    const size_t n = (size_t)(b / S / CB);
+    const int t = threadIdx.x, R = MM_THREADS / CW;
+    const int cl = t % CW, pr = t / CW;
+    const int lo = (int)((long long)s * P / S), hi = (int)((long long)(s + 1) * P / S);
+    const T* p = x + n * (size_t)P * ld + off + (size_t)(cb * CW + cl) * CH;
+    double acc[CH];
+#pragma unroll
+    for (int j = 0; j < CH; j++) acc[j] = 0.0;
+    for (int q = lo + pr; q < hi; q += MM_FLIGHT * R) {
+        i32x4 v[MM_FLIGHT];                                              // the chunks as loaded: converted when they are added
+#pragma unroll
+        for (int u = 0; u < MM_FLIGHT; u++) {
+            const int qq = q + u * R;
+            v[u] = qq < hi ? *(const i32x4*)(p + (size_t)qq * ld) : i32x4{0, 0, 0, 0};      // + 0.0 leaves an f64 sum as it is
+        }
+#pragma unroll
+        for (int u = 0; u < MM_FLIGHT; u++) {
+            float f[CH];
+            Chunk<T>::unpack(v[u], f);
+#pragma unroll
+            for (int j = 0; j < CH; j++) acc[j] += (double)f[j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CH; j++) part[t * CH + j] = acc[j];              // [pr][cl][j]
+    __syncthreads();
+    const int W = CW * CH;                                                // channels of this workgroup, <= MM_THREADS
+    if (t < W) {
+        double sum = 0.0;
+        for (int r = 0; r < R; r++) sum += part[r * W + t];
+        const int c = cb * W + t;
+        if (S == 1) out[n * C + c] = (float)(sum / (double)P);
+        else ws[(n * S + s) * C + c] = sum;
+    }
+}
+
+__global__ __launch_bounds__(IN_THREADS) void map_mean_fold_kernel(const double* __restrict__ ws, int S, int C, int P,
+                                                                    float* __restrict__ out, size_t total) {
+    for (size_t i = (size_t)blockIdx.x * IN_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * IN_THREADS) {
+        const size_t n = i / C;
+        const int c = (int)(i - n * C);
+        const double* p = ws + n * S * C + c;
+        double sum = 0.0;
+        for (int s = 0; s < S; s++) sum += p[(size_t)s * C];
+        out[i] = (float)(sum / (double)P);
+    }
+}
+
 }  // namespace
 
 namespace {
+
+// the chunk lanes of a gcc_map_mean workgroup: the largest power of two that divides the chunks, at most MM_THREADS / CH (one
+// thread per channel folds)
+template <typename T> int map_mean_cw(int C) {
+    constexpr int CH = Chunk<T>::CH;
+    const int chunks = C / CH;
+    int cw = 1;
+    while (cw * 2 * CH <= MM_THREADS && chunks % (cw * 2) == 0) cw *= 2;
+    return cw;
+}
+inline int map_mean_max_segments(size_t P) { return (int)(P < GCC_MAP_MEAN_MAX_SEGMENTS ? P : GCC_MAP_MEAN_MAX_SEGMENTS); }
+// the library's split, the same for both element types: a thread of the fp32 kernel adds about GCC_MAP_MEAN_PIXELS_PER_THREAD
+// pixels of a segment (one of the bf16 kernel, whose chunks hold twice the channels, half as many)
+int map_mean_segments(size_t P, int C) {
+    const size_t rows = MM_THREADS / map_mean_cw<float>(C);
+    const size_t s = P / (rows * GCC_MAP_MEAN_PIXELS_PER_THREAD);
+    const size_t most = map_mean_max_segments(P);
+    return (int)(s < 1 ? 1 : (s > most ? most : s));
+}
+
+template <typename T>
+int map_mean_impl(const T* x, int ld, int off, int N, int h, int w, int C, int segments, float* out, void* ws, size_t ws_bytes,
+                  gcc_stream_t stream) {
+    constexpr int CH = Chunk<T>::CH;
+    GCC_ENTER();
+    if (!out || N <= 0 || h <= 0 || w <= 0 || C <= 0 || segments < 0) return GCC_ERR_BAD_ARG;
+    if (!in_window_ok(x, ld, off, (C + CH - 1) / CH * CH, CH) || (((uintptr_t)out) & 15)) return GCC_ERR_BAD_ARG;
+    if (C & (CH - 1)) return GCC_ERR_UNSUPPORTED;
+    const size_t P = (size_t)h * w;
+    if (P >= (size_t)1 << 24 || (size_t)N * P * ld >= (size_t)1 << 40) return GCC_ERR_UNSUPPORTED;
+    if (segments > map_mean_max_segments(P)) return GCC_ERR_BAD_ARG;
+    const int S = segments ? segments : map_mean_segments(P, C);
+    const int CW = map_mean_cw<T>(C), CB = C / CH / CW;
+    const size_t wgs = (size_t)N * CB * S;
+    if (wgs >= (size_t)1 << 31) return GCC_ERR_UNSUPPORTED;
+    if (S > 1) {
+        if (!ws || (((uintptr_t)ws) & 7)) return GCC_ERR_BAD_ARG;
+        if (ws_bytes < (size_t)N * S * C * sizeof(double)) return GCC_ERR_WORKSPACE;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(map_mean_kernel<T>, dim3((unsigned)wgs), dim3(MM_THREADS), 0, st, x, ld, off, (int)P, C, CW, CB, S, out,
+                       (double*)ws);
+    GCC_CHECK_LAUNCH();
+    if (S > 1) {
+        const size_t total = (size_t)N * C;
+        hipLaunchKernelGGL(map_mean_fold_kernel, dim3(in_blocks(total)), dim3(IN_THREADS), 0, st, (const double*)ws, S, C, (int)P, out,
+                           total);
+        GCC_CHECK_LAUNCH();
+    }
+    return GCC_OK;
+}
 
 template <typename T>
 int fid_resize_impl(const float* x, int N, int H, int W, T* y, int ld, int off, int Ho, int Wo, gcc_stream_t stream) {
@@ -306,4 +427,24 @@ extern "C" int gcc_global_avgpool(const void* x, int ld, int off, int N, int h, 
 
 extern "C" int gcc_global_avgpool_f32(const float* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream) {
     return global_avgpool_impl(x, ld, off, N, h, w, C, out, stream);
+}
+
+extern "C" int gcc_map_mean_segments(int h, int w, int C) {
+    if (h <= 0 || w <= 0 || C <= 0 || (C & 3)) return 0;
+    return map_mean_segments((size_t)h * w, C);
+}
+
+extern "C" size_t gcc_map_mean_workspace(int N, int h, int w, int C) {
+    if (N <= 0 || h <= 0 || w <= 0 || C <= 0) return 0;
+    return (size_t)N * map_mean_max_segments((size_t)h * w) * C * sizeof(double);
+}
+
+extern "C" int gcc_map_mean(const void* x, int ld, int off, int N, int h, int w, int C, int segments, float* out, void* ws,
+                            size_t ws_bytes, gcc_stream_t stream) {
+    return map_mean_impl((const bf16_t*)x, ld, off, N, h, w, C, segments, out, ws, ws_bytes, stream);
+}
+
+extern "C" int gcc_map_mean_f32(const float* x, int ld, int off, int N, int h, int w, int C, int segments, float* out, void* ws,
+                                size_t ws_bytes, gcc_stream_t stream) {
+    return map_mean_impl(x, ld, off, N, h, w, C, segments, out, ws, ws_bytes, stream);
 }

@@ -21,6 +21,11 @@ per run.  Checkpoints are still chosen by FID alone.  Without the files nothing 
 Recall: %.4f | Density: %.4f | Coverage: %.4f`` of the same activations (prdc_score.prdc with k nearest neighbours), the real
 set's radii computed once per run.  It needs the feature files: with the variable set and one missing, the scorer raises.
 
+``GCC_FID_DIMS=<64 | 192 | 768 | 2048>`` (unset or empty: 2048) scores with the reference's narrower output blocks
+(metric/inception.py BLOCK_INDEX_BY_DIM, the --dims of metric/fid_score.py): the native network stops after that block and its map
+is averaged to 1 x 1 by gcc_map_mean.  With fewer images than features the covariance is rank deficient; a lower width is the
+original FID code's own remedy.  The real statistics must be of the same width (get_real_stat --dims).
+
 The one deliberate difference from the reference: it runs Inception at batch 1 (its evaluations set opt.batch_size = 1); this
 evaluator batches up to 50 images (get_activations' own default).  An eval-mode network's output for an image does not depend on
 its batch neighbours, so the activations are those of the batch-1 run up to the network's own batched arithmetic."""
@@ -163,7 +168,9 @@ def load_real_stat(path, d, device):
     with np.load(path) as z:
         mu, sigma = np.asarray(z['mu']), np.asarray(z['sigma'])
     if mu.shape != (d,) or sigma.shape != (d, d):
-        raise GccError('%s holds mu %s and sigma %s; the network\'s activations have d = %d' % (path, mu.shape, sigma.shape, d))
+        raise GccError('%s holds mu %s and sigma %s; the network\'s activations have d = %d (python -m '
+                       'gcc_amd.metric.get_real_stat --dims %d --dataroot ... --output_path %s writes statistics of that width)'
+                       % (path, mu.shape, sigma.shape, d, d, path))
     f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
     return f(mu), f(sigma)
 
@@ -320,14 +327,31 @@ def fid_evaluator(inception, logger=None, batch_size=50):
 
 
 PRECISION_ENV = 'GCC_FID_PRECISION'
+DIMS_ENV = 'GCC_FID_DIMS'
 
 
-def _native_inception(path):
+def fid_dims(dims=None):
+    """the feature width to score with: ``dims``, else GCC_FID_DIMS, else 2048; GccError names the four widths otherwise"""
+    from .inception_fid import BLOCK_INDEX_BY_DIM
+    what = 'dims'
+    if dims is None:
+        dims, what = os.environ.get(DIMS_ENV) or 2048, DIMS_ENV
+    try:
+        value = int(str(dims).strip())
+    except ValueError:
+        value = None
+    if value not in BLOCK_INDEX_BY_DIM:
+        raise GccError('%s=%s: expected one of %s' % (what, dims, ', '.join(str(d) for d in sorted(BLOCK_INDEX_BY_DIM))))
+    return value
+
+
+def _native_inception(path, dims=None):
     """(InceptionFidEngine on the host, None) when `path` is the reference's own weight file -- the plain state_dict of
     fid_inception_v3() --, (None, why) when it is one this package does not run, (None, None) for any other file.  The environment
     variable GCC_FID_PRECISION ('bf16', the default, or 'fp32': the reference's own arithmetic on the f32-input matrix
-    instructions) chooses the engine's precision; any other value raises GccError."""
-    from .inception_fid import PRECISIONS, InceptionFidEngine, is_fid_inception_state_dict
+    instructions) chooses the engine's precision; any other value raises GccError.  ``dims`` (else GCC_FID_DIMS, else 2048:
+    fid_dims) chooses the output block whose pooled features the engine returns."""
+    from .inception_fid import BLOCK_INDEX_BY_DIM, PRECISIONS, InceptionFidEngine, is_fid_inception_state_dict
     try:
         sd = torch.load(path, map_location='cpu', weights_only=True)
     except Exception:
@@ -337,16 +361,18 @@ def _native_inception(path):
     precision = os.environ.get(PRECISION_ENV) or 'bf16'
     if precision not in PRECISIONS:
         raise GccError('%s=%s: expected one of %s' % (PRECISION_ENV, precision, ', '.join(PRECISIONS)))
+    block = BLOCK_INDEX_BY_DIM[fid_dims(dims)]
     try:
-        return InceptionFidEngine(sd, precision=precision), None
+        return InceptionFidEngine(sd, precision=precision, output_blocks=(block,), pooled=True), None
     except GccError as e:
         return None, '%s %s holds an Inception state_dict this package does not run: %s' % (ENV, path, e)
 
 
-def load_inception():
+def load_inception(dims=None):
     """(network, None) from the file GCC_FID_INCEPTION names -- a TorchScript archive of InceptionV3([3]), or the reference's own
     pt_inception weight file (a plain state_dict: InceptionFidEngine runs it natively, at the precision GCC_FID_PRECISION names)
-    --, else (None, the condition that failed).  A TorchScript archive runs as it was exported and ignores GCC_FID_PRECISION."""
+    --, else (None, the condition that failed).  A TorchScript archive runs as it was exported and ignores GCC_FID_PRECISION and
+    the width (``dims``, else GCC_FID_DIMS, else 2048: the native network's output block, fid_dims)."""
     path = os.environ.get(ENV)
     if not path:
         return None, '%s is not set (the path of a TorchScript archive of the Inception network)' % ENV
@@ -356,7 +382,7 @@ def load_inception():
         return torch.jit.load(path, map_location='cpu'), None
     except Exception as e:
         first = (str(e).strip().splitlines() or [type(e).__name__])[0]
-        engine, refusal = _native_inception(path)
+        engine, refusal = _native_inception(path, dims)
         if engine is not None or refusal is not None:
             return engine, refusal
         return None, 'torch.jit.load could not read %s %s as a TorchScript archive (%s: %s); a plain state_dict needs the ' \
@@ -364,9 +390,13 @@ def load_inception():
 
 
 def network_label(inception):
-    """' (native, bf16|fp32)' for a native engine, '' for a TorchScript archive: the log lines' word on which network scores"""
+    """' (native, bf16|fp32)' for a native engine -- ' (native, bf16, dims 192)' when it is tapped below 2048 --, '' for a
+    TorchScript archive: the log lines' word on which network scores"""
     precision = getattr(inception, 'precision', None)
-    return ' (native, %s)' % precision if precision else ''
+    if not precision:
+        return ''
+    blocks = getattr(inception, 'output_blocks', (3,))
+    return ' (native, %s%s)' % (precision, '' if blocks[-1] == 3 else ', dims %d' % inception.d)
 
 
 def builtin_inception(opt):

@@ -2,11 +2,12 @@
 distance with a Newton-Schulz matrix square root; and the reference's path-based half (:55-145, 287-322, 332-370): image folders,
 statistics files and feature files scored against each other,
 
-    python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 2048] [-c GPU] [--prdc [--nearest-k 5]]
+    python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 64|192|768|2048] [-c GPU] [--prdc [--nearest-k 5]]
 
 prints ``FID: %.2f`` and, when both sides have activations (folders, or the feature files get_real_stat --features_path writes),
 ``KID: %.6f`` (gcc_amd.metric.kid_score); with --prdc one more line, ``Precision: %.4f | Recall: %.4f | Density: %.4f | Coverage:
-%.4f`` (gcc_amd.metric.prdc_score) of the second path against the first as the real set.  No CPU path: a missing library / GPU
+%.4f`` (gcc_amd.metric.prdc_score) of the second path against the first as the real set.  --dims below 2048 scores with the
+reference's narrower output blocks (the native network stops there; unset, GCC_FID_DIMS or 2048).  No CPU path: a missing library / GPU
 raises GccError."""
 import argparse
 import os
@@ -162,7 +163,9 @@ parser.add_argument('path', type=str, nargs=2,
                     help='two of: a folder of *.jpg / *.png images, a real_stat*.npz statistics file (mu, sigma), '
                          'a real_act*.npz feature file (get_real_stat --features_path)')
 parser.add_argument('--batch-size', type=int, default=50, help='images per pass of the network')
-parser.add_argument('--dims', type=int, default=2048, choices=list(DIMS), help='width of the network\'s features')
+parser.add_argument('--dims', type=int, default=2048, choices=list(DIMS),
+                    help='width of the network\'s features: the output block the native network is tapped at (not given: '
+                         'GCC_FID_DIMS, else the default)')
 parser.add_argument('-c', '--gpu', default='', type=str, help='index of the GPU to use (blank: the current device; there is no CPU path)')
 parser.add_argument('--prdc', action='store_true',
                     help='also print precision, recall, density and coverage (gcc_amd.metric.prdc_score) of the second path '
@@ -290,7 +293,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, use_tqdm=Fa
 
 def _network(model, dims, cuda):
     """a callable that returns the scoring network on the device: ``model``, or the file GCC_FID_INCEPTION names (loaded on the
-    first call, at the precision GCC_FID_PRECISION names)"""
+    first call, at the precision GCC_FID_PRECISION names and tapped at the output block of ``dims`` features)"""
     state = {}
 
     def get():
@@ -299,7 +302,7 @@ def _network(model, dims, cuda):
             from .fid_eval import load_inception
             net = model
             if net is None:
-                net, why = load_inception()
+                net, why = load_inception(dims)
                 if net is None:
                     raise GccError('fid_score: %s' % why)
             state['net'] = _prepare(net, _cuda_device(cuda))
@@ -350,7 +353,7 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqd
 
 
 def main(argv=None, model=None):
-    args = parser.parse_args(argv)
+    args = parser.parse_args(argv, argparse.Namespace(dims=None))       # None: --dims was not given, GCC_FID_DIMS may speak
     if not torch.cuda.is_available():
         raise GccError('gcc_amd runs on MI355X only (no CPU path): need a visible GPU')
     if args.gpu != '':
@@ -359,7 +362,8 @@ def main(argv=None, model=None):
     if args.prdc:
         from .prdc_score import check_k, prdc_text
         prdc_k = check_k(args.nearest_k, '--nearest-k')
-    values = calculate_fid_given_paths(args.path, args.batch_size, True, args.dims, model=model, kid=True, prdc_k=prdc_k)
+    from .fid_eval import fid_dims
+    values = calculate_fid_given_paths(args.path, args.batch_size, True, fid_dims(args.dims), model=model, kid=True, prdc_k=prdc_k)
     fid_value, kid_value = values[:2]
     print('FID: %.2f' % fid_value)
     if kid_value is not None:

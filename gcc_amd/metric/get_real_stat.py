@@ -18,6 +18,10 @@ batch 32 (the reference's value) into the streamed statistics.  The file is the 
 np.savez(act=<fp32 [n, d]>, network=<which network made them>): named real_act*.npz beside its real_stat*.npz, it lets every FID
 evaluation report the Kernel Inception Distance as well (gcc_amd.metric.kid_score).
 
+``--dims 64|192|768|2048`` (this tool's own flag too; unset: GCC_FID_DIMS, else 2048) writes the statistics -- and the activations
+-- of the reference's narrower output blocks: what a FID evaluation under the same GCC_FID_DIMS, or fid_score --dims, compares
+against.
+
 One difference: the reference sets max_dataset_size = -1, which makes its file listing drop whichever file os.walk listed
 last; this tool reads every file of the split."""
 import argparse
@@ -51,6 +55,12 @@ tool_parser.add_argument('--features_path', type=str, default=None,
                          help='also save the activations the statistics were built from (np.savez(act=, network=)): a '
                               'real_act*.npz beside its real_stat*.npz lets every FID evaluation report KID as well')
 
+# ... and the width, on a parser of its own around the two: the flags of `parser` and `tool_parser` stay what they were
+dims_parser = argparse.ArgumentParser(parents=[tool_parser], add_help=False, description=parser.description)
+dims_parser.add_argument('--dims', type=int, default=None, choices=[64, 192, 768, 2048],
+                         help='width of the features: the output block the native network is tapped at (unset: GCC_FID_DIMS, '
+                              'else 2048); a TorchScript archive runs as exported')
+
 # dataset mode -> (image, its path) of a batch, per direction
 _PICK = {'aligned': lambda AtoB: ('B', 'B_paths') if AtoB else ('A', 'A_paths'),
          'unaligned': lambda AtoB: ('B', 'B_paths') if AtoB else ('A', 'A_paths'),
@@ -58,12 +68,14 @@ _PICK = {'aligned': lambda AtoB: ('B', 'B_paths') if AtoB else ('A', 'A_paths'),
 
 
 def parse(argv=None):
-    opt = tool_parser.parse_args(argv)
+    opt = dims_parser.parse_args(argv)
     if opt.dataset_mode not in _PICK:
         raise GccError('get_real_stat: --dataset_mode %s (aligned, sa and unaligned have real images to score)' % opt.dataset_mode)
     opt.num_threads, opt.batch_size, opt.serial_batches, opt.no_flip = 0, 1, True, True
     opt.max_dataset_size = float('inf')
     opt.gpu_ids = [i for i in (int(s) for s in str(opt.gpu_ids).split(',')) if i >= 0]
+    from .fid_eval import fid_dims
+    opt.dims = fid_dims(opt.dims)
     return opt
 
 
@@ -94,7 +106,7 @@ def main(argv=None, inception=None):
     device = torch.device('cuda', opt.gpu_ids[0])
     if inception is None:
         from .fid_eval import load_inception
-        inception, why = load_inception()
+        inception, why = load_inception(opt.dims)
         if inception is None:
             raise GccError('get_real_stat: %s' % why)
     mu, sigma, *act = real_statistics(opt, inception, device, features=opt.features_path is not None)

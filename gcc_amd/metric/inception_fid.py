@@ -20,6 +20,11 @@ no 'border' step:
 
 There is no split-K on that route: an image's features do not depend on the batch it is in, bit for bit.
 
+output_blocks=(...) asks for the reference's other output blocks (metric/inception.py:24-29 BLOCK_INDEX_BY_DIM, :143-163): 0 after
+the stem's first max pool, 1 after its second, 2 Mixed_6e's output, 3 the final mean.  The program stops after the last block
+asked for; a block below 3 is a 'tap' step where its map is produced: the NCHW fp32 copy InceptionV3(output_blocks).forward
+returns, or with pooled=True its spatial mean [N, C, 1, 1] through gcc_map_mean (what fid_score does with such a map), no copy made.
+
 Every width is read from the shapes: the only constraints are that concatenations match and that widths are multiples of 8, so a
 thin seeded network runs through the same code as the real one.  Construction parses the state_dict on the host (no device, no
 library); .to(device) packs the weights and folds the BatchNorms once -- the weights of an evaluator never change."""
@@ -36,6 +41,8 @@ UNUSED_KEYS = ('fc.weight', 'fc.bias')
 MAX_S2, MAX_S1P1, AVG_S1P1 = 0, 1, 2                 # _lib.POOL3_*
 WHAT = 'FID Inception state_dict'
 PRECISIONS = ('bf16', 'fp32')
+BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}      # metric/inception.py:24-29: feature width -> output block
+BLOCKS = (0, 1, 2, 3)
 
 
 def _c(name, k=1, stride=1, pad=0):
@@ -90,14 +97,17 @@ def _block_e(p, pool):
 
 
 def _network():
-    """the module tree: a list of ('conv', _c) / ('pool', mode) / ('block', name, branches)"""
+    """the module tree: a list of ('conv', _c) / ('pool', mode) / ('block', name, branches) / ('tap', output block): the place
+    where the reference's output block 0, 1 or 2 ends (block 3 is the mean behind the last item)"""
     net = [('conv', _c('Conv2d_1a_3x3', 3, 2)), ('conv', _c('Conv2d_2a_3x3', 3)), ('conv', _c('Conv2d_2b_3x3', 3, pad=1)),
-           ('pool', MAX_S2), ('conv', _c('Conv2d_3b_1x1')), ('conv', _c('Conv2d_4a_3x3', 3)), ('pool', MAX_S2)]
+           ('pool', MAX_S2), ('tap', 0), ('conv', _c('Conv2d_3b_1x1')), ('conv', _c('Conv2d_4a_3x3', 3)), ('pool', MAX_S2),
+           ('tap', 1)]
     for n in ('Mixed_5b', 'Mixed_5c', 'Mixed_5d'):
         net.append(('block', n, _block_a(n + '.')))
     net.append(('block', 'Mixed_6a', _block_b('Mixed_6a.')))
     for n in ('Mixed_6b', 'Mixed_6c', 'Mixed_6d', 'Mixed_6e'):
         net.append(('block', n, _block_c(n + '.')))
+    net.append(('tap', 2))
     net.append(('block', 'Mixed_7a', _block_d('Mixed_7a.')))
     net.append(('block', 'Mixed_7b', _block_e('Mixed_7b.', AVG_S1P1)))
     net.append(('block', 'Mixed_7c', _block_e('Mixed_7c.', MAX_S1P1)))          # the FID network's max pool
@@ -124,7 +134,7 @@ def is_fid_inception_state_dict(sd):
 def parse_fid_inception(sd):
     """the architecture of a fid_inception_v3 state_dict (values: tensors, or bare shapes) from its keys and shapes:
     SimpleNamespace(net (the module tree with every conv's ci / co filled in), convs (in launch order), widths {block: output
-    channels}, d (the feature width)).  Raises GccError naming the first key that does not belong or does not fit."""
+    channels}, d (the feature width), block_widths {output block 0..3: its channels}).  Raises GccError naming the first key that does not belong or does not fit."""
     if not isinstance(sd, dict):
         raise GccError('%s: expected a dict, got %s' % (WHAT, type(sd).__name__))
     net = _network()
@@ -143,7 +153,7 @@ def parse_fid_inception(sd):
             raise GccError('%s: %s takes %d channels, the layer before it gives %d' % (WHAT, c.key, c.ci, cin))
         return c.co
 
-    cin, widths = 3, {}
+    cin, widths, block_widths = 3, {}, {}
     for item in net:
         if item[0] == 'conv':
             cin = read(item[1], cin)
@@ -155,7 +165,23 @@ def parse_fid_inception(sd):
                     cur = read(c, cur)
                 total += sum(read(c, cur) for c in b.tails) if b.tails else cur
             widths[item[1]] = cin = total                 # every slice offset is a sum of multiples of 8 (cin of a pool: checked above)
-    return SimpleNamespace(net=net, convs=convs, widths=widths, d=cin)
+        elif item[0] == 'tap':
+            block_widths[item[1]] = cin
+    block_widths[3] = cin
+    return SimpleNamespace(net=net, convs=convs, widths=widths, d=cin, block_widths=block_widths)
+
+
+def check_output_blocks(output_blocks):
+    """the blocks asked for, deduplicated and ascending (metric/inception.py:84); GccError names the choices otherwise"""
+    try:
+        blocks = sorted(set(output_blocks))
+    except TypeError:
+        blocks = []
+    if not blocks or any(isinstance(b, bool) or not isinstance(b, int) or b not in BLOCKS for b in blocks):
+        raise GccError('InceptionFidEngine: output_blocks %r; expected one or more of %s (the blocks of %s features)'
+                       % (output_blocks, ', '.join(str(b) for b in BLOCKS),
+                          ' / '.join(str(d) for d in sorted(BLOCK_INDEX_BY_DIM))))
+    return tuple(blocks)
 
 
 def _out(size, k, stride, pad):
@@ -164,20 +190,25 @@ def _out(size, k, stride, pad):
 
 class InceptionFidEngine(SlabProgramEngine):
     """inception(x)[0] for fid_eval.ImageStatistics: x NCHW fp32 [N, 3, H, W] in [0, 1] on the device, any H, W -> [features],
-    features fp32 [N, d, 1, 1] (d = 2048 for the real network), InceptionV3([3]).forward's list.  Activations are NHWC bf16 with
+    features fp32 [N, d, 1, 1] (d = 2048 for the real network), InceptionV3([3]).forward's list.  With output_blocks: one fp32
+    tensor per block asked for, ascending, InceptionV3(output_blocks).forward's list -- a block below 3 as its contiguous NCHW map
+    [N, C, h, w], or with pooled=True as that map's spatial mean [N, C, 1, 1] in f64 (gcc_map_mean: the bf16 route's maps hold
+    bf16 values, the mean adds one fp32 rounding); .d is the width of the last block asked for.  Activations are NHWC bf16 with
     one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic.
     precision='fp32': activations, weights and every sum are fp32 (the reference's own arithmetic), one launch per convolution.  The
     engine's scaffold -- .to(), the slab and its programs, the route check -- is metric/_native.py's."""
     BN_EPS = BN_EPS
 
-    def __init__(self, state_dict, resize=299, precision='bf16'):
+    def __init__(self, state_dict, resize=299, precision='bf16', output_blocks=(3,), pooled=False):
         if precision not in PRECISIONS:
             raise GccError('InceptionFidEngine: precision %r; expected one of %s' % (precision, ', '.join(PRECISIONS)))
         self.precision = precision
         if precision == 'fp32':
             self._slab_dtype = torch.float32
+        self.output_blocks, self.pooled = check_output_blocks(output_blocks), bool(pooled)
         self.arch = parse_fid_inception(state_dict)
-        self.d = self.arch.d
+        self.block_widths = dict(self.arch.block_widths)
+        self.d = self.block_widths[self.output_blocks[-1]]
         self.resize = int(resize)
         if self.resize <= 0:
             raise GccError('InceptionFidEngine: resize must be positive, got %r' % (resize,))
@@ -193,7 +224,9 @@ class InceptionFidEngine(SlabProgramEngine):
         fp32), four regions -- a block's input and output, which swap from layer to layer, and two temporaries the branches
         alternate between.  The input's own H and W appear in no launch but gcc_fid_resize, so a program depends on N alone.
         bf16: ('conv', conv, source, destination), ('pool', mode, source, destination), ('border', source, destination, ph, pw)
-        in front of a rectangular kernel.  fp32: no 'border' -- a 'conv' step's (ph, pw) are its conv's own .pad."""
+        in front of a rectangular kernel.  fp32: no 'border' -- a 'conv' step's (ph, pw) are its conv's own .pad.
+        ('tap', block, source): an output block below 3 that was asked for, read where it stands before its region is written
+        again; the program ends behind the last block asked for, so it is a prefix of the whole network's."""
         steps, sizes, where = [], [], ['the input']
         R = self.resize
         f32 = self.precision == 'fp32'
@@ -237,6 +270,12 @@ class InceptionFidEngine(SlabProgramEngine):
 
         x = Act(3, R, R, -1, ld=grid)
         for item in self.arch.net:
+            if item[0] == 'tap':
+                if item[1] in self.output_blocks:
+                    steps.append(('tap', item[1], x))
+                if item[1] == self.output_blocks[-1]:
+                    break
+                continue
             if item[0] == 'conv':
                 c = item[1]
                 where[0] = c.key
@@ -299,9 +338,16 @@ class InceptionFidEngine(SlabProgramEngine):
     def _run(self, x, N, count_only=False):
         self._check_device()
         prog = self._bind(N)
-        if count_only:
-            return 2 + sum(self._conv(st, route_only=True) if st[0] == 'conv' else 1 for st in prog.steps)
         f32 = self.precision == 'fp32'
+        if count_only:
+            def launches(st):
+                if st[0] == 'conv':
+                    return self._conv(st, route_only=True)
+                if st[0] == 'tap' and self.pooled:
+                    return ops.map_mean_launches(st[2].h, st[2].w, st[2].C)
+                return 1
+            return 1 + sum(launches(st) for st in prog.steps) + (3 in self.output_blocks)
+        outs = []
         (ops.fid_resize_f32 if f32 else ops.fid_resize)(x, prog.x_in)
         pool3x3 = ops.pool3x3_f32 if f32 else ops.pool3x3
         for st in prog.steps:
@@ -313,11 +359,24 @@ class InceptionFidEngine(SlabProgramEngine):
                     raise self._conv_error(st, e)
             elif kind == 'pool':
                 pool3x3(st[1], st[2].view, st[3].view)
+            elif kind == 'tap':
+                outs.append(self._tap(st[2].view, N))
             else:
                 ops.border_copy(st[1].view, st[2].view, st[3], st[4])
-        out = torch.empty((N, self.d, 1, 1), dtype=torch.float32, device=self.device)
-        (ops.global_avgpool_f32 if f32 else ops.global_avgpool)(prog.last.view, out)
-        return [out]
+        if 3 in self.output_blocks:
+            out = torch.empty((N, self.block_widths[3], 1, 1), dtype=torch.float32, device=self.device)
+            (ops.global_avgpool_f32 if f32 else ops.global_avgpool)(prog.last.view, out)
+            outs.append(out)
+        return outs
+
+    def _tap(self, view, N):
+        """an output block below 3 from its slab view: the NCHW fp32 map, or pooled its mean over the pixels"""
+        f32 = self.precision == 'fp32'
+        if not self.pooled:
+            return (ops.nhwc_to_nchw_f32 if f32 else ops.nhwc_to_nchw)(view)
+        out = torch.empty((N, view.shape[1], 1, 1), dtype=torch.float32, device=self.device)
+        (ops.map_mean_f32 if f32 else ops.map_mean)(view, out)
+        return out
 
     def __call__(self, x):
         self._check_input(x, refuse_empty=True)

@@ -1327,6 +1327,40 @@ def global_avgpool_f32(x, out=None):
     return out
 
 
+def map_mean_segments(h, w, Cc):
+    """gcc_map_mean_segments: the pixel ranges the library cuts an h x w map of Cc channels into when `segments` is 0"""
+    return lib().gcc_map_mean_segments(h, w, Cc)
+
+
+def map_mean_launches(h, w, Cc, segments=0):
+    """kernel launches of one map_mean call: one range needs no second pass"""
+    return 1 if (segments or map_mean_segments(h, w, Cc)) == 1 else 2
+
+
+def _map_mean(name, g, x, out, segments, slot):
+    xp, N, Cc, h, w, ld = g(x)
+    if out is None:
+        out = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or out.numel() != N * Cc or not out.is_contiguous() or out.device != x.device:
+        raise _lib.GccError('%s: out must be a contiguous fp32 tensor of %d x %d elements on %s' % (name, N, Cc, x.device))
+    ws = workspace(lib().gcc_map_mean_workspace(N, h, w, Cc), x.device, slot)
+    check(getattr(lib(), 'gcc_' + name)(xp, ld, 0, N, h, w, Cc, int(segments), out.data_ptr(), ws.data_ptr(), ws.numel(), stream()),
+          'gcc_' + name)
+    return out
+
+
+def map_mean(x, out=None, segments=0, slot='map_mean'):
+    """gcc_map_mean: fp32 [N, C] mean over the pixels of an NHWC bf16 view, summed in f64 with the pixels of an image split over
+    workgroups (a large map: the network's earlier output blocks).  ``segments``: 0 for the library's split, a positive value
+    forces it."""
+    return _map_mean('map_mean', geom, x, out, segments, slot)
+
+
+def map_mean_f32(x, out=None, segments=0, slot='map_mean'):
+    """gcc_map_mean_f32: map_mean of an NHWC fp32 view"""
+    return _map_mean('map_mean_f32', geom_f32, x, out, segments, slot)
+
+
 def _kid_rows(t, what):
     """(pointer, is_f64, ld, rows, d) of a [rows, d] fp32 / f64 device matrix whose rows may be strided (read in place)"""
     if not torch.is_tensor(t) or t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or not t.is_cuda or \

@@ -1187,6 +1187,45 @@ int gcc_pool3x3_f32(int mode, const float* x, int ldx, int xoff, float* y, int l
 int gcc_global_avgpool_f32(const float* x, int ld, int off, int N, int h, int w, int C, float* out, gcc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The spatial mean of a LARGE map: the network's earlier output blocks (metric/inception.py BLOCK_INDEX_BY_DIM: 64 channels at
+ * 73 x 73, 192 at 35 x 35, 768 at 17 x 17 for a 299 x 299 input), averaged to 1 x 1 as metric/fid_score.py:136-137 does
+ * (gcc_amd/csrc/inception.hip, InceptionFidEngine(output_blocks=, pooled=True)).  Added without a GCC_HIP_ABI bump (additions
+ * only); gcc_global_avgpool(_f32) keep their behaviour and their bits.
+ * Operand.  x is an NHWC channel window as in gcc_global_avgpool: bf16 in 16-byte chunks of 8 channels (gcc_map_mean) or fp32 in
+ *   chunks of 4 (gcc_map_mean_f32), C a multiple of the chunk, ld and off on the chunk grid with ld >= off + C, x 16-byte
+ *   aligned.  Nothing between off + C and ld, or after the last pixel, is read.  out: fp32 [N][C], 16-byte aligned.
+ * Result.  out[n * C + c] = (float)(S / (double)(h w)), S the sum of the h w values x[n][.][off + c], each converted to f64
+ *   (exactly) and accumulated in f64: one division in f64, then one rounding to fp32.  Whatever the order, |S_computed - S| <=
+ *   gamma_{h w} sum |x| (gamma_n = n u / (1 - n u), u = 2^-53); a map of integers below 2^53 / (h w) in magnitude is summed
+ *   exactly, so every `segments` gives it the same bits.
+ * Order.  The pixels of an image are cut into `segments` ranges (range s is [s P / segments, (s + 1) P / segments), P = h w);
+ *   a workgroup owns one range of one image for a block of CW chunks (CW: the largest power of two that divides C / chunk, at most
+ *   256 / chunk channels), its 256 threads as R = 256 / CW pixel rows: row r adds pixels lo + r, lo + r + R, ... in ascending
+ *   order, eight 16-byte loads in flight; the rows are added through LDS in ascending r, the ranges in ascending s.  The order
+ *   is a function of h w, C and `segments` alone -- not of N, of the image's place in the batch, of ld or off -- so an image's
+ *   mean does not depend on its batch neighbours, bit for bit.
+ * segments == 0: the library's split gcc_map_mean_segments(h, w, C) = clamp(P / ((256 / CW4) GCC_MAP_MEAN_PIXELS_PER_THREAD), 1,
+ *   max) with CW4 the CW of C / 4 chunks for either element type: a function of h w and C alone.  1 <= segments <= max = min(h w,
+ *   GCC_MAP_MEAN_MAX_SEGMENTS) forces it (for tests).  gcc_map_mean_segments is 0 for a size < 1 or a C that is no multiple of 4.
+ * Execution.  segments in use == 1: one launch, nothing is written to ws (ws may be NULL).  Otherwise the per-range sums go to ws
+ *   as f64 [N][segments][C] and a second launch adds them: two launches.  No floating-point atomics, no workgroup waits for
+ *   another, nothing is zero-filled: the same input gives the same bits.
+ * gcc_map_mean_workspace(N, h, w, C): bytes that serve every legal `segments` (N max C doubles); 0 for a size < 1.
+ * Refusals, all before anything is launched: GCC_ERR_BAD_ARG for a null x or out (or ws with more than one range in use), a size
+ *   < 1, an ld / off off the chunk grid, ld < off + C, a pointer off its alignment (ws: 8 bytes), segments < 0 or above max;
+ *   GCC_ERR_UNSUPPORTED for a C that is no multiple of the chunk, h w >= 2^24, N h w ld >= 2^40 (gcc_global_avgpool's limits) or
+ *   2^31 workgroups; GCC_ERR_WORKSPACE for ws_bytes short of N segments C doubles with more than one range in use.
+ * --------------------------------------------------------------------------------------------- */
+#define GCC_MAP_MEAN_MAX_SEGMENTS 64
+#define GCC_MAP_MEAN_PIXELS_PER_THREAD 64
+int gcc_map_mean_segments(int h, int w, int C);
+size_t gcc_map_mean_workspace(int N, int h, int w, int C);
+int gcc_map_mean(const void* x, int ld, int off, int N, int h, int w, int C, int segments, float* out, void* ws, size_t ws_bytes,
+                 gcc_stream_t stream);
+int gcc_map_mean_f32(const float* x, int ld, int off, int N, int h, int w, int C, int segments, float* out, void* ws,
+                     size_t ws_bytes, gcc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * FID around the Inception network (metric/test_metric.py:15-45, 129-204, metric/get_real_stat.py; the network itself is the
  * caller's).  Added without a GCC_HIP_ABI bump (additions only).
  * gcc_fid_input: the network's input, NCHW fp32 out[N][3][H][W] in [0, 1] = float(byte) / 255.f (equal to the reference's
