@@ -122,6 +122,7 @@ KID_TILE, KID_KSTEP = 128, 16                                # include/gcc_hip.h
 # include/gcc_hip.h GCC_PRDC_* (gcc_prdc_kth_dist, gcc_prdc_ball_count)
 PRDC_TILE, PRDC_COL_TILE, PRDC_SMALL_TILE, PRDC_SMALL_BELOW, PRDC_KSTEP = 128, 128, 64, 256, 16
 PRDC_MAX_K, PRDC_MAX_CHUNKS, PRDC_FILL_WORKGROUPS = 8, 16, 512
+IS_TILE, IS_KSTEP, IS_CHUNK = 64, 16, 4096                   # include/gcc_hip.h GCC_IS_* (gcc_is_logits, gcc_is_split_scores)
 MAP_MEAN_MAX_SEGMENTS, MAP_MEAN_PIXELS_PER_THREAD = 64, 64   # include/gcc_hip.h GCC_MAP_MEAN_* (gcc_map_mean)
 
 
@@ -345,6 +346,9 @@ PROTOTYPES = {
     'gcc_prdc_chunks': (_I, [_I, _I]),
     'gcc_prdc_kth_dist': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
     'gcc_prdc_ball_count': (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _Z, _P]),
+    'gcc_is_workspace': (_Z, [_I, _I, _I]),
+    'gcc_is_logits': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    'gcc_is_split_scores': (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     'gcc_attention_fwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_bwd': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     'gcc_attention_infer': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P]),

@@ -21,6 +21,12 @@ per run.  Checkpoints are still chosen by FID alone.  Without the files nothing 
 Recall: %.4f | Density: %.4f | Coverage: %.4f`` of the same activations (prdc_score.prdc with k nearest neighbours), the real
 set's radii computed once per run.  It needs the feature files: with the variable set and one missing, the scorer raises.
 
+``GCC_FID_IS=<splits>`` (an integer >= 1, usually 10; unset or empty: off) adds a last line, ``IS: %.4f +- %.4f``: the Inception
+Score of the generated images (inception_score.inception_score: mean and standard deviation over that many splits) from the same
+pool features and the classifier of the native network's weight file.  It needs no real set, so the activations are kept for it
+also where no feature file exists.  A network without the classifier -- a TorchScript archive, a weight file without fc.*, a
+width below 2048 -- is refused when the scorer is made, before any image is generated.
+
 ``GCC_FID_DIMS=<64 | 192 | 768 | 2048>`` (unset or empty: 2048) scores with the reference's narrower output blocks
 (metric/inception.py BLOCK_INDEX_BY_DIM, the --dims of metric/fid_score.py): the native network stops after that block and its map
 is averaged to 1 x 1 by gcc_map_mean.  With fewer images than features the covariance is rank deficient; a lower width is the
@@ -179,9 +185,11 @@ class FidScorer:
     """one evaluation: generated images in (per slot), one FID per slot out -- and one KID per slot (``kid()``) when a feature
     file real_act*.npz (get_real_stat --features_path) lies beside every slot's real_stat*.npz; with one missing, no activation
     is kept and nothing is launched for it.  ``kid_cache``: a dict that outlives the scorer (the evaluator's): the real sets'
-    activations and self terms are loaded and computed once per run."""
+    activations and self terms are loaded and computed once per run.  ``is_splits`` (GCC_FID_IS): the activations are kept
+    whether or not the feature files exist, and ``inception_score()`` gives one (mean, std) per slot; the network must carry
+    its classifier (inception_score.classifier_of says what is missing otherwise)."""
 
-    def __init__(self, inception, dataroot, slots, batch_size=50, kid_cache=None, prdc_k=None):
+    def __init__(self, inception, dataroot, slots, batch_size=50, kid_cache=None, prdc_k=None, is_splits=None):
         from .kid_score import features_name
         from .prdc_score import ENV as PRDC_ENV, check_k
         self.files = [os.path.join(str(dataroot), name) for name, _ in slots]
@@ -195,9 +203,15 @@ class FidScorer:
                            '--dataroot ... --output_path %s --features_path %s writes it)'
                            % (PRDC_ENV, self.prdc_k, ', '.join(str(f or s) for f, s in missing), missing[0][1],
                               missing[0][0] or 'real_act*.npz'))
+        self.is_splits, self.classifier = None, None
+        if is_splits is not None:
+            from . import inception_score as IS
+            self.is_splits = IS.check_splits(is_splits, IS.ENV)
+            self.classifier = IS.classifier_of(inception, '%s=%d' % (IS.ENV, self.is_splits))
         self.kid_cache = kid_cache if kid_cache is not None else {}
         self.label = network_label(inception)
-        self.stats = [ImageStatistics(inception, batch_size, keep_features=self.with_kid) for _ in slots]
+        keep = self.with_kid or self.is_splits is not None
+        self.stats = [ImageStatistics(inception, batch_size, keep_features=keep) for _ in slots]
 
     def add(self, key, fake, slot=0):
         self.stats[slot].add(key, fake)
@@ -259,6 +273,21 @@ class FidScorer:
         return values
 
 
+    def inception_score(self):
+        """one Inception Score (mean, std) per slot over the scorer's splits, or None when it was made without them"""
+        if self.is_splits is None:
+            return None
+        from . import inception_score as IS
+        values = []
+        for st in self.stats:
+            if st.count < self.is_splits:
+                raise GccError('the Inception Score over %d splits needs at least %d images, %d were scored'
+                               % (self.is_splits, self.is_splits, st.count))
+            st.flush()
+            values.append(IS.inception_score(st.features.rows(), *self.classifier, splits=self.is_splits))
+        return values
+
+
 def fid_line(values, tags, model):
     if 'cyclegan' in model:
         return ' | '.join('%s FID: %.2f' % (t, v) for v, t in zip(values, tags))
@@ -278,6 +307,13 @@ def prdc_line(values, tags, model):
     return prdc_text(values[0])
 
 
+def is_line(values, tags, model):
+    from .inception_score import is_text
+    if 'cyclegan' in model:
+        return ' | '.join('%s %s' % (t, is_text(v)) for v, t in zip(values, tags))
+    return is_text(values[0])
+
+
 def fid_evaluator(inception, logger=None, batch_size=50):
     """evaluate(model, opt) for gcc_amd.train.run_evaluation: test_pix2pix_fid / test_cyclegan_fid / test_sagan_fid.
     ``evaluate.scorer(model, opt)`` gives python -m gcc_amd.test the scorer of the images it writes.  Inception runs on batches
@@ -287,8 +323,10 @@ def fid_evaluator(inception, logger=None, batch_size=50):
     def scorer(model, opt):
         if state['inception'] is None:
             state['inception'] = _prepare(inception, model.device)
+        from .inception_score import env_splits
         from .prdc_score import env_k
-        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size, kid_cache=state['kid'], prdc_k=env_k())
+        return FidScorer(state['inception'], opt.dataroot, real_stat_slots(opt), batch_size, kid_cache=state['kid'], prdc_k=env_k(),
+                         is_splits=env_splits())
 
     def evaluate(model, opt):
         from ..data import create_dataset
@@ -319,6 +357,9 @@ def fid_evaluator(inception, logger=None, batch_size=50):
         prdc = sc.prdc()                           # None unless GCC_FID_PRDC names a k
         if prdc is not None and logger is not None:
             logger.info(prdc_line(prdc, sc.tags, opt.model))
+        score = sc.inception_score()               # None unless GCC_FID_IS names the splits
+        if score is not None and logger is not None:
+            logger.info(is_line(score, sc.tags, opt.model))
         return list(zip(values, sc.tags))
 
     evaluate.state = state

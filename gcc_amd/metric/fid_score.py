@@ -3,10 +3,13 @@ distance with a Newton-Schulz matrix square root; and the reference's path-based
 statistics files and feature files scored against each other,
 
     python -m gcc_amd.metric.fid_score PATH PATH [--batch-size N] [--dims 64|192|768|2048] [-c GPU] [--prdc [--nearest-k 5]]
+                                                 [--inception-score [--splits 10]]
 
 prints ``FID: %.2f`` and, when both sides have activations (folders, or the feature files get_real_stat --features_path writes),
 ``KID: %.6f`` (gcc_amd.metric.kid_score); with --prdc one more line, ``Precision: %.4f | Recall: %.4f | Density: %.4f | Coverage:
-%.4f`` (gcc_amd.metric.prdc_score) of the second path against the first as the real set.  --dims below 2048 scores with the
+%.4f`` (gcc_amd.metric.prdc_score) of the second path against the first as the real set; with --inception-score a last line,
+``IS: %.4f +- %.4f`` (gcc_amd.metric.inception_score): the Inception Score of the second path, the generated set, from the native
+network's 2048 features and the classifier of its weight file.  --dims below 2048 scores with the
 reference's narrower output blocks (the native network stops there; unset, GCC_FID_DIMS or 2048).  No CPU path: a missing library / GPU
 raises GccError."""
 import argparse
@@ -171,6 +174,10 @@ parser.add_argument('--prdc', action='store_true',
                     help='also print precision, recall, density and coverage (gcc_amd.metric.prdc_score) of the second path '
                          'against the first as the real set; both sides need activations: folders or real_act*.npz')
 parser.add_argument('--nearest-k', type=int, default=5, help='the k of the nearest-neighbour balls of --prdc')
+parser.add_argument('--inception-score', action='store_true',
+                    help='also print the Inception Score (gcc_amd.metric.inception_score) of the second path, the generated set: '
+                         'it needs activations (a folder or a real_act*.npz), --dims 2048 and the native network with its classifier')
+parser.add_argument('--splits', type=int, default=10, help='the number of splits of --inception-score')
 
 
 def list_image_files(path):
@@ -324,15 +331,43 @@ def calculate_fid_given_ims(ims_fake, ims_real, batch_size, cuda, dims, model=No
     return calculate_frechet_distance(*stats[0], *stats[1])
 
 
-def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqdm=False, kid=False, prdc_k=None):
+def _classifier_for(paths, dims, net, splits):
+    """the (weight, bias) --inception-score scores the second path with, after the three things it needs: 2048 features, a second
+    path that has activations, a native network with its classifier; each failing case is a GccError that says which it is"""
+    from . import inception_score, kid_score
+    if dims != inception_score.DIMS:
+        raise GccError('fid_score --inception-score: --dims %d; the classifier reads the %d pool features: score with --dims %d '
+                       '(or without --dims and GCC_FID_DIMS)' % (dims, inception_score.DIMS, inception_score.DIMS))
+    second = str(paths[1])
+    if second.endswith('.npz') and not kid_score.is_features_file(second):
+        raise GccError('fid_score --inception-score: %s holds statistics (mu, sigma) only; the Inception Score needs the '
+                       'activations: a folder of images or a real_act*.npz (get_real_stat --features_path)' % second)
+    inception_score.check_splits(splits, '--splits')
+    return inception_score.classifier_of(net(), 'fid_score --inception-score')
+
+
+def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqdm=False, kid=False, prdc_k=None, is_splits=None):
     """metric/fid_score.py:350-370: the FID of two paths, each a folder of images, a real_stat*.npz or a real_act*.npz feature
     file.  ``kid``: return (FID, KID) instead, KID None unless both sides have activations (folders or feature files).
     ``prdc_k``: return (FID, KID, prdc_score.prdc(first, second, k)) -- the first path is the real set, as the FID's arguments
-    are ordered; a side without activations is a GccError that names it."""
+    are ordered; a side without activations is a GccError that names it.  ``is_splits``: one more element at the end of the
+    tuple (behind the FID alone: a pair), the (mean, std) of inception_score.inception_score of the second path's activations
+    over that many splits."""
     for p in paths:
         if not os.path.exists(str(p)):
             raise RuntimeError('Invalid path: %s' % p)
     net = _network(model, dims, cuda)
+    classifier = _classifier_for(paths, dims, net, is_splits) if is_splits is not None else None
+    values = _fid_kid_prdc(paths, batch_size, cuda, dims, net, kid, prdc_k)
+    if classifier is None:
+        return values[0]
+    from .inception_score import inception_score
+    score = inception_score(values[1], *classifier, splits=is_splits)
+    return (values[0] if isinstance(values[0], tuple) else (values[0],)) + (score,)
+
+
+def _fid_kid_prdc(paths, batch_size, cuda, dims, net, kid, prdc_k):
+    """(what calculate_fid_given_paths returns without is_splits, the second path's activations or None)"""
     (m1, s1, a1), (m2, s2, a2) = (_path_statistics(p, net, batch_size, dims, cuda) for p in paths[:2])
     if tuple(m1.shape) != (dims,) or tuple(m2.shape) != (dims,):
         raise GccError('the statistics have mu %s and %s, dims = %d was asked for' % (tuple(m1.shape), tuple(m2.shape), dims))
@@ -343,13 +378,13 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, model=None, use_tqd
                                'need the activations: a folder of images or a real_act*.npz (get_real_stat --features_path)' % p)
     fid_value = calculate_frechet_distance(m1, s1, m2, s2)
     if not kid and prdc_k is None:
-        return fid_value
+        return fid_value, a2
     from .kid_score import polynomial_mmd2
     kid_value = polynomial_mmd2(a1, a2) if a1 is not None and a2 is not None else None
     if prdc_k is None:
-        return fid_value, kid_value
+        return (fid_value, kid_value), a2
     from .prdc_score import prdc
-    return fid_value, kid_value, prdc(a1, a2, prdc_k)
+    return (fid_value, kid_value, prdc(a1, a2, prdc_k)), a2
 
 
 def main(argv=None, model=None):
@@ -362,14 +397,21 @@ def main(argv=None, model=None):
     if args.prdc:
         from .prdc_score import check_k, prdc_text
         prdc_k = check_k(args.nearest_k, '--nearest-k')
+    is_splits = None
+    if args.inception_score:
+        from .inception_score import check_splits, is_text
+        is_splits = check_splits(args.splits, '--splits')
     from .fid_eval import fid_dims
-    values = calculate_fid_given_paths(args.path, args.batch_size, True, fid_dims(args.dims), model=model, kid=True, prdc_k=prdc_k)
+    values = calculate_fid_given_paths(args.path, args.batch_size, True, fid_dims(args.dims), model=model, kid=True, prdc_k=prdc_k,
+                                       is_splits=is_splits)
     fid_value, kid_value = values[:2]
     print('FID: %.2f' % fid_value)
     if kid_value is not None:
         print('KID: %.6f' % kid_value)
     if prdc_k is not None:
         print(prdc_text(values[2]))
+    if is_splits is not None:
+        print(is_text(values[-1]))
     return values
 
 

@@ -171,6 +171,32 @@ def parse_fid_inception(sd):
     return SimpleNamespace(net=net, convs=convs, widths=widths, d=cin, block_widths=block_widths)
 
 
+CLASSIFIER_KEYS = UNUSED_KEYS                        # unused by the features; the Inception Score reads them (inception_score.py)
+
+
+def parse_classifier(sd, arch=None):
+    """the network's classifier head (Inception3.fc: the logits the Inception Score is computed from): (sd['fc.weight'],
+    sd['fc.bias']) when the state_dict (values: tensors, or bare shapes) carries both, None when it carries neither.  Their shapes
+    must be [C, d] and [C] with C >= 2 and d the feature width of output block 3 (``arch``: parse_fid_inception(sd), made here if
+    not given); GccError names the key that is missing or does not fit."""
+    from ._native import _shape
+    wk, bk = CLASSIFIER_KEYS
+    if not isinstance(sd, dict):
+        raise GccError('%s: expected a dict, got %s' % (WHAT, type(sd).__name__))
+    if wk not in sd and bk not in sd:
+        return None
+    for key in (wk, bk):
+        if key not in sd:
+            raise GccError('%s: %s is missing (the classifier has a weight and a bias)' % (WHAT, key))
+    d = (arch or parse_fid_inception(sd)).block_widths[3]
+    ws, bs = _shape(sd[wk]), _shape(sd[bk])
+    if len(ws) != 2 or ws[1] != d or ws[0] < 2:
+        raise GccError('%s: %s has shape %s, expected (C >= 2, %d): the classifier reads the %d pool features' % (WHAT, wk, ws, d, d))
+    if bs != (ws[0],):
+        raise GccError('%s: %s has shape %s, expected (%d,)' % (WHAT, bk, bs, ws[0]))
+    return sd[wk], sd[bk]
+
+
 def check_output_blocks(output_blocks):
     """the blocks asked for, deduplicated and ascending (metric/inception.py:84); GccError names the choices otherwise"""
     try:
@@ -195,8 +221,10 @@ class InceptionFidEngine(SlabProgramEngine):
     [N, C, h, w], or with pooled=True as that map's spatial mean [N, C, 1, 1] in f64 (gcc_map_mean: the bf16 route's maps hold
     bf16 values, the mean adds one fp32 rounding); .d is the width of the last block asked for.  Activations are NHWC bf16 with
     one rounding per conv + BatchNorm + ReLU and per average pool; the input resize and the final mean are fp32 arithmetic.
-    precision='fp32': activations, weights and every sum are fp32 (the reference's own arithmetic), one launch per convolution.  The
-    engine's scaffold -- .to(), the slab and its programs, the route check -- is metric/_native.py's."""
+    precision='fp32': activations, weights and every sum are fp32 (the reference's own arithmetic), one launch per convolution.
+    .classifier: (fc.weight [C, d], fc.bias [C]) as fp32 tensors, on the device after .to(device) -- the head the Inception Score
+    reads (inception_score.py; the engine itself never applies it) --, None when the state_dict has no fc.* or the engine stops
+    below block 3.  The engine's scaffold -- .to(), the slab and its programs, the route check -- is metric/_native.py's."""
     BN_EPS = BN_EPS
 
     def __init__(self, state_dict, resize=299, precision='bf16', output_blocks=(3,), pooled=False):
@@ -212,11 +240,19 @@ class InceptionFidEngine(SlabProgramEngine):
         self.resize = int(resize)
         if self.resize <= 0:
             raise GccError('InceptionFidEngine: resize must be positive, got %r' % (resize,))
+        # the classifier (fc.*: the Inception Score's logits) of an engine that runs to the pool features, when the file has one
+        head = parse_classifier(state_dict, self.arch) if self.output_blocks[-1] == 3 else None
         super().__init__(state_dict, self.arch.convs)
+        self._head = None if head is None else tuple(t.detach().to('cpu', torch.float32).contiguous() for t in head)
+        self.classifier = self._head                   # (weight, bias): fp32, on the host until .to(device)
         self._plan(1)                                  # a resize too small for the network is refused here, on the host
 
     def _pack(self, c, master):
         return ops.pack_weights_f32(master) if self.precision == 'fp32' else super()._pack(c, master)
+
+    def _to_extra(self, device):
+        if self._head is not None:
+            self.classifier = tuple(t.to(device) for t in self._head)      # fp32, on the device
 
     # ---- the launch program ---------------------------------------------------------------------------------------------
     def _plan(self, N):

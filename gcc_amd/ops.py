@@ -1464,6 +1464,58 @@ def prdc_ball_count(Q, C, r2, out=None, chunks=0, tile=0, slot='prdc'):
     return out
 
 
+def is_workspace_bytes(C, splits, chunk=0):
+    """gcc_is_workspace: one chunk of logits and [splits][C] + [splits] doubles of state, whatever the number of rows"""
+    return lib().gcc_is_workspace(C, splits, chunk)
+
+
+def _is_operands(what, X, W, b, chunk):
+    """the operands of the classifier head: X [n, d] as _kid_rows takes it, W a contiguous fp32 [C, d] and b a contiguous fp32
+    [C] on X's device, C >= 2, chunk >= 0"""
+    X, xp, xf, ldx, n, d = _kid_rows(X, what)
+    chunk = int(chunk)
+    if not torch.is_tensor(W) or W.dtype != torch.float32 or W.dim() != 2 or W.shape[1] != d or W.shape[0] < 2 or \
+            not W.is_contiguous() or W.device != X.device:
+        raise _lib.GccError('%s: W must be a contiguous fp32 [C >= 2, %d] tensor on %s, got %s'
+                            % (what, d, X.device, '%s %s on %s' % (W.dtype, tuple(W.shape), W.device) if torch.is_tensor(W) else type(W).__name__))
+    C = W.shape[0]
+    if not torch.is_tensor(b) or b.dtype != torch.float32 or b.dim() != 1 or b.numel() != C or not b.is_contiguous() or \
+            b.device != X.device:
+        raise _lib.GccError('%s: b must be a contiguous fp32 [%d] tensor on %s' % (what, C, X.device))
+    if chunk < 0:
+        raise _lib.GccError('%s: chunk = %d, expected 0 (GCC_IS_CHUNK = %d rows) or a positive number of rows' % (what, chunk, _lib.IS_CHUNK))
+    return X, xp, xf, ldx, n, d, C, chunk
+
+
+def is_logits(X, W, b, out=None, chunk=0):
+    """gcc_is_logits: out[i][c] (f64 [n, C] on the device, made if not given) = b[c] + sum_k X[i][k] W[c][k], one k-ascending f64
+    fma chain per element: the classifier head of the Inception network on pool features X [n, d] (fp32 or f64, rows may be
+    strided).  ``chunk``: rows per launch, 0 for GCC_IS_CHUNK (the bits do not depend on it).  Nothing is read back."""
+    X, xp, xf, ldx, n, d, C, chunk = _is_operands('is_logits', X, W, b, chunk)
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float64, device=X.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n, C) or not out.is_contiguous() or out.device != X.device:
+        raise _lib.GccError('is_logits: out must be a contiguous f64 [%d, %d] tensor on %s' % (n, C, X.device))
+    check(lib().gcc_is_logits(xp, xf, ldx, n, d, W.data_ptr(), b.data_ptr(), C, chunk, out.data_ptr(), stream()), 'gcc_is_logits')
+    return out
+
+
+def inception_split_scores(X, W, b, splits=10, chunk=0, slot='inception_score'):
+    """gcc_is_split_scores: f64 [splits] on the device, the Inception Score exp(mean_i KL(p_i || mean_i p_i)) of each of
+    ``splits`` consecutive ranges of the rows of X [n, d], p_i = softmax(W x_i + b).  Rows go through in chunks of ``chunk`` (0:
+    GCC_IS_CHUNK) and no more than one chunk of logits exists at a time; the scores' bits do not depend on it.  Nothing is read
+    back."""
+    X, xp, xf, ldx, n, d, C, chunk = _is_operands('inception_split_scores', X, W, b, chunk)
+    splits = int(splits)
+    if not 1 <= splits <= n:
+        raise _lib.GccError('inception_split_scores: splits = %d, expected 1..%d (every split needs a row of the %d)' % (splits, n, n))
+    out = torch.empty(splits, dtype=torch.float64, device=X.device)
+    ws = workspace(is_workspace_bytes(C, splits, chunk), X.device, slot)
+    check(lib().gcc_is_split_scores(xp, xf, ldx, n, d, W.data_ptr(), b.data_ptr(), C, splits, chunk, out.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), stream()), 'gcc_is_split_scores')
+    return out
+
+
 def conv_eval_rect(x, w, Co, kernel, stride, out, scale=None, shift=None, act=_lib.EVAL_ACT_NONE, slot='eval', route_only=False):
     """inference conv with a (kh, kw) kernel and NO padding (gcc_conv_eval_ex with KH != KW allowed): out = act(scale[c] conv(x, w)
     + shift[c]).  gcc_conv_t has one `pad` for both directions, so a rectangular kernel's own padding (ph, pw) is border_copy's

@@ -9,7 +9,8 @@ Same flags as gcc_amd.train (--pretrain_path is required).  Per model:
   pix2pix (other roots), cyclegan, sagan: with a TorchScript Inception network at GCC_FID_INCEPTION and real_stat*.npz under
             --dataroot, prints the FID of the images written (cyclegan: also of generator B's, which are not written), and
             their KID on the next line when a real_act*.npz (get_real_stat --features_path) lies beside every real_stat*.npz,
-            and with GCC_FID_PRDC=<k> their precision / recall / density / coverage on one more
+            and with GCC_FID_PRDC=<k> their precision / recall / density / coverage on one more; with GCC_FID_IS=<splits> and
+            the native network's weight file their Inception Score (IS: mean +- std over the splits) on the last
   srgan     every test/{Set5, Set14, B100, Urban100} present; the generator through SRResNetEngine.infer, at the precision
             GCC_SR_PRECISION names (bf16, the default, or fp32: the reference's own)
   cyclegan  phase test, visual_forward, visuals real_A / fake_B
@@ -235,6 +236,9 @@ def run(opt, model):
         prdc = fid.prdc()                        # GCC_FID_PRDC=<k>: precision / recall / density / coverage of the same images
         if prdc is not None:
             print(fid_eval.prdc_line(prdc, fid.tags, opt.model))
+        score = fid.inception_score()            # GCC_FID_IS=<splits>: the Inception Score of the same images
+        if score is not None:
+            print(fid_eval.is_line(score, fid.tags, opt.model))
     return result_dir
 
 

@@ -1322,6 +1322,40 @@ int gcc_prdc_kth_dist(const void* X, int x_f64, int ldx, int m, const void* Y, i
 int gcc_prdc_ball_count(const void* Q, int q_f64, int ldq, int m, const void* C, int c_f64, int ldc, int n, int d,
                         const double* r2, int chunks, int tile, int* out, void* ws, size_t ws_bytes, gcc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Inception Score (Salimans et al. 2016) on the same activations: the network's classifier head and the per-split scores
+ * (gcc_amd/csrc/inception_score.hip, gcc_amd/metric/inception_score.py).  Added without a GCC_HIP_ABI bump (additions only).
+ * X [n][ldx]: fp32 (x_f64 == 0) or f64 rows of d elements, row stride ldx >= d elements; what lies between d and ldx, or after
+ * the last row, is never read.  W [C][d] and b [C]: fp32, contiguous.  Any n, d >= 1 and C >= 2; nothing needs to be a multiple
+ * of the tile, the k-step or the chunk.  All arithmetic is f64.
+ * gcc_is_logits: Z[i][c] (f64, [n][C] contiguous) = b[c] + sum_k X[i][k] W[c][k], as ONE chain per element: acc = b[c], then acc =
+ *   fma(X[i][k], W[c][k], acc) for k = 0, 1, ..., d - 1 (and fma(0, 0, acc) up to the next multiple of GCC_IS_KSTEP): the bits of
+ *   Z[i][c] are a function of row i, class c and d alone -- a row alone gives the bits it has in its set, at every `chunk`.
+ * gcc_is_split_scores: scores[s] (f64, s < splits) of split s = rows [s n / splits, (s + 1) n / splits) (integer divisions: the
+ *   original code's slicing), n_s of them.  Per row: m = max_c z_c, S = sum_c exp(z_c - m), logp_c = (z_c - m) - log S, p_c =
+ *   exp(logp_c), h_i = sum_c p_c logp_c where a class with p_c == 0 adds exactly 0.  Per split: mbar_c = (sum_i p_ic) / n_s,
+ *   KL = (sum_i h_i) / n_s - sum_c mbar_c log mbar_c (zero terms skipped), scores[s] = exp(KL).  The mean and the population
+ *   standard deviation of the scores are the host's.
+ * Rows go through in chunks of `chunk` (0: GCC_IS_CHUNK; any positive value forces it), three launches per chunk -- logits by
+ *   GCC_IS_TILE x GCC_IS_TILE tiles over d in steps of GCC_IS_KSTEP, one wave per row, one thread per (split, class) -- and one
+ *   launch at the end.  ws holds one chunk of logits / probabilities and [splits][C] + [splits] doubles of state carried from
+ *   chunk to chunk: gcc_is_workspace(C, splits, chunk) = (chunk C + chunk + splits C + splits) doubles, whatever n is (0 for C <
+ *   2, splits < 1 or chunk < 0).  Order of sums: a row's sums take lane l's classes l, l + 64, ... ascending and fold the lanes
+ *   by xor-shuffles; a split's sums over rows are ONE chain in row order per class, which a chunk edge only interrupts; the sum
+ *   over classes takes thread t's classes t, t + 256, ... and folds lanes, then waves.  Every order is fixed by (n, C, splits):
+ *   the same input gives the same bits, at every `chunk`.  No floating-point atomics, no workgroup waits for another.
+ * GCC_ERR_BAD_ARG (a null pointer, n or d < 1, C < 2, ldx < d, chunk < 0, splits < 1, n < splits), GCC_ERR_UNSUPPORTED (2^31
+ *   workgroups or more) and GCC_ERR_WORKSPACE (ws_bytes short) are returned before anything is launched.
+ * --------------------------------------------------------------------------------------------- */
+#define GCC_IS_TILE 64
+#define GCC_IS_KSTEP 16
+#define GCC_IS_CHUNK 4096
+size_t gcc_is_workspace(int C, int splits, int chunk);
+int gcc_is_logits(const void* X, int x_f64, int ldx, int n, int d, const float* W, const float* b, int C, int chunk, double* Z,
+                  gcc_stream_t stream);
+int gcc_is_split_scores(const void* X, int x_f64, int ldx, int n, int d, const float* W, const float* b, int C, int splits,
+                        int chunk, double* scores, void* ws, size_t ws_bytes, gcc_stream_t stream);
+
 /* ---- gradient exchange ---------------------------------------------------------------------------------
  * The reference trains on one device (models/Pix2Pix.py:356); the data-parallel path sums the five optimizers' flat fp32
  * gradient buffers over ranks before each `optimizer.step()` (train.py has no counterpart: this is the exchange a
